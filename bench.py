@@ -1,20 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: effective GFLOP/s of dgemm_compressed (2-bit SNP x fp64) on N MI355X.
 
-python bench.py --gpus N --steps K --warmup W   (N > 1: launched by torch.distributed.run, one rank per GPU; without a launcher: SNP shards behind the C ABI)
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    (N > 1: launched by torch.distributed.run, one rank per GPU; without a launcher: SNP shards behind the C ABI)
+
+A plain run measures the headline and nothing else: stage the workload, W warm-up steps, K timed steps, the outputs of the last timed step to DIR
+(--dump-outputs), one JSON line.  Everything below that is not `value` (checks, legs, roofline traffic, bench_detail.json) runs with --full only.
 
 Workload (BASELINE.json configs[1]): 1M SNPs x 50k individuals, n = 32, dgemm_compressed 'N' and 'T', uncentred, synthetic PLINK data generated on
 the device.  One step = one 'N' multiply (+ the fp64 reduction of the indiv x n result when N > 1) and one 'T' multiply; flops per step =
 2 * (2 * snps * indiv * n).  Inputs (packed genotypes, B, C) are resident in HBM when the timed region starts.  N > 1: the SNP dimension is sharded
 (strong scaling, total work fixed).
 
-Order of a run: setup_process / stage_headline -> ONE untimed step checked against the oracle (oracle_check: every N, every form; a violation ends the run
+Order of a --full run: setup_process / stage_headline -> ONE untimed step checked against the oracle (oracle_check: every N, every form; a violation ends the run
 without a number) -> warm-up -> the timed region (run_timed: `value`) -> legs that never feed `value`: per_rank (launcher) or per_shard + the other
 reduction + hub operands (in-process N > 1), opt-in engines, abi_end_to_end, cpu_baseline (+ the check against the CPU library), and at N = 1 the other
 BASELINE configs under their own checkers (config5_cg_step, config4_shard, config3_crossprod, the full-extent legs).
 
-Output: ONE compact JSON line on stdout (compact_line: <= 4 KB -- the contract's keys, roofline, cpu_baseline + cpu_baseline_port, check, who reduced,
-one number per leg: c3_* crossproduct, c4_* config 4, c5_* CG step) and everything measured in bench_detail.json beside this file."""
+Output: ONE compact JSON line on stdout (compact_line: <= 4 KB -- the contract's keys, roofline, who reduced; with --full also cpu_baseline +
+cpu_baseline_port, check, one number per leg: c3_* crossproduct, c4_* config 4, c5_* CG step) and, with --full, everything measured in bench_detail.json
+beside this file."""
 import argparse
 import ctypes
 import json
@@ -1071,6 +1076,72 @@ def opt_in_engine_leg(W, L, args, step, sync, engine, flops_step, description):
     return out
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs writes at most this much in all
+
+
+def dump_rows(total_rows, n):
+    """the rows of a total_rows x n fp64 result that --dump-outputs writes when the two results do not fit DUMP_BYTES whole: at most half the budget per
+    result (8 bytes per row extra for its row number), as a fixed seeded sample in ascending order.  None = all rows."""
+    import numpy as np
+    cap = DUMP_BYTES // 2 // (8 * n + 8)
+    if total_rows <= cap:
+        return None
+    return np.sort(np.random.default_rng(12345).choice(total_rows, cap, replace=False))
+
+
+def gather_T_rows(W, rows, snps):
+    """host copy (numpy) of the rows `rows` (global SNP numbers, ascending; None = all) of the 'T' result, from wherever they live: the one C_T, the shards'
+    slices (in-process), or every rank's block, gathered on rank 0 (launcher; None on the other ranks)"""
+    import numpy as np
+    torch, dist = W.torch, W.dist
+    rows = np.arange(snps) if rows is None else rows
+    if W.inprocess:
+        parts = []
+        for (b1, e1), c in zip(W.bounds, W.CT_s):
+            sel = rows[(rows >= b1) & (rows < e1)] - b1
+            parts.append(c[torch.from_numpy(sel).to(c.device)].cpu().numpy())
+        return np.concatenate(parts)
+    sel = rows[(rows >= W.begin) & (rows < W.end)] - W.begin
+    mine = W.C_T[torch.from_numpy(sel).to(W.device)]
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return mine.cpu().numpy()
+    from miraculix_amd.distributed import shard_bounds
+    world = dist.get_world_size()
+    counts = []
+    for r in range(world):
+        b1, e1 = shard_bounds(snps, world, r)
+        counts.append(int(((rows >= b1) & (rows < e1)).sum()))
+    cdev = torch.device("cpu") if dist.get_backend() != "nccl" else W.device
+    buf = torch.zeros((max(counts), mine.shape[1]), dtype=torch.float64, device=cdev)
+    buf[: len(sel)] = mine.to(cdev)
+    got = [torch.zeros_like(buf) for _ in range(world)]
+    dist.all_gather(got, buf)
+    if dist.get_rank() != 0:
+        return None
+    return np.concatenate([g[:c].cpu().numpy() for g, c in zip(got, counts)])
+
+
+def dump_outputs(W, args):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the path receives it, in float64 -- C_N.npy, the 'N' product (indiv x ncol,
+    reduced over shards / ranks), and C_T.npy, the 'T' product (snps x ncol).  A result too large for the budget (DUMP_BYTES) is written as a fixed seeded
+    sample of its rows, with their row numbers in <name>_rows.npy.  The inputs come from fixed seeds: two builds run with the same arguments compare
+    output for output."""
+    import numpy as np
+    n = args.ncol
+    whole = 8 * n * (args.indiv + args.snps) <= DUMP_BYTES
+    rows_N = None if whole else dump_rows(args.indiv, n)
+    rows_T = None if whole else dump_rows(args.snps, n)
+    C_T = gather_T_rows(W, rows_T, args.snps)        # (a collective under the launcher: every rank takes part)
+    if W.rank != 0:
+        return
+    C_N = W.C_N.cpu().numpy() if rows_N is None else W.C_N[W.torch.from_numpy(rows_N).to(W.device)].cpu().numpy()
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, arr, rows in (("C_N", C_N, rows_N), ("C_T", C_T, rows_T)):
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+        if rows is not None:
+            np.save(os.path.join(args.dump_outputs, name + "_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1092,9 +1163,18 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the legs for BASELINE configs 3, 4 (shard) and 5 (shard)")
     ap.add_argument("--configs-scale", type=float, default=1.0, help=argparse.SUPPRESS)   # rehearsals shrink the config legs
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline traffic (rocprofv3 --pmc children), the oracle and adjoint checks of the results, the opt-in int8 "
+                         "engines, the ABI end-to-end leg, the CPU baseline, the other reduction and hub operands (in-process N > 1), the all-reduce alone "
+                         "(launcher), the other BASELINE configs, bench_detail.json.  The --no-* options switch single legs off again.")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/C_N.npy and DIR/C_T.npy (float64, <= 60 MB in all: a fixed "
+                         "sample of rows, numbered in DIR/<name>_rows.npy, where a result is larger)")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
+    if not args.full:   # a plain run: the headline only
+        args.no_pmc = args.no_cpu_baseline = args.no_alt_engine = args.no_abi = args.no_configs = True
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints a version banner when its communicator comes up, i.e. on every
     # N > 1 run): keep the real stdout aside for the line and send everything else that reaches fd 1 to stderr.
     sys.stdout.flush()
@@ -1105,7 +1185,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     inprocess = world == 1 and args.gpus > 1
     # roofline.traffic is measured first, before this process touches the GPU (N = 1 only; the children profile the same workload)
-    traffic, traffic_detail = None, {"skipped": "N > 1" if (world > 1 or inprocess) else "--no-pmc"}
+    traffic, traffic_detail = None, {"skipped": "N > 1" if (world > 1 or inprocess) else "--no-pmc" if args.full else "plain run (--full measures it)"}
     if world == 1 and not inprocess and not args.no_pmc:
         traffic, traffic_detail = measure_traffic(args)
 
@@ -1147,9 +1227,12 @@ def main():
                 except RuntimeError:
                     pass
     # ---- parity first ("parity check on every run ... before timing counts"): one untimed step, both results against the oracle, for every N
-    step()
-    sync()
-    chk = oracle_check(W, args)
+    # (--full; a plain run goes straight to its warm-up)
+    chk = None
+    if args.full:
+        step()
+        sync()
+        chk = oracle_check(W, args)
     for _ in range(args.warmup):
         step()
     sync()
@@ -1176,7 +1259,9 @@ def main():
                           "rccl_vs_p2p_max_rel_diff": info0["rccl_vs_p2p_max_rel_diff"], "devices": info0["devices"],
                           "peer_access_to_root": [s["peer_to_root"] for s in info0["per_shard"]]}
     launches, total_ms = kernel_profile(L)
-    adj_err = adjoint_check(W)
+    if args.dump_outputs:
+        dump_outputs(W, args)
+    adj_err = adjoint_check(W) if args.full else None
     flops_step = 2 * 2.0 * snps * indiv * n
     value = flops_step * args.steps / dt * 1e-9
     ms_per_step = dt / args.steps * 1e3
@@ -1195,7 +1280,7 @@ def main():
     # in-process N > 1, extra (never `value`): (i) the same steps with the RCCL reduction (its first product is cross-checked against the
     # peer-to-peer one inside the library), (ii) the hub variant: all of B / C on the first device through the plain dgemm_compressed symbol
     extra_multi = None
-    if W.inprocess:
+    if W.inprocess and args.full:
         extra_multi = {}
         other = "p2p" if reduction == "rccl" else "rccl"
         key = other + "_reduction"
@@ -1230,7 +1315,7 @@ def main():
     # N > 1 under the launcher: what every rank's dominant kernel took, and what the all-reduce of the indiv x n result costs on its own
     # (untimed extra pass), so that a scaling curve explains itself
     per_rank = None
-    if dist.is_initialized():
+    if dist.is_initialized() and args.full:
         km = torch.tensor([avg_ms], dtype=torch.float64, device=W.device)
         allk = [torch.zeros_like(km) for _ in range(dist.get_world_size())]
         dist.all_gather(allk, km)
@@ -1315,7 +1400,6 @@ def main():
                                    + (" inside one process behind the C ABI (MIRACULIX_NUM_GPUS), operands per shard on the shards' devices" if W.inprocess else ""),
                        "snps": snps, "indiv": indiv, "ncol": n, "parallelism": f"snp-shard{W.n_gpus}",
                        "genotypes": "p_s ~ U(0.1, 0.6), g ~ Binomial(2, p_s), no missings; B ~ N(0, 1)"},
-            "check": {"adjoint_identity_max_rel_err": adj_err, "adjoint_tolerance": 1e-10, **chk},
             "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / FP64_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
                          "traffic_unit": "GB per launch, measured by this run (two rocprofv3 --pmc child passes of the same workload)", "traffic_detail": traffic_detail,
@@ -1323,6 +1407,8 @@ def main():
                          "kernel": "k_gemm<8,8,3> on v_mfma_f64_4x4x4_4b_f64, two launches per step on the ONE stored (SNP-major) copy: 'N' = k_gemm<8, 8, 3, false, true> "
                                    "(transposed-operand form), 'T' = k_gemm<8, 8, 3, false, false> (plain form); same tile, same permuted K order, same rate", "launches": launches, "avg_launch_ms": round(avg_ms, 3)},
         }
+        if args.full:
+            out["check"] = {"adjoint_identity_max_rel_err": adj_err, "adjoint_tolerance": 1e-10, **chk}
         if W.n_gpus > 1:
             slowest = max(per_rank["avg_k_gemm_launch_ms"]) if per_rank is not None else avg_ms
             out["predicted_ms_per_step_from_per_shard"] = predicted_step_ms(W.n_gpus, snps, indiv, n, slowest)
@@ -1330,7 +1416,7 @@ def main():
             out["per_rank"] = per_rank
         if per_shard is not None:
             out["per_shard"] = per_shard
-            out.update(extra_multi)
+            out.update(extra_multi or {})
         if alt is not None:
             out["opt_in_engine"] = alt
         if alt_exact is not None:
@@ -1377,15 +1463,14 @@ def main():
         if bad:
             raise SystemExit(f"bench.py: parity check failed in {bad}: {json.dumps({k: out[k] for k in bad})}")
     if W.rank == 0:
-        # everything measured goes to bench_detail.json (next to this file, and to gpurun_out/ when that exists); the ONE line on stdout is its compact
-        # summary (<= 4 KB, so that the driver's record keeps every leg)
-        for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
-            if os.path.isdir(d):
-                try:
-                    with open(os.path.join(d, "bench_detail.json"), "w") as fh:
-                        json.dump(out, fh, indent=1)
-                except OSError:
-                    pass
+        # --full: everything measured goes to bench_detail.json next to this file; the ONE line on stdout is its compact summary (<= 4 KB, so that a
+        # record of the run keeps every leg).  A plain run writes the line alone.
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, "bench_detail.json"), "w") as fh:
+                    json.dump(out, fh, indent=1)
+            except OSError:
+                pass
         line = json.dumps(compact_line(out), separators=(",", ":"))
         assert len(line) <= 4096, len(line)
         sys.stdout.flush()
@@ -1409,9 +1494,10 @@ def compact_line(d):
         if k in d:
             b = d[k]
             line[k] = {"value": b["value"], "unit": b["unit"], "cores": b["cores"], "kind": b["kind"].split(" (")[0], "sample": b["sample"].split(", one 'N'")[0]}
-    ck = d["check"]
-    line["check"] = {k: ck[k] for k in ("oracle_T_max_rel_err", "oracle_N_max_rel_err", "rows_T", "rows_N", "tol", "adjoint_identity_max_rel_err",
-                                        "gpu_T_rows_vs_cpu_library_max_rel_err", "gpu_N_64_sampled_rows_vs_dense_oracle_max_rel_err") if k in ck}
+    ck = d.get("check")
+    if ck is not None:
+        line["check"] = {k: ck[k] for k in ("oracle_T_max_rel_err", "oracle_N_max_rel_err", "rows_T", "rows_N", "tol", "adjoint_identity_max_rel_err",
+                                            "gpu_T_rows_vs_cpu_library_max_rel_err", "gpu_N_64_sampled_rows_vs_dense_oracle_max_rel_err") if k in ck}
     line["reduction"] = d["reduction"][:90]
     for k in ("world_size", "backend", "shards", "rccl_ranks", "rccl_checked", "devices", "peer_access_to_rank0", "peer_access_to_root"):
         if k in d:
@@ -1462,7 +1548,8 @@ def compact_line(d):
         line["legs_parity_ok"] = True          # (the legs ran; a violated leg check ends the run before this line is printed)
     if failed:
         line["legs_failed"] = failed
-    line["detail"] = "bench_detail.json"
+    if "check" in d:   # (--full: the detail file was written)
+        line["detail"] = "bench_detail.json"
     return line
 
 

@@ -222,19 +222,24 @@ def test_kernels_with_hand_counted_vmcnt_have_no_scratch_traffic(built, tmp_path
 def test_reference_fortran_programs_bind_only_symbols_this_library_exports(built):
     """oracle/Makefile.ref_fortran links the reference's own (unmodified) Fortran tests and benchmark harness against libmiraculix_amd.so: every symbol their
     binding modules leave undefined (bind(C) names of mod5codesapi.f90 / modmiraculix_gpu.f90) must be one this library exports -- the link itself proves
-    it; here the list is written out.  (No compute: the programs run in tests/test_reference_fortran_gpu.py.)  Skipped where they are not built."""
+    it; here the list is written out.  (No compute: the programs run in tests/test_reference_fortran_gpu.py.)  Where they are not built, the lists
+    recorded from them (tests/golden/make_golden_fortran_symbols.py) stand in; where they are, the recorded lists must still be theirs."""
+    import json
     bindir = os.path.join(ROOT, "oracle", "_ref", "fortran")
-    progs = [os.path.join(bindir, p) for p in ("test_5codesapi.out", "test_5codesapi_t.out", "test_solve.out", "benchmark.out")]
-    if not all(os.path.exists(p) for p in progs):
-        pytest.skip("oracle/_ref/fortran not built (needs /root/reference and flang)")
+    recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_fortran_symbols.json")))
     exported = {ln.split()[-1].split("@")[0] for ln in subprocess.check_output(["nm", "-D", "--defined-only", LIB], text=True).splitlines() if ln.strip()}
     api = {"setOptions_compressed", "plink2compressed", "dgemm_compressed", "free_compressed", "get_compressed_freq", "sparse_times_plink",
            "sparse2gpu", "dcsrtrsv_solve_gpu", "potrs_solve_gpu", "free_sparse_gpu", "snp_multiply_gpu"}
     bound = set()
-    for p in progs:
-        needed = subprocess.check_output(["readelf", "-d", p], text=True)
+    for name in ("test_5codesapi.out", "test_5codesapi_t.out", "test_solve.out", "benchmark.out"):
+        p = os.path.join(bindir, name)
+        needed, undef = " ".join(recorded[name]["needed"]), set(recorded[name]["undefined"])
+        if os.path.exists(p):
+            live_needed = subprocess.check_output(["readelf", "-d", p], text=True)
+            live_undef = {ln.split()[-1].split("@")[0] for ln in subprocess.check_output(["nm", "-D", "--undefined-only", p], text=True).splitlines() if ln.strip()}
+            assert live_undef & api == undef & api, name
+            needed, undef = live_needed, live_undef
         assert "libmiraculix_amd.so" in needed
-        undef = {ln.split()[-1].split("@")[0] for ln in subprocess.check_output(["nm", "-D", "--undefined-only", p], text=True).splitlines() if ln.strip()}
         bound |= undef & api
         assert (undef & api) <= exported
     assert {"setOptions_compressed", "plink2compressed", "dgemm_compressed", "free_compressed", "sparse2gpu", "dcsrtrsv_solve_gpu", "free_sparse_gpu"} <= bound

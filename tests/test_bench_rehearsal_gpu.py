@@ -1,7 +1,8 @@
 """bench.py's control flow for every form the driver runs, on a one-GPU box: N = 1, N = 2 in-process (virtual shards behind the C ABI) and N = 2 under the
 launcher (two ranks on cuda:0 with gloo in place of RCCL: MXA_BENCH_SINGLE_DEVICE / MXA_BENCH_BACKEND rehearsal knobs).  Checks the contract of the JSON line
-(<= 4 KB, the compact keys), that every form validates itself against the oracle before timing counts (`check.oracle_*`), that a deliberately mis-cut shard
-boundary ends the run WITHOUT a number, and the detail file bench_detail.json.  Not a measurement."""
+(<= 4 KB, the compact keys), that every form validates itself against the oracle before timing counts under --full (`check.oracle_*`), that a deliberately
+mis-cut shard boundary ends such a run WITHOUT a number, the detail file bench_detail.json, and that a plain run is the headline alone and dumps the outputs
+of its last timed step (--dump-outputs).  Not a measurement."""
 import json
 import os
 import socket
@@ -36,7 +37,7 @@ def _launch(extra_env=None, extra_args=()):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, MXA_BENCH_SINGLE_DEVICE="1", MXA_BENCH_BACKEND="gloo", **(extra_env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL + list(extra_args)
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL + list(extra_args)
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
 
 
@@ -65,7 +66,7 @@ def test_bench_two_ranks_miscut_shard_boundary_aborts_without_a_number():
 
 
 def _run_bench(extra, env=None, check=True):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--configs-scale", "0.02"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + SMALL + ["--configs-scale", "0.02"] + extra
     r = subprocess.run(cmd, env=dict(os.environ, **(env or {})), capture_output=True, text=True, timeout=900, cwd=ROOT)
     return _line_and_detail(r) if check else r
 
@@ -149,3 +150,34 @@ def test_bench_inprocess_miscut_shard_boundary_aborts_without_a_number():
     r = _run_bench(["--gpus", "2", "--no-alt-engine", "--no-abi", "--no-configs"], env={"MXA_BENCH_TEST_MISCUT": "1"}, check=False)
     assert r.returncode != 0 and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")], r.stdout[-800:]
     assert "differ from the oracle" in r.stderr, r.stderr[-1500:]
+
+
+def _run_plain(extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-1500:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """python bench.py without --full: the contract's keys for exactly --steps timed steps, no check, no leg, no detail file; --dump-outputs writes the two
+    products of the last timed step as float64, and they are those of a --full run of the same arguments, which checks them against the oracle"""
+    import numpy as np
+    detail = os.path.join(ROOT, "bench_detail.json")
+    stamp = os.path.getmtime(detail) if os.path.exists(detail) else None
+    line = _run_plain(["--dump-outputs", str(tmp_path / "plain")])
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "f64" and line["unit"] == "GFLOP/s"
+    assert line["higher_is_better"] is True and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 4.0 * 60002 * 8000 * 32 / (line["ms_per_step"] * 1e-3) * 1e-9) <= 1e-2 * line["value"]     # value and ms_per_step: the same steps
+    assert line["roofline"]["launches"] == 2 * 2 and line["roofline"]["traffic"] is None                                    # two k_gemm launches per timed step
+    for k in ("check", "cpu_baseline", "cpu_baseline_port", "abi_GFLOPs", "engine_i8_GFLOPs", "c3_ms_f4", "c5_step_ms", "legs_parity_ok", "detail"):
+        assert k not in line, k
+    assert (os.path.getmtime(detail) if os.path.exists(detail) else None) == stamp
+    assert sorted(os.listdir(tmp_path / "plain")) == ["C_N.npy", "C_T.npy"]
+    full, _ = _line_and_detail(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-pmc", "--no-cpu-baseline", "--no-alt-engine", "--no-abi",
+                                               "--no-configs", "--dump-outputs", str(tmp_path / "full")] + SMALL, capture_output=True, text=True, timeout=600, cwd=ROOT))
+    _check_self_validation(full, 1)
+    for name, rows in (("C_N", 8000), ("C_T", 60002)):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == b.shape == (rows, 32)
+        assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max(), name

@@ -1,6 +1,6 @@
 """CPU tests of the oracle (test infrastructure): pinned against the golden fixtures emitted by the reference's own CPU
-library (tests/golden/make_golden.py), against the analytic oracles of the reference's tests, and - where the reference
-build travelled (oracle/_ref) - against the reference library itself."""
+library (tests/golden/make_golden.py), against the analytic oracles of the reference's tests, and against the reference library itself
+where its build travelled (oracle/_ref), else its stored outputs for the same case."""
 import os
 
 import numpy as np
@@ -9,6 +9,7 @@ import pytest
 from _util import Oracle, have_reference, make_B, make_problem, pack_plink, run_reference
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dgemm_golden.npz")
+PORT_CHECK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "port_check_golden.npz")
 
 
 @pytest.fixture(scope="module")
@@ -147,14 +148,19 @@ def test_crossprod_oracle_missing_byte_table(oracle):
     assert M[0, 0] == 0 + 1 + 4 + 0 + 9 * 4
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference CPU library (oracle/_ref) not built here")
 def test_port_vs_live_reference_library(oracle):
-    prob = make_problem(1500, 700, 9, seed=77)
-    h = oracle.five_create(prob, 8)
+    """make_problem(1500, 700, 9, seed=77), 'N' / 'T', uncentred / centred: the port against the reference library itself where its build travelled
+    (oracle/_ref), and everywhere against what that library wrote for the same inputs (tests/golden/make_golden_port_check.py)"""
+    g = np.load(PORT_CHECK)
+    snps, indiv, n, cores = [int(x) for x in g["dims"]]
+    prob = dict(snps=snps, indiv=indiv, plink=np.ascontiguousarray(g["plink"]), plink_t=np.ascontiguousarray(g["plink_t"]), f=np.ascontiguousarray(g["f"]))
+    h = oracle.five_create(prob, cores)
     for trans in (0, 1):
-        k = 700 if trans else 1500
-        B = make_B(k, 9, seed=5)
+        B = np.ascontiguousarray(g[f"B{trans}"])
         for centered in (0, 1):
-            ref, _ = run_reference(prob, trans, B, centered, cores=8)
+            ref = g[f"C{trans}{centered}"]
+            if have_reference():
+                live, _ = run_reference(prob, trans, B, centered, cores=cores)
+                assert np.array_equal(live, ref)
             assert np.array_equal(oracle.five_dgemm(h, trans, prob, B, centered), ref)
     oracle.five_free(h)

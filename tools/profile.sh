@@ -4,7 +4,7 @@
 # Everything is written under gpurun_out/<round>/ (scratch; MXA_ROUND, default r06); what is worth keeping is copied to profiles/ by hand.
 # Targets:
 #   tests [pytest args]  all -m gpu tests + smoke(); full log in gputests_full.txt
-#   bench [bench args]   default bench.py line -> bench_n1.json (+ bench_detail.json)
+#   bench [bench args]   bench.py --full line -> bench_n1.json (+ bench_detail.json)
 #   stats                bench.py (headline only) under rocprofv3 --kernel-trace --stats -> bench_n1_kernel_stats.csv
 #   pmc-mfma <gemm|i8|xprod_f4|xprod_i8>        SQ counter pass (MFMA busy, clock, waits) of one kernel family -> pmc_mfma_util_<t>.json
 #   pmc-traffic <gemm|i8|gram|xprod_f4|xprod_i8>  FETCH_SIZE / WRITE_SIZE passes (separate runs) -> pmc_traffic_<t>.txt
@@ -43,7 +43,7 @@ tests)
   tail -c 6000 "$O/gputests_full.txt"; tail -6 "$O/gputests_full.txt" > "$O/gputests.txt"; [ $rc = 0 ] &&
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a "$O/gputests.txt" ;;
 bench)
-  timeout -k 10 1100 python bench.py "$@" > "$O/bench_n1.json" 2> "$O/bench_n1.stderr"; rc=$?
+  timeout -k 10 1100 python bench.py --full "$@" > "$O/bench_n1.json" 2> "$O/bench_n1.stderr"; rc=$?
   cp -f bench_detail.json "$O/bench_detail.json" 2>/dev/null
   tail -c 4500 "$O/bench_n1.json"; tail -3 "$O/bench_n1.stderr"; exit $rc ;;
 stats)
@@ -100,11 +100,11 @@ xprod)
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)
-  timeout -k 10 500 python bench.py --gpus 8 --steps 5 --warmup 1 > "$O/bench_inprocess_8_virtual_shards.json" 2> "$O/inprocess8.err" || { tail -5 "$O/inprocess8.err"; exit 1; }
+  timeout -k 10 500 python bench.py --full --gpus 8 --steps 5 --warmup 1 > "$O/bench_inprocess_8_virtual_shards.json" 2> "$O/inprocess8.err" || { tail -5 "$O/inprocess8.err"; exit 1; }
   cp -f bench_detail.json "$O/bench_detail_inprocess_8_virtual_shards.json"
   for n in 2 4; do
     MXA_BENCH_SINGLE_DEVICE=1 MXA_BENCH_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2957$n \
-      bench.py --gpus $n --steps 5 --warmup 1 > "$O/launcher_${n}ranks.log" 2>&1 || { tail -5 "$O/launcher_${n}ranks.log"; exit 1; }
+      bench.py --full --gpus $n --steps 5 --warmup 1 > "$O/launcher_${n}ranks.log" 2>&1 || { tail -5 "$O/launcher_${n}ranks.log"; exit 1; }
     grep '^{' "$O/launcher_${n}ranks.log" > "$O/bench_launcher_${n}_ranks_one_gpu_gloo.json"
   done
   for f in "$O"/bench_inprocess_8_virtual_shards.json "$O"/bench_launcher_*_ranks_one_gpu_gloo.json; do echo "== $f"; cat "$f"; done ;;

@@ -103,15 +103,16 @@ struct XPost {
 };
 // The two divisions of the reference (by the scalar c, by sigma_i and sigma_j) are multiplications by reciprocals formed once (<= 1 ulp from the
 // quotient; the stated tolerance of this path is 1e-12): an fp64 division is ~15 instructions on the pipe the epilogue shares with nothing else.
+// Every map is symmetric in (i, j) bit for bit -- the per-index operands are combined by a commutative operation first -- so that element (i, j) and
+// element (j, i) of a GRM / LD result are equal (the reference's order, two rank-1 updates one after the other, rounds them differently).
 __device__ __forceinline__ double grm_map(double v, double cs_i, double cs_j, double inv_n, double tot_nn, double inv_c, int do_scale) {
-  v = fma(-cs_i, inv_n, v);       // BLAS.ger!(-1/indiv, col_sum, one_vector, M)
-  v = fma(-cs_j, inv_n, v);       // BLAS.ger!(-1/indiv, one_vector, col_sum, M)
-  v = v + tot_nn;                 // M .+= sum(col_sum) / indiv^2
-  if (do_scale) v *= inv_c;       // M ./= 2 sum f (1 - f)
+  v = fma(-(cs_i + cs_j), inv_n, v);   // BLAS.ger!(-1/indiv, col_sum, one_vector, M); BLAS.ger!(-1/indiv, one_vector, col_sum, M)  (cs_i + cs_j: exact integers)
+  v = v + tot_nn;                      // M .+= sum(col_sum) / indiv^2
+  if (do_scale) v *= inv_c;            // M ./= 2 sum f (1 - f)
   return v;
 }
-__device__ __forceinline__ double ld_center_map(double v, double f_i, double f_j, double four_indiv) { return fma(-four_indiv * f_i, f_j, v); }   // syr!('U', -4 indiv, f, M)
-__device__ __forceinline__ double ld_scale_map(double v, double is_i, double is_j) { return v * is_i * is_j; }                                    // M ./= sigma; M ./= sigma' (is = 1 / sigma)
+__device__ __forceinline__ double ld_center_map(double v, double f_i, double f_j, double four_indiv) { return fma(-four_indiv, f_i * f_j, v); }   // syr!('U', -4 indiv, f, M)
+__device__ __forceinline__ double ld_scale_map(double v, double is_i, double is_j) { return v * (is_i * is_j); }                                  // M ./= sigma; M ./= sigma' (is = 1 / sigma)
 
 // Epilogue shared by both engines.  32x32 C/D map: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5); element (gi, gj) = M[gi][gj].
 // The output holds columns [c0, ..) of M with leading dimension ld (whole matrix: c0 = 0, ld = n).

@@ -209,3 +209,96 @@ def run_reference(prob, trans, B, centered, ldc=None, variant=256, cores=8, reps
         raw = np.fromfile(fout, dtype=np.float64)
     C = raw[: n * ldc].reshape(n, ldc)
     return C, float(raw[n * ldc])
+
+
+# ====================================================================================================== sampled-rows checker of the tests
+# A checker of its own for the full-size fp64 tests, independent of bench.py's check_sample (which the bench legs use): the sampled packed rows are
+# unpacked here with numpy, the reference is summed here in long double, and the "got" values are read from C by one gather of (row, column) pairs.
+SAMPLE_RTOL = 1e-11   # stated fp64 tolerance of the dgemm path: max|C - C_ref| <= 1e-11 max|C_ref|
+
+
+def unpack_2bit(P, k, is_plink=True):
+    """packed rows (rows x ceil(k/4) uint8, 4 fields per byte, low bits first) -> rows x k int8.  PLINK codes decode as the dgemm path reads them:
+    00 -> 0, 01 (missing) -> 0, 10 -> 1, 11 -> 2; raw fields are the values."""
+    P = np.ascontiguousarray(P, dtype=np.uint8)
+    V = np.stack([(P >> (2 * q)) & 3 for q in range(4)], axis=-1).reshape(P.shape[0], -1)[:, :k]
+    if is_plink:
+        V = np.where(V >= 2, V - 1, 0)
+    return V.astype(np.int8)
+
+
+def _to_numpy(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def take_sample(torch, S, nsample, seed):
+    """nsample individuals (rows of the individual-major S["plink_t"]) and nsample SNPs (rows of the SNP-major S["plink"]) chosen by a generator
+    seeded with `seed`, their packed rows copied to the host.  S: dict(snps, indiv, plink, plink_t, f) with device tensors."""
+    snps, indiv = S["snps"], S["indiv"]
+    rng = np.random.default_rng(seed)
+    ii = np.sort(rng.choice(indiv, min(nsample, indiv), replace=False))
+    ss = np.sort(rng.choice(snps, min(nsample, snps), replace=False))
+    rows_t = S["plink_t"].index_select(0, torch.as_tensor(ii, device=S["plink_t"].device))
+    rows_s = S["plink"].index_select(0, torch.as_tensor(ss, device=S["plink"].device))
+    return dict(snps=snps, indiv=indiv, f=_to_numpy(S["f"]), ii=ii, ss=ss, rows_t=_to_numpy(rows_t), rows_s=_to_numpy(rows_s))
+
+
+def check_sampled_rows(sample, trans, B, C, cols, centered, row_offset=0, rtol=SAMPLE_RTOL):
+    """Sampled rows of C = op(Z - 2 f 1^T) B ('N': C indiv x n, rows = individuals sample["ii"] from sample["rows_t"]; 'T': C snps x n, rows = SNPs
+    sample["ss"] from sample["rows_s"]), columns `cols`, against a long-double sum over the numpy-unpacked packed rows.  C (numpy or torch, any strides)
+    may be the row block of the result that starts at row `row_offset`.  Returns dict(err = max|got - ref| / max|ref|, bound_ratio = max over the sampled
+    elements of |got - ref| / elementwise_bound (4 K 2^-53 times the magnitude of the sum), ok = err <= rtol and bound_ratio <= 1).  The long-double
+    reference is within K 2^-64 of that magnitude: 1/8192 of the bound."""
+    snps, indiv = sample["snps"], sample["indiv"]
+    f = _to_numpy(sample["f"]).astype(np.float64)
+    cols = np.asarray(cols, dtype=np.int64)
+    Bs = _to_numpy(B[:, [int(c) for c in cols]] if hasattr(B, "detach") else np.asarray(B)[:, cols]).astype(np.float64)    # k x len(cols)
+    if not trans:
+        rows, k = np.asarray(sample["ii"]), snps
+        Z = unpack_2bit(sample["rows_t"], snps)                                       # nsample x snps
+        shift = np.broadcast_to(2.0 * f.astype(np.longdouble)[None, :], Z.shape)      # z_is - 2 f_s
+    else:
+        rows, k = np.asarray(sample["ss"]), indiv
+        Z = unpack_2bit(sample["rows_s"], indiv)                                      # nsample x indiv
+        shift = np.broadcast_to(2.0 * f[rows].astype(np.longdouble)[:, None], Z.shape)   # z_si - 2 f_s
+    assert Bs.shape[0] == k, (Bs.shape, k)
+    Bl = Bs.astype(np.longdouble)
+    ref = np.empty((len(rows), len(cols)), dtype=np.float64)
+    for q in range(len(rows)):
+        zc = Z[q].astype(np.longdouble) - (shift[q] if centered else 0.0)
+        ref[q] = (zc @ Bl).astype(np.float64)
+    r = rows - row_offset
+    if hasattr(C, "detach"):
+        import torch
+        got = C[torch.as_tensor(r, device=C.device)[:, None], torch.as_tensor(cols, device=C.device)[None, :]].cpu().numpy()
+    else:
+        got = np.asarray(C)[r[:, None], cols[None, :]]
+    diff = np.abs(got - ref)
+    err = float(diff.max() / np.abs(ref).max()) if np.abs(ref).max() > 0 else float(diff.max())
+    # the hard element-wise bound on the sub-problem of the sampled rows (SNP-major packing of the unpacked values)
+    if not trans:
+        prob = dict(snps=snps, indiv=len(rows), plink=pack_plink(np.ascontiguousarray(Z.T)), f=f)
+    else:
+        prob = dict(snps=len(rows), indiv=indiv, plink=pack_plink(Z), f=np.ascontiguousarray(f[rows]))
+    bound = elementwise_bound(Oracle(), trans, prob, np.ascontiguousarray(Bs.T), centered).T        # nsample x len(cols)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0, diff / bound, np.where(diff == 0, 0.0, np.inf))
+    ratio = float(ratio.max())
+    ok = bool(np.all(np.isfinite(got)) and err <= rtol and ratio <= 1.0)
+    return dict(err=err, bound_ratio=ratio, ok=ok)
+
+
+def second_opinion_on_check_sample(monkeypatch, bench):
+    """Wrap bench.check_sample (through monkeypatch) so that every (B, C) a bench leg checks also goes through check_sampled_rows, on the same sample
+    and the same columns; returns the list the verdicts are appended to.  The leg's own result is returned unchanged."""
+    verdicts = []
+    orig = bench.check_sample
+
+    def both(torch, sample, trans, Bdev, Cdev, cols, centered, row_offset=0, want_bound=False):
+        out = orig(torch, sample, trans, Bdev, Cdev, cols, centered, row_offset=row_offset, want_bound=want_bound)
+        v = check_sampled_rows(sample, trans, Bdev, Cdev, cols, centered, row_offset=row_offset)
+        verdicts.append(dict(v, trans=int(trans), rows=len(sample["ss"] if trans else sample["ii"]), cols=list(cols)))
+        return out
+
+    monkeypatch.setattr(bench, "check_sample", both)
+    return verdicts

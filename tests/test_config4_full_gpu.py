@@ -12,13 +12,15 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-11
 
 
-def test_config4_full_5M_x_200k_x_128_one_product_one_copy():
+def test_config4_full_5M_x_200k_x_128_one_product_one_copy(monkeypatch):
     import torch
     import bench
     import miraculix_amd as mx
     L = mx.load_shared_library()
     torch.cuda.empty_cache()
     dev = torch.device("cuda", 0)
+    from _util import second_opinion_on_check_sample
+    verdicts = second_opinion_on_check_sample(monkeypatch, bench)          # each (B, C) the leg checks, also through tests/_util.py's own sampler
     leg = bench.config4_full_one_copy_leg(torch, mx, L, dev, 5_000_000, 200_000, 128, log=lambda m: print(m, file=sys.stderr, flush=True))
     print(leg, file=sys.stderr)
     assert bench.leg_checks_ok(leg), leg
@@ -30,3 +32,5 @@ def test_config4_full_5M_x_200k_x_128_one_product_one_copy():
     # the stated size ran (a device with less free memory runs the largest SNP count that fits and says so: then this fails loudly, with the budget)
     assert leg["snps_run"] == 5_000_000, leg["byte_budget_GB"]
     assert leg["N"]["TFLOPs_call"] > 60.0 and leg["T"]["TFLOPs_call"] > 60.0, leg
+    assert [v["trans"] for v in verdicts] == [0, 1], verdicts
+    assert all(v["ok"] for v in verdicts), verdicts

@@ -38,11 +38,12 @@ def _stage(torch, mx, dev, snps, indiv, n, seed):
 
 
 def _sampled_vs_oracle(S, trans, Bdev, Cdev, cols, centered, nsample=64, seed=1):
-    """nsample rows of the result against the long-double dense oracle on the extracted rows of the packed matrix (the helper bench.py's
-    config legs use too)"""
-    from bench import sampled_rows_vs_oracle
-    err = sampled_rows_vs_oracle(S["torch"], S, trans, Bdev, Cdev, cols, centered, nsample=nsample, seed=seed)
-    assert err <= RTOL, (trans, err)
+    """nsample rows of the result against a long-double sum over the extracted, numpy-unpacked rows of the packed matrix: norm-wise <= 1e-11 and
+    element-wise <= 4 K 2^-53 of each element's magnitude (tests/_util.py: check_sampled_rows, a checker of its own -- not the one bench.py's legs use)"""
+    from _util import check_sampled_rows, take_sample
+    sample = take_sample(S["torch"], S, nsample, seed)
+    v = check_sampled_rows(sample, trans, Bdev, Cdev, cols, centered, rtol=RTOL)
+    assert v["ok"], (trans, v)
 
 
 # ====================================================================================================== config 4 shard

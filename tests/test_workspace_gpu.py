@@ -14,7 +14,8 @@ pytestmark = pytest.mark.gpu
 def test_peeled_plan_fits_the_workspace_and_matches_the_oracle(n):
     import torch
     import miraculix_amd as mx
-    from bench import sampled_rows_vs_oracle, stage_object
+    from bench import stage_object
+    from _util import check_sampled_rows, take_sample
     L = mx.load_shared_library()
     L.mxa_plan_partial_doubles.restype = ctypes.c_long
     L.mxa_plan_partial_doubles.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
@@ -39,8 +40,8 @@ def test_peeled_plan_fits_the_workspace_and_matches_the_oracle(n):
             L.mxa_last_geometry(None, None, ctypes.byref(gn), None, None, None)
             assert gn.value == n4                                    # the MFMA launch saw the multiple of 4: the odd columns were peeled
             assert L.mxa_partial_capacity(S["obj"]) >= (need_peeled if not trans else 0)
-            err = sampled_rows_vs_oracle(torch, S, int(trans), B, C, list(range(n)), 1, nsample=32, seed=3)
-            assert err <= 1e-11, (trans, err)
+            v = check_sampled_rows(take_sample(torch, S, 32, 3), int(trans), B, C, list(range(n)), 1)
+            assert v["err"] <= 1e-11 and v["ok"], (trans, v)
             assert torch.equal(C, dg.dgemm_compressed_main(trans, S["obj"], B, snps, indiv))
     finally:
         dg.free_compressed(S["obj"])

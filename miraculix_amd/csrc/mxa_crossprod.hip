@@ -21,7 +21,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -494,46 +493,15 @@ int launch_plink_lut(uint8_t *d, size_t nbytes, hipStream_t s) {
   return 0;
 }
 
-// XCD-aware order of a tile list.  Consecutive workgroups are dealt round-robin to the 8 XCDs (own L2 each).  In plain i-major
-// order the 32 tiles an XCD works on at a time share one I block and need 32 different J blocks; here the tiles are grouped into
-// super-tiles of sr x 8 tiles (sr tile rows, 8 tile columns), whole super-tiles go to the XCD with the shortest list so far, and the
-// lists are interleaved (list index = 8 * slot + xcd, padded with no-op entries {0,0,0,0}) so that an XCD streams sr + 8 row blocks
-// for 8 * sr tiles.  MXA_XPROD_XCD=0 keeps the plain order (A/B measurement).
-// Returns true when the list has the interleaved per-XCD form (false: left in plain order).
-static bool xcd_order_tiles(std::vector<int4> &tiles, int nb, int sr) {
-  constexpr bool on = true;
-  if (!on || tiles.size() < 8 * 64 || sr < 1) return false;
-  int i_min = tiles[0].x;
-  for (const int4 &t : tiles) i_min = std::min(i_min, t.x);
-  const int ncb = (nb + 7) / 8;
-  std::vector<std::vector<int4>> super((size_t)((nb - i_min + sr - 1) / sr) * ncb);
-  for (const int4 &t : tiles) super[(size_t)((t.x - i_min) / sr) * ncb + t.y / 8].push_back(t);
-  std::vector<std::vector<int4>> per_xcd(8);
-  for (auto &st : super) {
-    if (st.empty()) continue;
-    int best = 0;
-    for (int x = 1; x < 8; x++) if (per_xcd[x].size() < per_xcd[best].size()) best = x;
-    per_xcd[best].insert(per_xcd[best].end(), st.begin(), st.end());
-  }
-  size_t longest = 0;
-  for (auto &v : per_xcd) longest = std::max(longest, v.size());
-  std::vector<int4> inter;
-  inter.reserve(longest * 8);
-  for (size_t slot = 0; slot < longest; slot++)
-    for (int x = 0; x < 8; x++) inter.push_back(slot < per_xcd[x].size() ? per_xcd[x][slot] : make_int4(0, 0, 0, 0));
-  tiles.swap(inter);
-  return true;
-}
-
 // Order for the gang-synchronised kernel: the list is cut into GANGS of 32 tiles (the workgroups of an XCD) that are compact in the tile grid -- bands of 4
 // tile rows, walked column by column, so a gang is 4 x 8 tiles = 12 row blocks (a little more where it meets the diagonal or the end of a band) -- and the
 // gangs are dealt whole to the 8 XCD lists (neighbouring gangs of a band run on different XCDs at the same time and share the band's 4 row blocks through
-// the Infinity Cache).  Gang boundaries stay aligned with multiples of 32 slots in every list; with the 8 x 8 super-tiles of xcd_order_tiles one
-// partial super-tile (36 tiles on the diagonal) shifts every later gang of that list across two super-tile halves.
+// the Infinity Cache).  Gang boundaries stay aligned with multiples of 32 slots in every list; with the 8 x 8 super-tiles of round 2's order one
+// partial super-tile (36 tiles on the diagonal) shifted every later gang of that list across two super-tile halves.
+// Returns true when the list has the interleaved per-XCD form (list index = 8 * slot + xcd, padded with no-op entries {0,0,0,0}); false: too short, plain order.
 static bool gang_order_tiles(std::vector<int4> &tiles) {
-  constexpr bool on = true;
   constexpr size_t kGang = 32;
-  if (!on || tiles.size() < 8 * 64) return false;
+  if (tiles.size() < 8 * 64) return false;
   std::sort(tiles.begin(), tiles.end(), [](const int4 &a, const int4 &b) {
     if (a.x / 4 != b.x / 4) return a.x / 4 < b.x / 4;
     if (a.y != b.y) return a.y < b.y;
@@ -578,15 +546,45 @@ struct XBuf {
   int alloc(size_t bytes) { MXA_HIP(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
   void release() { if (p) { (void)hipFree(p); p = nullptr; } }
 };
+// Geometry of one call: X has `rows` rows, staged as nb tiles of 256 rows; a staged row is nslabs slabs of 128 genotypes (32 bytes, the pitch), one
+// K stage of the kernels each.
+struct XGeom {
+  long rows;
+  int nb, stages;
+  long nslabs;
+  XGeom(long k, long r) : rows(r), nb((int)((r + kXT - 1) / kXT)), stages((int)((k + kXStageK - 1) / kXStageK)), nslabs(stages) {}
+  long rows_pad() const { return (long)nb * kXT; }
+  size_t pitch() const { return (size_t)nslabs * kXStageBytes; }
+};
 }  // namespace
 
-// one launch over a tile list with either engine (f4: FP4 MFMA, else int8 MFMA); diag_out: in-kernel clocks of the DIAG instantiation
+// measured time of one 256 x 256 tile per K stage on one CU (FP4 / int8 MFMA): the estimates of the gang decision and of the ring
+static double tile_stage_ms(bool f4) { return f4 ? 0.66e-3 : 1.0e-3; }
+
+// the profile counts one launch per call, with the time between its two events
+static hipError_t profile_launch(const XEvent &e0, const XEvent &e1) {
+  float ms = 0.f;
+  const hipError_t err = hipEventElapsedTime(&ms, e0.e, e1.e);
+  if (err == hipSuccess) { std::lock_guard<std::mutex> lk(g_xprof_mutex); profile().launches += 1; profile().total_ms += ms; }
+  return err;
+}
+
+// one launch of the kernel instantiation K with kF4Lds bytes of dynamic LDS: its attribute is set first (per device, once per instantiation)
+template <auto K, typename... A>
+static int launch_lds(dim3 grid, hipStream_t s, A... a) {
+  static unsigned long long mask = 0;
+  if (ensure_dyn_lds(reinterpret_cast<const void *>(K), kF4Lds, &mask)) return 1;
+  hipLaunchKernelGGL(K, grid, dim3(256), kF4Lds, s, a...);
+  MXA_HIP(hipGetLastError());
+  return 0;
+}
+// the one-workgroup-per-tile instantiation of an engine
+template <bool I8, bool DIAG, int POST> constexpr auto k_tiles = I8 ? &k_crossprod_i8<DIAG, POST> : &k_crossprod_f4<DIAG, 0, POST>;
+
+// one launch over a tile list with either engine (f4: FP4 MFMA, else int8 MFMA); d_diag: in-kernel clocks of the DIAG instantiation
 // gang_mid_capacity: ints available behind d_gang[32] for the per-gang counters of the second meeting point (0: none)
-static int launch_tiles(bool f4, size_t ntiles, hipStream_t s, const uint8_t *d_X, long nslabs, int stages, const int4 *d_tiles, long rows, double *d_ans, long ld,
-                        long c0, unsigned long long *d_diag, int post_kind = 0, const XPost &post = XPost(), int *d_gang = nullptr, size_t gang_mid_capacity = 0) {
-  static unsigned long long m2 = 0, m3 = 0;   // per-device function attributes
-  if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_f4<false>), kF4Lds, &m2) || ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_f4<true>), kF4Lds, &m3)) return 1;
-  const dim3 grid((unsigned)ntiles), block(256);
+static int launch_tiles(const XGeom &g, bool f4, size_t ntiles, hipStream_t s, const uint8_t *d_X, const int4 *d_tiles, double *d_ans, long ld, long c0,
+                        unsigned long long *d_diag, int post_kind, const XPost &post, int *d_gang, size_t gang_mid_capacity) {
   // gang-synchronised persistent form: needs the interleaved per-XCD lists (d_gang != nullptr) and is not instrumented (MXA_DIAG keeps the classic kernels)
   // It pays when the launch is long enough for the power limit to matter and a tile long enough to carry the meeting: config 3 -5 ... -8 %, 30 000 rows x
   // 500k -3.4 %, but K = 50 000 (0.26 ms per tile) +2 ... +8 % at 8 192 - 40 000 rows.  MXA_XPROD_GANG: 0 never, 1 (default) by this estimate, 2 whenever possible.
@@ -598,57 +596,95 @@ static int launch_tiles(bool f4, size_t ntiles, hipStream_t s, const uint8_t *d_
     MXA_HIP(hipGetDevice(&dev));
     MXA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   }
-  const double est_ms = cus > 0 ? (double)stages * (f4 ? 0.66e-3 : 1.0e-3) * ((double)ntiles / cus) : 0.0;
-  if (cus > 0 && (gang_on >= 2 || (stages >= 1024 && est_ms >= 20.0))) {
-    const int slots = (int)(ntiles / 8);
-    const dim3 pgrid((unsigned)std::max(8, std::min<int>(cus, (int)ntiles)));
+  const double est_ms = cus > 0 ? (double)g.stages * tile_stage_ms(f4) * ((double)ntiles / cus) : 0.0;
+  const bool gang = cus > 0 && (gang_on >= 2 || (g.stages >= 1024 && est_ms >= 20.0));
+  const int slots = (int)(ntiles / 8);
+  int *d_mid = nullptr, mid_parts = 1, xcc_mask = 7;
+  unsigned join_ticks = 0;
+  if (gang) {
+    static const int mask = [] { const char *e = getenv("MXA_XPROD_GANG_XCC_MASK"); return e ? atoi(e) & 7 : 7; }();
+    static const unsigned ticks = [] { const char *e = getenv("MXA_XPROD_GANG_US"); return e ? (unsigned)std::max(0, atoi(e)) * 100u : (unsigned)kGangJoinTicks; }();
+    xcc_mask = mask;
+    join_ticks = ticks;
     MXA_HIP(hipMemsetAsync(d_gang, 0, sizeof(int) * kGangCtrs, s));
     // second meeting point: one counter per gang and XCD list, behind the 17 control counters when the caller's buffer has room for them
     // MXA_XPROD_GANG_MID = number of parts a tile's K range is cut into (meetings = parts - 1): 0 / 1 none, 2 (default) one meeting half way through.
     // The gang form is only taken for long tiles (stages >= 1024, i.e. K >= 131k: tiles of >= 0.7 ms), and the meeting's wait is bounded by 4 % of the tile.
     const char *e_mid = getenv("MXA_XPROD_GANG_MID");
-    const int mid_parts = std::max(1, std::min(8, e_mid ? atoi(e_mid) : 2));
-    int *d_mid = nullptr;
+    mid_parts = std::max(1, std::min(8, e_mid ? atoi(e_mid) : 2));
     if (mid_parts > 1 && gang_mid_capacity >= (size_t)8 * slots * (mid_parts - 1)) {
       d_mid = d_gang + 32;
       MXA_HIP(hipMemsetAsync(d_mid, 0, sizeof(int) * (size_t)8 * slots * (mid_parts - 1), s));
     }
-    static unsigned long long g0 = 0, g1 = 0, g2 = 0, g3 = 0, g4 = 0, g5 = 0;
-    static const int xcc_mask = [] { const char *e = getenv("MXA_XPROD_GANG_XCC_MASK"); return e ? atoi(e) & 7 : 7; }();
-    static const unsigned join_ticks = [] { const char *e = getenv("MXA_XPROD_GANG_US"); return e ? (unsigned)std::max(0, atoi(e)) * 100u : (unsigned)kGangJoinTicks; }();
-#define MXA_GANG_LAUNCH(I8, POST, MASK)                                                                                                          \
-    {                                                                                                                                            \
-      if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_gang<I8, POST>), kF4Lds, &MASK)) return 1;                                   \
-      hipLaunchKernelGGL((k_crossprod_gang<I8, POST>), pgrid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, slots, rows, d_ans, ld, c0, post, d_gang, join_ticks, xcc_mask, d_mid, mid_parts); \
+  }
+  const dim3 grid(gang ? (unsigned)std::max(8, std::min<int>(cus, (int)ntiles)) : (unsigned)ntiles);
+  // the instantiation for (gang, engine, post_kind, diag); the GRM / LD maps never run in the diagnostic instantiations
+  auto go = [&](auto i8, auto pk) {
+    constexpr bool I8 = decltype(i8)::value;
+    constexpr int POST = decltype(pk)::value;
+    if (gang)
+      return launch_lds<&k_crossprod_gang<I8, POST>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, slots, g.rows, d_ans, ld, c0, post, d_gang, join_ticks, xcc_mask, d_mid, mid_parts);
+    if (POST == 0 && d_diag) return launch_lds<k_tiles<I8, true, 0>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, g.rows, d_ans, ld, c0, d_diag, post);
+    return launch_lds<k_tiles<I8, false, POST>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, g.rows, d_ans, ld, c0, nullptr, post);
+  };
+  using F4 = std::false_type;
+  using I8 = std::true_type;
+  if (post_kind == 1) return f4 ? go(F4(), std::integral_constant<int, 1>()) : go(I8(), std::integral_constant<int, 1>());
+  if (post_kind == 2) return f4 ? go(F4(), std::integral_constant<int, 2>()) : go(I8(), std::integral_constant<int, 2>());
+  return f4 ? go(F4(), std::integral_constant<int, 0>()) : go(I8(), std::integral_constant<int, 0>());
+}
+
+// ---- tile lists.  Tile (i, j), i <= j, with flags bit 1: it writes its direct image M[J rows, I cols] (columns of tile i), bit 2: its mirror image
+// M[I rows, J cols] (columns of tile j; never on the diagonal).
+// The tiles that touch the column panel of tile columns [t0, t1); upper_only: the direct image only for j < t1 (rows on and above the panel's diagonal block).
+static std::vector<int4> panel_tiles(int nb, int t0, int t1, bool upper_only) {
+  std::vector<int4> tiles;
+  for (int i = 0; i < nb; i++)
+    for (int j = i; j < nb; j++) {
+      int flags = 0;
+      if (i >= t0 && i < t1 && (!upper_only || j < t1)) flags |= 1;
+      if (j >= t0 && j < t1 && i != j) flags |= 2;
+      if (flags) tiles.push_back(make_int4(i, j, flags, 0));
     }
-    if (f4) { if (post_kind == 1) MXA_GANG_LAUNCH(false, 1, g1) else if (post_kind == 2) MXA_GANG_LAUNCH(false, 2, g2) else MXA_GANG_LAUNCH(false, 0, g0) }
-    else { if (post_kind == 1) MXA_GANG_LAUNCH(true, 1, g4) else if (post_kind == 2) MXA_GANG_LAUNCH(true, 2, g5) else MXA_GANG_LAUNCH(true, 0, g3) }
-#undef MXA_GANG_LAUNCH
-    MXA_HIP(hipGetLastError());
-    return 0;
+  return tiles;
+}
+// The tile rows [i0, i1) of the upper triangle, both images of every tile.
+static std::vector<int4> row_tiles(int nb, int i0, int i1) {
+  std::vector<int4> tiles;
+  for (int i = i0; i < i1; i++)
+    for (int j = i; j < nb; j++) tiles.push_back(make_int4(i, j, i == j ? 1 : 3, 0));
+  return tiles;
+}
+
+namespace {
+// The tile lists of a call's chunks, uploaded once: chunk c is d_tiles[first[c], first[c + 1]), in the gang order where gang_order_tiles took it (xcd[c]).
+// d_gang: the gangs' 32 control counters, then mid_cap ints for the counters of their meetings inside a tile, sized for the longest list.
+struct XTiles {
+  std::vector<int4> tiles;
+  std::vector<size_t> first;
+  std::vector<char> xcd;
+  size_t mid_cap = 0;
+  XBuf d_tiles, d_gang;
+  int launch(int c, const XGeom &g, bool f4, hipStream_t s, const uint8_t *d_X, double *d_ans, long ld, long c0, unsigned long long *d_diag, int post_kind,
+             const XPost &post) const {
+    return launch_tiles(g, f4, first[(size_t)c + 1] - first[(size_t)c], s, d_X, (const int4 *)d_tiles.p + first[(size_t)c], d_ans, ld, c0, d_diag, post_kind,
+                        post, xcd[(size_t)c] ? (int *)d_gang.p : nullptr, mid_cap);
   }
-  if (post_kind == 1 || post_kind == 2) {   // GRM / LD map fused into the epilogue (never with the diagnostic instantiations)
-    static unsigned long long p1 = 0, p2 = 0, p3 = 0, p4 = 0;
-    if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_f4<false, 0, 1>), kF4Lds, &p1) || ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_f4<false, 0, 2>), kF4Lds, &p2) ||
-        ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_i8<false, 1>), kF4Lds, &p3) || ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_i8<false, 2>), kF4Lds, &p4)) return 1;
-    if (f4 && post_kind == 1) hipLaunchKernelGGL((k_crossprod_f4<false, 0, 1>), grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, nullptr, post);
-    else if (f4) hipLaunchKernelGGL((k_crossprod_f4<false, 0, 2>), grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, nullptr, post);
-    else if (post_kind == 1) hipLaunchKernelGGL((k_crossprod_i8<false, 1>), grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, nullptr, post);
-    else hipLaunchKernelGGL((k_crossprod_i8<false, 2>), grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, nullptr, post);
-    MXA_HIP(hipGetLastError());
-    return 0;
+};
+}  // namespace
+
+static int upload_tiles(std::vector<std::vector<int4>> chunks, hipStream_t s, XTiles &t) {
+  t.first.assign(chunks.size() + 1, 0);
+  t.xcd.assign(chunks.size(), 0);
+  for (size_t c = 0; c < chunks.size(); c++) {
+    t.first[c] = t.tiles.size();
+    t.xcd[c] = gang_order_tiles(chunks[c]);
+    t.mid_cap = std::max(t.mid_cap, 7 * (chunks[c].size() + 64));      // >= 8 lists x slots per list x up to 7 meetings per tile
+    t.tiles.insert(t.tiles.end(), chunks[c].begin(), chunks[c].end());
   }
-  if (f4) {
-    // (the diagnostic EXP instantiations of round 2 -- no unpack, no DMA, barrier only ..., all with wrong results -- were removed in round 5; what they measured: profiles/r02_mfma_f4_probe.txt)
-    if (d_diag) hipLaunchKernelGGL(k_crossprod_f4<true>, grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, d_diag, post);
-    else hipLaunchKernelGGL(k_crossprod_f4<false>, grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, d_diag, post);
-  } else {
-    static unsigned long long i0 = 0, i1 = 0;
-    if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_i8<false>), kF4Lds, &i0) || ensure_dyn_lds(reinterpret_cast<const void *>(&k_crossprod_i8<true>), kF4Lds, &i1)) return 1;
-    if (d_diag) hipLaunchKernelGGL(k_crossprod_i8<true>, grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, d_diag, post);
-    else hipLaunchKernelGGL(k_crossprod_i8<false>, grid, block, kF4Lds, s, d_X, nslabs, stages, d_tiles, rows, d_ans, ld, c0, d_diag, post);
-  }
-  MXA_HIP(hipGetLastError());
+  t.first.back() = t.tiles.size();
+  if (t.d_tiles.alloc(t.tiles.size() * sizeof(int4)) || t.d_gang.alloc(sizeof(int) * (32 + t.mid_cap))) return 1;
+  MXA_HIP(hipMemcpyAsync(t.d_tiles.p, t.tiles.data(), t.tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
   return 0;
 }
 
@@ -656,91 +692,61 @@ static int launch_tiles(bool f4, size_t ntiles, hipStream_t s, const uint8_t *d_
 // Columns [c_begin, c_end) of M = X X^T into d_ans (leading dimension ld; c_begin a multiple of the 256-row tile, c_end a multiple
 // or the matrix end).  upper_only: only rows [0, c_end) are written -- everything above the panel's diagonal block and the block
 // itself; rows >= c_end are left untouched.  The whole matrix is c_begin = 0, c_end = rows, ld = rows.
-int crossprod_device(const uint8_t *d_X, long k, long rows, size_t pitch, double *d_ans, hipStream_t s, long c_begin, long c_end, bool upper_only,
-                     long ld, bool f4, int post_kind, const XPost *post) {
-  const int nb = (int)((rows + kXT - 1) / kXT);
-  const int stages = (int)((k + kXStageK - 1) / kXStageK);
-  const long nslabs = (long)(pitch / kXStageBytes);
-  if (stages > nslabs) { set_error(4, "internal: crossproduct pitch too small"); return 1; }
-  if (c_begin % kXT != 0 || c_begin < 0 || c_end > rows || c_begin >= c_end || ld < (upper_only ? c_end : rows)) { set_error(4, "crossproduct: bad column panel"); return 1; }
-  const int t0 = (int)(c_begin / kXT), t1 = (int)((c_end + kXT - 1) / kXT);
-  const bool whole = c_begin == 0 && c_end == rows;
-  if (!whole && c_end % kXT != 0 && c_end != rows) { set_error(4, "crossproduct: panel end must be a multiple of %d or the matrix end", kXT); return 1; }
-  // upper-triangular tiles (i <= j) that touch the panel: the direct image M[J rows, I cols] lands in the panel when i is a panel
-  // column tile, the mirror image M[I rows, J cols] when j is
-  std::vector<int4> tiles;
-  for (int i = 0; i < nb; i++)
-    for (int j = i; j < nb; j++) {
-      int flags = 0;
-      if (i >= t0 && i < t1 && (!upper_only || j < t1)) flags |= 1;      // rows of tile j >= i: on/below the diagonal
-      if (j >= t0 && j < t1 && i != j) flags |= 2;                        // rows of tile i < j: above the diagonal
-      if (flags) tiles.push_back(make_int4(i, j, flags, 0));
-    }
-  if (tiles.empty()) return 0;
-  constexpr int gang_order = 1;   // (0: the 8 x 8 super-tiles of round 2, the A/B baseline)
-  const bool xcd_lists = gang_order ? gang_order_tiles(tiles) : xcd_order_tiles(tiles, nb, 8);
-  XBuf d_tiles, d_diag, d_gang;
-  const size_t mid_cap = 7 * (tiles.size() + 64);      // >= 8 lists x slots per list x up to 7 meetings per tile
-  if (d_gang.alloc(sizeof(int) * (32 + mid_cap))) return 1;
-  if (d_tiles.alloc(tiles.size() * sizeof(int4))) return 1;
-  MXA_HIP(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+static int crossprod_device(const XGeom &g, const uint8_t *d_X, double *d_ans, hipStream_t s, long c_begin, long c_end, bool upper_only, long ld, bool f4,
+                            int post_kind, const XPost &post) {
+  XTiles t;
+  if (upload_tiles({panel_tiles(g.nb, (int)(c_begin / kXT), (int)((c_end + kXT - 1) / kXT), upper_only)}, s, t)) return 1;
+  const size_t ntiles = t.tiles.size();
   XEvent e0, e1;
   if (e0.create() || e1.create()) return 1;
+  XBuf d_diag;
   const bool diag_on = getenv("MXA_DIAG") != nullptr;
-  if (diag_on && d_diag.alloc(16 * tiles.size())) return 1;
+  if (diag_on && d_diag.alloc(16 * ntiles)) return 1;
   MXA_HIP(hipEventRecord(e0.e, s));
-  if (launch_tiles(f4, tiles.size(), s, d_X, nslabs, stages, (const int4 *)d_tiles.p, rows, d_ans, ld, c_begin, (unsigned long long *)d_diag.p, post ? post_kind : 0, post ? *post : XPost(),
-                   xcd_lists ? (int *)d_gang.p : nullptr, mid_cap)) return 1;
+  if (t.launch(0, g, f4, s, d_X, d_ans, ld, c_begin, (unsigned long long *)d_diag.p, post_kind, post)) return 1;
   MXA_HIP(hipEventRecord(e1.e, s));
   MXA_HIP(hipStreamSynchronize(s));   // tiles vector / d_tiles lifetime
   if (diag_on) {   // diagnostic instantiation: in-kernel clock and cycles per stage
-    std::vector<unsigned long long> hd(2 * tiles.size());
-    MXA_HIP(hipMemcpy(hd.data(), d_diag.p, 16 * tiles.size(), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> hd(2 * ntiles);
+    MXA_HIP(hipMemcpy(hd.data(), d_diag.p, 16 * ntiles, hipMemcpyDeviceToHost));
     std::vector<double> ghz, cyc;
-    for (size_t i = 0; i < tiles.size(); i++) if (tiles[i].z && hd[2 * i + 1]) { ghz.push_back((double)hd[2 * i] / (double)hd[2 * i + 1] * 0.1); cyc.push_back((double)hd[2 * i] / stages); }
+    for (size_t i = 0; i < ntiles; i++) if (t.tiles[i].z && hd[2 * i + 1]) { ghz.push_back((double)hd[2 * i] / (double)hd[2 * i + 1] * 0.1); cyc.push_back((double)hd[2 * i] / g.stages); }
     std::sort(ghz.begin(), ghz.end()); std::sort(cyc.begin(), cyc.end());
     if (!ghz.empty()) printf("MXA_DIAG %s: %zu tiles, in-kernel clock median %.3f GHz (min %.3f max %.3f); shader cycles per stage median %.0f (ideal %d)\n",
-                             f4 ? "k_crossprod_f4" : "k_crossprod_i8", tiles.size(), ghz[ghz.size() / 2], ghz.front(), ghz.back(), cyc[cyc.size() / 2], f4 ? 1024 : 2048);
+                             f4 ? "k_crossprod_f4" : "k_crossprod_i8", ntiles, ghz[ghz.size() / 2], ghz.front(), ghz.back(), cyc[cyc.size() / 2], f4 ? 1024 : 2048);
   }
-  float ms = 0.f;
-  MXA_HIP(hipEventElapsedTime(&ms, e0.e, e1.e));
-  { std::lock_guard<std::mutex> lk(g_xprof_mutex); profile().launches += 1; profile().total_ms += ms; }
+  MXA_HIP(profile_launch(e0, e1));
   return 0;
 }
 
-// Whole matrix for a HOST result (the plain reference ABI): the upper-triangular tiles are launched in chunks of tile rows i
-// (all j >= i).  Tile (i, j) stores M[J rows, I cols] and M[I rows, J cols], so once every chunk up to tile row i1 has run, columns
-// [0, 256*i1) of M are final: a helper thread copies each finished column slab to the host on its own non-blocking stream while
-// the next chunk computes (at config 3 the 80 GB device-to-host copy is as long as the compute).
-static int crossprod_to_host(const uint8_t *d_X, long k, long rows, size_t pitch, double *d_ans, double *h_ans, hipStream_t s, bool f4, int post_kind = 0,
-                             const XPost *post = nullptr, const HostPrefault *pf = nullptr) {
-  const int nb = (int)((rows + kXT - 1) / kXT);
-  const int stages = (int)((k + kXStageK - 1) / kXStageK);
-  const long nslabs = (long)(pitch / kXStageBytes);
-  if (stages > nslabs) { set_error(4, "internal: crossproduct pitch too small"); return 1; }
+// Whole matrix for a HOST result, in chunks of ~1 GiB column slabs: chunk c holds columns [256 w c, 256 w (c + 1)) of M, and four helper threads copy each
+// finished chunk to the host, each on its own non-blocking stream, while the next chunk computes (at config 3 the 80 GB device-to-host copy is as long
+// as the compute).  Two forms:
+//  - into d_ans, the n x n device buffer: chunk c is the tile rows [w c, w (c + 1)) (all j >= i).  Tile (i, j) stores M[J rows, I cols] and M[I rows, J cols],
+//    so once every chunk up to tile row i1 has run, columns [0, 256*i1) of M are final.
+//  - ring (round 4): no device copy of the whole matrix.  Its hipMalloc (80 GB at config 3) takes anything from nothing to 4.6 s on this pool (the phase
+//    clock of crossprod_any, profiles/r04_crossprod_host_*.txt: that -- not a copy scheme -- was round 3's unexplained "one call in 24 takes 4-5 s"), and
+//    the result could never exceed HBM.  Chunk c is the column panel of mxa_snp_multiply_panel (every tile (i, j >= i) that touches it), computed into
+//    slot c % 3 of a RING of device buffers.  Every off-diagonal tile is computed twice (once per image): twice the arithmetic of the triangular
+//    launch -- taken only where the call is bound by the copy anyway (crossprod_any compares the two estimates).
+static int crossprod_slabs(const XGeom &g, const uint8_t *d_X, double *d_ans, double *h_ans, hipStream_t s, bool f4, int post_kind, const XPost &post,
+                           bool ring, HostPrefault &pf) {
+  const long rows = g.rows;
   const char *slab_env = getenv("MXA_XPROD_SLAB_MB");                                        // tests use small slabs
   const long slab_bytes = (slab_env && atol(slab_env) > 0 ? atol(slab_env) : 1024L) << 20;
-  const int rows_per_chunk = (int)std::max<long>(1, slab_bytes / (rows * 8 * kXT));         // ~1 GiB column slabs
-  const int nchunks = (nb + rows_per_chunk - 1) / rows_per_chunk;
-  constexpr int gang_order = 1;
-  // one tile list per chunk of tile rows, each in XCD-aware order (super-tiles = the chunk's rows x 8 tile columns)
-  std::vector<int4> tiles;
-  std::vector<size_t> first((size_t)nchunks + 1, 0);
-  std::vector<char> chunk_xcd((size_t)nchunks, 0);      // the chunk's list has the interleaved per-XCD form (gang-synchronised kernel)
-  for (int c = 0; c < nchunks; c++) {
-    first[(size_t)c] = tiles.size();
-    std::vector<int4> part;
-    for (int i = c * rows_per_chunk; i < std::min(nb, (c + 1) * rows_per_chunk); i++)
-      for (int j = i; j < nb; j++) part.push_back(make_int4(i, j, i == j ? 1 : 3, 0));
-    chunk_xcd[(size_t)c] = gang_order ? gang_order_tiles(part) : xcd_order_tiles(part, nb, std::min(rows_per_chunk, 8));
-    tiles.insert(tiles.end(), part.begin(), part.end());
-  }
-  first[(size_t)nchunks] = tiles.size();
-  XBuf d_tiles, d_gang;
-  size_t mid_cap = 0;   // counters of the gangs' meetings inside a tile: sized for the longest slab list
-  for (int c = 0; c < nchunks; c++) mid_cap = std::max(mid_cap, 7 * (first[(size_t)c + 1] - first[(size_t)c] + 64));
-  if (d_tiles.alloc(tiles.size() * sizeof(int4)) || d_gang.alloc(sizeof(int) * (32 + mid_cap))) return 1;
-  MXA_HIP(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  const int w = (int)std::max<long>(1, slab_bytes / (rows * 8 * kXT));                        // tile rows or tile columns per chunk
+  const int nchunks = (g.nb + w - 1) / w;
+  constexpr int kRing = 3, kCopiers = 4;
+  XBuf slot[kRing];
+  if (ring)
+    for (auto &r : slot) if (r.alloc((size_t)rows * (size_t)std::min<long>(rows, (long)w * kXT) * sizeof(double))) return 1;
+  std::vector<std::vector<int4>> chunks;
+  for (int c = 0; c < nchunks; c++) chunks.push_back(ring ? panel_tiles(g.nb, c * w, std::min(g.nb, (c + 1) * w), false) : row_tiles(g.nb, c * w, std::min(g.nb, (c + 1) * w)));
+  XTiles t;
+  if (upload_tiles(std::move(chunks), s, t)) return 1;
+  // chunk c: its first column, and the output its launch writes -- base pointer and the column held there first
+  auto col0 = [&](int c) { return std::min<long>(rows, (long)c * w * kXT); };
+  auto out = [&](int c) { return ring ? std::make_pair((double *)slot[c % kRing].p, col0(c)) : std::make_pair(d_ans, 0L); };
   std::vector<XEvent> ev((size_t)nchunks);
   int dev = 0;
   MXA_HIP(hipGetDevice(&dev));
@@ -749,9 +755,10 @@ static int crossprod_to_host(const uint8_t *d_X, long k, long rows, size_t pitch
   if (e0.create() || e1.create()) return 1;
   std::atomic<int> launched{0}, copy_err{0};
   std::atomic<bool> abort_copy{false};
+  std::vector<std::atomic<int>> copied((size_t)nchunks);   // copiers done with chunk c: its ring slot is free once all are
+  for (auto &c : copied) c.store(0);
   // a copy into pageable memory is staged by the runtime and bound by one host thread's memcpy (~17 GB/s measured): several
   // copier threads, each with its own stream and its own share of every slab, run those memcpys side by side
-  constexpr int kCopiers = 4;
   XStream cs[kCopiers];
   for (auto &c : cs) if (c.create(hipStreamNonBlocking)) return 1;
   // where the host time of a call goes, per copier: waiting for a slab to be computed, and inside the copies; the slowest single copy with its
@@ -760,166 +767,64 @@ static int crossprod_to_host(const uint8_t *d_X, long k, long rows, size_t pitch
   CopierLog clog[kCopiers];
   const auto t_call = std::chrono::steady_clock::now();
   auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  auto copy_loop = [&](int t) {
-    if (hipSetDevice(dev) != hipSuccess) { copy_err = 1; return; }
-    for (int c = 0; c < nchunks; c++) {
-      const auto tw = std::chrono::steady_clock::now();
-      while (launched.load() <= c) { if (abort_copy.load()) return; std::this_thread::yield(); }
-      if (hipEventSynchronize(ev[c].e) != hipSuccess) { copy_err = 1; return; }
-      clog[t].wait_s += since(tw);
-      const long col0 = (long)c * rows_per_chunk * kXT, col1 = std::min<long>(rows, (long)(c + 1) * rows_per_chunk * kXT);
-      const long w = col1 - col0, a = col0 + w * t / kCopiers, b = col0 + w * (t + 1) / kCopiers;
-      if (b <= a) continue;
-      const size_t off = (size_t)a * rows, cnt = (size_t)(b - a) * rows;
-      if (pf) { const auto tp = std::chrono::steady_clock::now(); pf->wait_for(h_ans + off + cnt); clog[t].wait_s += since(tp); }
-      const auto tc = std::chrono::steady_clock::now();
-      if (hipMemcpyAsync(h_ans + off, d_ans + off, cnt * sizeof(double), hipMemcpyDeviceToHost, cs[t].s) != hipSuccess || hipStreamSynchronize(cs[t].s) != hipSuccess) { copy_err = 1; return; }
-      const double dt = since(tc);
-      clog[t].copy_s += dt; clog[t].bytes += cnt * sizeof(double);
-      if (dt > clog[t].worst_s) { clog[t].worst_s = dt; clog[t].worst_slab = c; }
-    }
-  };
-  std::vector<std::thread> copiers;
-  for (int t = 0; t < kCopiers; t++) copiers.emplace_back(copy_loop, t);
-  int rc = 0;
-  if (hipEventRecord(e0.e, s) != hipSuccess) rc = 1;
-  for (int c = 0; c < nchunks && !rc; c++) {
-    const size_t cnt = first[(size_t)c + 1] - first[(size_t)c];
-    if (launch_tiles(f4, cnt, s, d_X, nslabs, stages, (const int4 *)d_tiles.p + first[(size_t)c], rows, d_ans, rows, 0L, nullptr, post ? post_kind : 0, post ? *post : XPost(), chunk_xcd[(size_t)c] ? (int *)d_gang.p : nullptr, mid_cap) || hipEventRecord(ev[c].e, s) != hipSuccess) { rc = 1; break; }
-    launched.store(c + 1);
-  }
-  if (rc) abort_copy = true;
-  if (!rc && hipEventRecord(e1.e, s) != hipSuccess) rc = 1;
-  const double t_launched = since(t_call);
-  for (auto &t : copiers) t.join();
-  if (hipStreamSynchronize(s) != hipSuccess) rc = 1;
-  for (int t = 0; t < kCopiers; t++)
-    debug_info("crossproduct host result: copier %d waited %.3f s for slabs, copied %.2f GB in %.3f s (%.1f GB/s), slowest single copy %.3f s (slab %d of %d)", t, clog[t].wait_s,
-               clog[t].bytes * 1e-9, clog[t].copy_s, clog[t].copy_s > 0 ? clog[t].bytes * 1e-9 / clog[t].copy_s : 0.0, clog[t].worst_s, clog[t].worst_slab, nchunks);
-  debug_info("crossproduct host result: %d slab launches enqueued after %.3f s, all copies done after %.3f s", nchunks, t_launched, since(t_call));
-  if (!rc && !copy_err.load()) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0.e, e1.e) == hipSuccess) { profile().launches += 1; profile().total_ms += ms; }
-  }
-  if (rc || copy_err.load()) { set_error(13, "snp_multiply_gpu: pipelined device-to-host copy of the result failed"); return 1; }
-  return 0;
-}
-
-// Host result WITHOUT a device copy of the whole matrix (round 4).  crossprod_to_host above needs the full n x n device buffer (80 GB at config 3):
-// hipMalloc of such a buffer takes anything from nothing to 4.6 s on this pool (the phase clock of crossprod_any, profiles/r04_crossprod_host_*.txt:
-// that -- not a copy scheme -- was round 3's unexplained "one call in 24 takes 4-5 s"), and the result could never exceed HBM.  Here the matrix is
-// produced column slab by column slab into a RING of three ~1 GiB device buffers: slab [c0, c1) is the column panel of mxa_snp_multiply_panel (every
-// tile (i, j >= i) that touches it: its direct image when i lies in the panel, its mirror image when j does), computed by the same kernels, and leaves
-// through the four copier threads while the next slab is computed.  Every off-diagonal tile is computed twice (once per image): twice the arithmetic of
-// the triangular launch -- taken only where the call is bound by the copy anyway (the caller compares the two estimates).
-static int crossprod_to_host_ring(const uint8_t *d_X, long k, long rows, size_t pitch, double *h_ans, hipStream_t s, bool f4, int post_kind, const XPost *post,
-                                  const std::function<void()> &all_allocated, const HostPrefault *pf) {
-  const int nb = (int)((rows + kXT - 1) / kXT);
-  const int stages = (int)((k + kXStageK - 1) / kXStageK);
-  const long nslabs = (long)(pitch / kXStageBytes);
-  if (stages > nslabs) { set_error(4, "internal: crossproduct pitch too small"); return 1; }
-  const char *slab_env = getenv("MXA_XPROD_SLAB_MB");                                        // tests use small slabs
-  const long slab_bytes = (slab_env && atol(slab_env) > 0 ? atol(slab_env) : 1024L) << 20;
-  const int tcols = (int)std::max<long>(1, slab_bytes / (rows * 8 * kXT));                   // tile columns per slab
-  const int nchunks = (nb + tcols - 1) / tcols;
-  constexpr int kRing = 3, kCopiers = 4;
-  const size_t slot_elems = (size_t)rows * (size_t)std::min<long>(rows, (long)tcols * kXT);
-  XBuf ring[kRing], d_tiles, d_gang;
-  for (auto &r : ring) if (r.alloc(slot_elems * sizeof(double))) return 1;
-  constexpr int gang_order = 1;
-  // tile lists of all slabs, one after the other (uploaded once)
-  std::vector<int4> tiles;
-  std::vector<size_t> first((size_t)nchunks + 1, 0);
-  std::vector<char> chunk_xcd((size_t)nchunks, 0);
-  for (int c = 0; c < nchunks; c++) {
-    first[(size_t)c] = tiles.size();
-    const int t0 = c * tcols, t1 = std::min(nb, t0 + tcols);
-    std::vector<int4> part;
-    for (int i = 0; i < nb; i++)
-      for (int j = i; j < nb; j++) {
-        int flags = 0;
-        if (i >= t0 && i < t1) flags |= 1;                   // direct image M[J rows, I cols]: columns of tile i
-        if (j >= t0 && j < t1 && i != j) flags |= 2;         // mirror image M[I rows, J cols]: columns of tile j
-        if (flags) part.push_back(make_int4(i, j, flags, 0));
-      }
-    chunk_xcd[(size_t)c] = gang_order ? gang_order_tiles(part) : xcd_order_tiles(part, nb, 8);
-    tiles.insert(tiles.end(), part.begin(), part.end());
-  }
-  first[(size_t)nchunks] = tiles.size();
-  size_t mid_cap = 0;   // counters of the gangs' meetings inside a tile: sized for the longest slab list
-  for (int c = 0; c < nchunks; c++) mid_cap = std::max(mid_cap, 7 * (first[(size_t)c + 1] - first[(size_t)c] + 64));
-  if (d_tiles.alloc(tiles.size() * sizeof(int4)) || d_gang.alloc(sizeof(int) * (32 + mid_cap))) return 1;
-  MXA_HIP(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  std::vector<XEvent> ev((size_t)nchunks);
-  int dev = 0;
-  MXA_HIP(hipGetDevice(&dev));
-  for (auto &e : ev) if (e.create(hipEventDisableTiming)) return 1;
-  XEvent e0, e1;
-  if (e0.create() || e1.create()) return 1;
-  std::atomic<int> launched{0}, copy_err{0};
-  std::atomic<bool> abort_copy{false};
-  std::vector<std::atomic<int>> copied((size_t)nchunks);
-  for (auto &c : copied) c.store(0);
-  XStream cs[kCopiers];
-  for (auto &c : cs) if (c.create(hipStreamNonBlocking)) return 1;
-  struct CopierLog { double wait_s = 0, copy_s = 0, worst_s = 0; int worst_slab = -1; size_t bytes = 0; };
-  CopierLog clog[kCopiers];
-  const auto t_call = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  auto copy_loop = [&](int t) {
+  auto copy_loop = [&](int th) {
     if (hipSetDevice(dev) != hipSuccess) { copy_err = 1; abort_copy = true; return; }
     for (int c = 0; c < nchunks; c++) {
       const auto tw = std::chrono::steady_clock::now();
       while (launched.load() <= c) { if (abort_copy.load()) return; std::this_thread::yield(); }
       if (hipEventSynchronize(ev[c].e) != hipSuccess) { copy_err = 1; abort_copy = true; return; }
-      clog[t].wait_s += since(tw);
-      const long col0 = (long)c * tcols * kXT, col1 = std::min<long>(rows, (long)(c + 1) * tcols * kXT);
-      const long w = col1 - col0, a = w * t / kCopiers, b = w * (t + 1) / kCopiers;   // columns of the slab, relative
+      clog[th].wait_s += since(tw);
+      const long width = col0(c + 1) - col0(c), a = col0(c) + width * th / kCopiers, b = col0(c) + width * (th + 1) / kCopiers;   // this copier's columns
       if (b > a) {
-        const double *src = (const double *)ring[c % kRing].p + (size_t)a * rows;
+        const auto [o, oc0] = out(c);
         const size_t cnt = (size_t)(b - a) * rows;
-        if (pf) { const auto tp = std::chrono::steady_clock::now(); pf->wait_for(h_ans + (size_t)(col0 + a) * rows + cnt); clog[t].wait_s += since(tp); }   // the destination pages exist: no faults inside the copy
+        double *dst = h_ans + (size_t)a * rows;
+        const auto tp = std::chrono::steady_clock::now();
+        pf.wait_for(dst + cnt);   // the destination pages exist: no faults inside the copy
+        clog[th].wait_s += since(tp);
         const auto tc = std::chrono::steady_clock::now();
-        if (hipMemcpyAsync(h_ans + (size_t)(col0 + a) * rows, src, cnt * sizeof(double), hipMemcpyDeviceToHost, cs[t].s) != hipSuccess || hipStreamSynchronize(cs[t].s) != hipSuccess) { copy_err = 1; abort_copy = true; return; }
+        if (hipMemcpyAsync(dst, o + (size_t)(a - oc0) * rows, cnt * sizeof(double), hipMemcpyDeviceToHost, cs[th].s) != hipSuccess ||
+            hipStreamSynchronize(cs[th].s) != hipSuccess) { copy_err = 1; abort_copy = true; return; }
         const double dt = since(tc);
-        clog[t].copy_s += dt; clog[t].bytes += cnt * sizeof(double);
-        if (dt > clog[t].worst_s) { clog[t].worst_s = dt; clog[t].worst_slab = c; }
+        clog[th].copy_s += dt; clog[th].bytes += cnt * sizeof(double);
+        if (dt > clog[th].worst_s) { clog[th].worst_s = dt; clog[th].worst_slab = c; }
       }
       copied[(size_t)c].fetch_add(1);
     }
   };
-  all_allocated();   // every device buffer, stream and event of this call exists: the background population of the destination pages may start (mxa_hostmem.h)
+  // the ring's destination pages are populated from here on: every device buffer, stream and event of the call exists (mxa_hostmem.h; the other form's
+  // population started when crossprod_any had allocated d_ans)
+  if (ring) pf.start(h_ans, (size_t)rows * (size_t)rows * sizeof(double));
   std::vector<std::thread> copiers;
-  for (int t = 0; t < kCopiers; t++) copiers.emplace_back(copy_loop, t);
+  for (int th = 0; th < kCopiers; th++) copiers.emplace_back(copy_loop, th);
   int rc = 0;
   double t_wait_slot = 0.0;
   if (hipEventRecord(e0.e, s) != hipSuccess) rc = 1;
   for (int c = 0; c < nchunks && !rc; c++) {
-    if (c >= kRing) {   // the slot is free once all copiers have taken slab c - kRing out of it
+    if (ring && c >= kRing) {   // the slot is free once all copiers have taken chunk c - kRing out of it
       const auto tw = std::chrono::steady_clock::now();
       while (copied[(size_t)(c - kRing)].load() < kCopiers) { if (abort_copy.load()) { rc = 1; break; } std::this_thread::yield(); }
       t_wait_slot += since(tw);
       if (rc) break;
     }
-    const size_t cnt = first[(size_t)c + 1] - first[(size_t)c];
-    const long col0 = (long)c * tcols * kXT;
-    if (launch_tiles(f4, cnt, s, d_X, nslabs, stages, (const int4 *)d_tiles.p + first[(size_t)c], rows, (double *)ring[c % kRing].p, rows, col0, nullptr, post ? post_kind : 0, post ? *post : XPost(),
-                     chunk_xcd[(size_t)c] ? (int *)d_gang.p : nullptr, mid_cap) || hipEventRecord(ev[c].e, s) != hipSuccess) { rc = 1; break; }
+    const auto [o, oc0] = out(c);
+    if (t.launch(c, g, f4, s, d_X, o, rows, oc0, nullptr, post_kind, post) || hipEventRecord(ev[c].e, s) != hipSuccess) { rc = 1; break; }
     launched.store(c + 1);
   }
   if (rc) abort_copy = true;
   if (!rc && hipEventRecord(e1.e, s) != hipSuccess) rc = 1;
   const double t_launched = since(t_call);
-  for (auto &t : copiers) t.join();
+  for (auto &th : copiers) th.join();
   if (hipStreamSynchronize(s) != hipSuccess) rc = 1;
-  for (int t = 0; t < kCopiers; t++)
-    debug_info("crossproduct host result (ring of %d slabs): copier %d waited %.3f s for slabs, copied %.2f GB in %.3f s (%.1f GB/s), slowest single copy %.3f s (slab %d of %d)", kRing, t, clog[t].wait_s,
-               clog[t].bytes * 1e-9, clog[t].copy_s, clog[t].copy_s > 0 ? clog[t].bytes * 1e-9 / clog[t].copy_s : 0.0, clog[t].worst_s, clog[t].worst_slab, nchunks);
-  debug_info("crossproduct host result (ring): %d slab launches enqueued after %.3f s (%.3f s of it waiting for a free slot), all copies done after %.3f s", nchunks, t_launched, t_wait_slot, since(t_call));
-  if (!rc && !copy_err.load()) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e0.e, e1.e) == hipSuccess) { std::lock_guard<std::mutex> lk(g_xprof_mutex); profile().launches += 1; profile().total_ms += ms; }
-  }
+  char form[32] = "";
+  if (ring) snprintf(form, sizeof form, " (ring of %d slabs)", kRing);
+  for (int th = 0; th < kCopiers; th++)
+    debug_info("crossproduct host result%s: copier %d waited %.3f s for slabs, copied %.2f GB in %.3f s (%.1f GB/s), slowest single copy %.3f s (slab %d of %d)", form, th,
+               clog[th].wait_s, clog[th].bytes * 1e-9, clog[th].copy_s, clog[th].copy_s > 0 ? clog[th].bytes * 1e-9 / clog[th].copy_s : 0.0, clog[th].worst_s,
+               clog[th].worst_slab, nchunks);
+  if (ring) debug_info("crossproduct host result (ring): %d slab launches enqueued after %.3f s (%.3f s of it waiting for a free slot), all copies done after %.3f s", nchunks, t_launched, t_wait_slot, since(t_call));
+  else debug_info("crossproduct host result: %d slab launches enqueued after %.3f s, all copies done after %.3f s", nchunks, t_launched, since(t_call));
+  if (!rc && !copy_err.load()) (void)profile_launch(e0, e1);
   if (rc || copy_err.load()) { set_error(13, "snp_multiply_gpu: pipelined device-to-host copy of the result failed"); return 1; }
   return 0;
 }
@@ -1087,6 +992,64 @@ static int postprocess_device(double *d_M, long rows, long k, int post, int do_s
   return 0;
 }
 
+// X (rows of row_bytes packed bytes, in device or host memory) -> d_X, zeroed first, in the tiled layout (k_xstage; is_plink: the reference's table);
+// *d_has3 = 1 when a staged field holds the value 3.  Host rows go through `bounce` (<= 256 MiB: kept by the caller, the pre-flight counts it).
+static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, bool is_plink, const XGeom &g, uint8_t *d_X, int *d_has3, XBuf &bounce,
+                         hipStream_t s) {
+  const long rows = g.rows;
+  MXA_HIP(hipMemsetAsync(d_X, 0, (size_t)g.rows_pad() * g.pitch(), s));
+  MXA_HIP(hipMemsetAsync(d_has3, 0, sizeof(int), s));
+  if (in_dev) {
+    const long total = rows * ((row_bytes + 3) / 4);
+    hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, snp_matrix, (size_t)row_bytes, row_bytes, rows, d_X, g.nslabs, 0L,
+                       is_plink ? 1 : 0, d_has3);
+    MXA_HIP(hipGetLastError());
+    return 0;
+  }
+  long chunk_rows = std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)row_bytes));
+  chunk_rows = std::min(chunk_rows, rows);
+  if (bounce.alloc((size_t)chunk_rows * row_bytes)) return 1;
+  for (long r0 = 0; r0 < rows; r0 += chunk_rows) {
+    const long nr = std::min(chunk_rows, rows - r0);
+    MXA_HIP(hipMemcpyAsync(bounce.p, snp_matrix + (size_t)r0 * row_bytes, (size_t)nr * row_bytes, hipMemcpyHostToDevice, s));
+    const long total = nr * ((row_bytes + 3) / 4);
+    hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, (const uint8_t *)bounce.p, (size_t)row_bytes, row_bytes, nr, d_X,
+                       g.nslabs, r0, is_plink ? 1 : 0, d_has3);
+    MXA_HIP(hipGetLastError());
+    MXA_HIP(hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+// What the GRM (post 1) / LD (post 2) map fused into the epilogue needs, from the staged 2-bit matrix: ~2 passes over rows * k / 4 bytes instead of 3 over
+// 8 * rows^2.  xp points into st[2]; st[0..2] are kept by the caller until the product has run.
+static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post, int do_scale, const double *d_f, XBuf (&st)[3], hipStream_t s, XPost &xp) {
+  const long rows = g.rows, rows_pad = g.rows_pad(), nslabs = g.nslabs, ntiles = g.nb;
+  if (st[0].alloc(sizeof(int) * (size_t)nslabs * 128) || st[1].alloc(sizeof(unsigned long long) * (size_t)rows_pad) || st[2].alloc(sizeof(double) * (size_t)(rows_pad + 4))) return 1;
+  MXA_HIP(hipMemsetAsync(st[1].p, 0, sizeof(unsigned long long) * (size_t)rows_pad, s));
+  int *t = (int *)st[0].p;
+  unsigned long long *raw = (unsigned long long *)st[1].p;
+  double *out = (double *)st[2].p;
+  const long chunks = std::max<long>(1, std::min<long>(nslabs, (1024 + ntiles - 1) / ntiles));   // >= ~1024 blocks
+  const long spc = (nslabs + chunks - 1) / chunks;
+  const dim3 g_rows((unsigned)ntiles, (unsigned)((nslabs + spc - 1) / spc));
+  const unsigned g_fin = (unsigned)((rows + 255) / 256);
+  if (post == 1) {
+    hipLaunchKernelGGL(k_x_colsum, dim3((unsigned)nslabs), dim3(256), 0, s, d_X, nslabs, ntiles, t);
+    hipLaunchKernelGGL((k_x_rowstats<true, false>), g_rows, dim3(256), 0, s, d_X, nslabs, spc, (const int *)t, raw, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(k_x_finish_stats, dim3(g_fin), dim3(256), 0, s, raw, rows, (const double *)nullptr, 0.0, out);
+    hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, out, rows, 0, out + rows_pad);
+    if (do_scale) hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, d_f, k, 1, out + rows_pad + 1);
+    xp.u = out; xp.scal = out + rows_pad; xp.a = 1.0 / (double)rows; xp.do_scale = do_scale;
+  } else {
+    hipLaunchKernelGGL((k_x_rowstats<false, true>), g_rows, dim3(256), 0, s, d_X, nslabs, spc, (const int *)nullptr, (unsigned long long *)nullptr, raw);
+    hipLaunchKernelGGL(k_x_finish_stats, dim3(g_fin), dim3(256), 0, s, raw, rows, d_f, 4.0 * (double)k, out);
+    xp.u = d_f; xp.w = out; xp.a = 4.0 * (double)k;
+  }
+  MXA_HIP(hipGetLastError());
+  return 0;
+}
+
 static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, double *ans, bool is_plink, int post = 0, int do_scale = 0,
                          const double *freq = nullptr, long c_begin = 0, long c_end = -1, bool upper_only = false, long ld = -1, int device = -1) {
   if (c_end < 0) c_end = rows;
@@ -1094,21 +1057,23 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   if (!snp_matrix || !ans || k <= 0 || rows <= 0) { set_error(1, "snp_multiply_gpu: bad arguments"); return 1; }
   if (device >= 0) MXA_HIP(hipSetDevice(device));
   else if (select_device() < 0) return 1;   // HIP_DEVICE / CUDA_DEVICE with the range check; GPU-only
+  const XGeom g(k, rows);
   const long row_bytes = (k + 3) / 4;
-  const long rows_pad = (rows + kXT - 1) / kXT * kXT;
-  const long nslabs = (k + kXStageK - 1) / kXStageK;
-  const size_t pitch = (size_t)nslabs * kXStageBytes;
   const bool in_dev = ptr_location(snp_matrix, nullptr) == 1, out_dev = ptr_location(ans, nullptr) == 1;
   if (c_begin < 0 || c_begin >= c_end || c_end > rows || c_begin % kXT != 0 || (c_end % kXT != 0 && c_end != rows) || ld < (upper_only ? c_end : rows)) {
     set_error(1, "crossproduct panel: need 0 <= col_begin < col_end <= n, col_begin %% %d == 0, col_end %% %d == 0 or col_end == n, ld >= rows written", kXT, kXT);
     return 1;
   }
-  const size_t xbytes = (size_t)rows_pad * pitch, abytes = (size_t)ld * (size_t)(c_end - c_begin) * sizeof(double);
+  const bool whole = c_begin == 0 && c_end == rows && !upper_only;
+  // a whole-matrix host result leaves slab by slab (crossprod_slabs) unless MXA_XPROD_NO_PIPELINE asks for one copy at the end
+  const bool pipelined = !out_dev && whole && ld == rows && !getenv("MXA_XPROD_NO_PIPELINE");
+  const char *e_fused = getenv("MXA_XPROD_FUSED_POST");   // read per call (tests compare both paths bit for bit)
+  const bool fused_on = !e_fused || atoi(e_fused) != 0;
+  const size_t xbytes = (size_t)g.rows_pad() * g.pitch(), abytes = (size_t)ld * (size_t)(c_end - c_begin) * sizeof(double);
   size_t free_b = 0, total_b = 0;
   MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-  // a whole-matrix host result can leave through a ring of three ~1 GiB slabs (crossprod_to_host_ring): the n x n device copy is then not needed
-  const bool ring_ok = !out_dev && c_begin == 0 && c_end == rows && !upper_only && ld == rows && !getenv("MXA_XPROD_NO_PIPELINE");
-  const size_t out_need = out_dev ? 0 : (ring_ok ? std::min<size_t>(abytes, (size_t)3400 << 20) : abytes);
+  // a pipelined result can leave through the ring of three ~1 GiB slabs: the n x n device copy is then not needed
+  const size_t out_need = out_dev ? 0 : (pipelined ? std::min<size_t>(abytes, (size_t)3400 << 20) : abytes);
   const size_t need = xbytes + out_need + (in_dev ? 0 : std::min<size_t>((size_t)rows * row_bytes, (size_t)256 << 20));
   if (need > free_b) { set_error(12, "snp_multiply_gpu: not enough device memory: required %zu GB, free %zu GB", need >> 30, free_b >> 30); return 1; }
   // a host result in fresh memory (crossproduct.jl:56 `M = zeros(...)`): its pages are populated in the background while the tiles are computed, so that
@@ -1141,79 +1106,52 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
   hipStream_t s = st.s;
   XBuf d_X, bounce, d_out, d_flag, f_tmp;
-  // the n x n device buffer of a host result that does not take the slab ring: checked against the free memory first, so that what does not fit is reported
-  // like the reference's pre-flight (cuda_utils.cu:162-185) instead of as a raw hipMalloc failure
-  auto alloc_result = [&](XBuf &b, size_t bytes) -> int {
-    size_t fb = 0, tb = 0;
-    if (hipMemGetInfo(&fb, &tb) == hipSuccess && bytes > fb) {
-      set_error(12, "Not enough device memory available. Required %zu GB, free %zu GB, total on device %zu GB", bytes >> 30, fb >> 30, tb >> 30);
-      return 1;
-    }
-    (void)hipGetLastError();
-    return b.alloc(bytes);
-  };
   if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int))) return 1;
   clk.mark("operand buffer allocated");
-  MXA_HIP(hipMemsetAsync(d_X.p, 0, xbytes, s));
-  MXA_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(int), s));
-  if (in_dev) {
-    const long total = rows * ((row_bytes + 3) / 4);
-    hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, snp_matrix, (size_t)row_bytes, row_bytes, rows, (uint8_t *)d_X.p, nslabs, 0L,
-                       is_plink ? 1 : 0, (int *)d_flag.p);
-    MXA_HIP(hipGetLastError());
-  } else {
-    long chunk_rows = std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)row_bytes));
-    chunk_rows = std::min(chunk_rows, rows);
-    if (bounce.alloc((size_t)chunk_rows * row_bytes)) return 1;
-    for (long r0 = 0; r0 < rows; r0 += chunk_rows) {
-      const long nr = std::min(chunk_rows, rows - r0);
-      MXA_HIP(hipMemcpyAsync(bounce.p, snp_matrix + (size_t)r0 * row_bytes, (size_t)nr * row_bytes, hipMemcpyHostToDevice, s));
-      const long total = nr * ((row_bytes + 3) / 4);
-      hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, (const uint8_t *)bounce.p, (size_t)row_bytes, row_bytes, nr, (uint8_t *)d_X.p,
-                         nslabs, r0, is_plink ? 1 : 0, (int *)d_flag.p);
-      MXA_HIP(hipGetLastError());
-      MXA_HIP(hipStreamSynchronize(s));
-    }
-  }
+  if (stage_operand(snp_matrix, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s)) return 1;
   clk.mark("operand staged (upload + k_xstage)");
-  bool prefault_started = false;
-  auto start_prefault = [&]() { if (!out_dev && !prefault_started) { prefault_started = true; prefault.start(ans, abytes); } };
   // engine: FP4 while the fp32 accumulator is provably exact (sum z z' < 2^24), int8 beyond (MXA_XPROD_ENGINE=i8 / f4 forces one, for A/B runs)
   int has3 = 1;
   MXA_HIP(hipMemcpyAsync(&has3, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
   MXA_HIP(hipStreamSynchronize(s));
   bool f4 = has3 ? 9 * k < (1L << 24) : 4 * k < (1L << 24);
   if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
-  double *d_ans = ans;
-  const bool whole0 = c_begin == 0 && c_end == rows && !upper_only;
-  const char *e_fused0 = getenv("MXA_XPROD_FUSED_POST");
-  const bool fused_possible = (!e_fused0 || atoi(e_fused0) != 0) && whole0;
-  // host result of the whole matrix: ring of column slabs (no n x n device buffer) where the call is bound by the download anyway -- the ring computes
-  // every off-diagonal tile twice.  Estimates: triangular arithmetic at the measured tile rate against the download at ~55 GB/s of four copiers.
-  // MXA_XPROD_HOST_RING: 0 never, 1 by this estimate (default), 2 always (tests).
-  bool use_ring = false;
-  if (!out_dev && whole0 && ld == rows && !getenv("MXA_XPROD_NO_PIPELINE")) {
+
+  // ---- the route, decided once the engine is known: the result on the device (out_dev), or a host result through ONE copy of an n x n device buffer,
+  // through the slab pipeline into that buffer, or through the pipeline's ring of column slabs with no such buffer at all.
+  // GRM / LD: the element-wise map is fused into the crossproduct epilogue (whole matrix; MXA_XPROD_FUSED_POST=0 keeps the three extra passes over the result).
+  constexpr long kXFusedMaxRows = 29000000L;   // k_x_rowstats: 16 * 3 * (3 rows) must fit 32 bits; beyond that the three-pass post-processing runs
+  const int post_kind = post && fused_on && whole && rows < kXFusedMaxRows ? post : 0;
+  const bool slabs = pipelined && (!post || post_kind);   // unfused post-processing needs the whole matrix on the device: one copy, even where the ring would go
+  // the ring where the call is bound by the download anyway -- the ring computes every off-diagonal tile twice.  Estimates: triangular arithmetic at the
+  // measured tile rate against the download at ~55 GB/s of four copiers.  MXA_XPROD_HOST_RING: 0 never, 1 by this estimate (default), 2 always (tests).
+  bool ring = false;
+  if (slabs) {
     const char *e_ring = getenv("MXA_XPROD_HOST_RING");
     const int ring_mode = e_ring ? atoi(e_ring) : 1;
-    const double nbt = (double)((rows + kXT - 1) / kXT), tri_ms = (double)nslabs * (f4 ? 0.66e-3 : 1.0e-3) * nbt * (nbt + 1.0) / 2.0 / 256.0, copy_ms = (double)abytes / 55e9 * 1e3;
-    use_ring = ring_mode >= 2 || (ring_mode == 1 && abytes >= ((size_t)4 << 30) && 2.0 * tri_ms <= 1.15 * copy_ms);
-    if (!use_ring && ring_mode >= 1 && (!post || fused_possible)) {   // a result that does not fit the free device memory can only leave through the ring
+    const double nbt = (double)g.nb, tri_ms = (double)g.nslabs * tile_stage_ms(f4) * nbt * (nbt + 1.0) / 2.0 / 256.0, copy_ms = (double)abytes / 55e9 * 1e3;
+    ring = ring_mode >= 2 || (ring_mode == 1 && abytes >= ((size_t)4 << 30) && 2.0 * tri_ms <= 1.15 * copy_ms);
+    if (!ring && ring_mode >= 1) {   // a result that does not fit the free device memory can only leave through the ring
       size_t fb = 0, tb = 0;
-      if (hipMemGetInfo(&fb, &tb) == hipSuccess && abytes + ((size_t)1 << 30) > fb) use_ring = true;
+      if (hipMemGetInfo(&fb, &tb) == hipSuccess && abytes + ((size_t)1 << 30) > fb) ring = true;
     }
   }
-  if (!out_dev && !use_ring) {
-    if (alloc_result(d_out, abytes)) return 1;
+  double *d_ans = out_dev ? ans : nullptr;
+  if (!out_dev && !ring) {
+    // checked against the free memory first, so that what does not fit is reported like the reference's pre-flight (cuda_utils.cu:162-185) instead of
+    // as a raw hipMalloc failure
+    size_t fb = 0, tb = 0;
+    if (hipMemGetInfo(&fb, &tb) == hipSuccess && abytes > fb) {
+      set_error(12, "Not enough device memory available. Required %zu GB, free %zu GB, total on device %zu GB", abytes >> 30, fb >> 30, tb >> 30);
+      return 1;
+    }
+    (void)hipGetLastError();
+    if (d_out.alloc(abytes)) return 1;
     d_ans = (double *)d_out.p;
     if (upper_only) MXA_HIP(hipMemsetAsync(d_ans, 0, abytes, s));   // the untouched part travels back as zeros
     clk.mark("device result buffer allocated");
-    start_prefault();
-  } else if (!out_dev) d_ans = nullptr;
-  const bool whole = c_begin == 0 && c_end == rows && !upper_only;
-  // GRM / LD: the element-wise map is fused into the crossproduct epilogue (whole matrix; MXA_XPROD_FUSED_POST=0 keeps the three extra passes over
-  // the result).  What the map needs comes from the staged 2-bit matrix: ~2 passes over rows * k / 4 bytes instead of 3 over 8 * rows^2.
-  const char *e_fused = getenv("MXA_XPROD_FUSED_POST");   // read per call (tests compare both paths bit for bit)
-  const bool fused_on = !e_fused || atoi(e_fused) != 0;
+    prefault.start(ans, abytes);
+  }
   const double *d_f = freq;
   if (post && freq && ptr_location(freq, nullptr) != 1) {
     const long flen = post == 1 ? k : rows;
@@ -1222,54 +1160,16 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
     d_f = (const double *)f_tmp.p;
   }
   XPost xp;
-  int post_kind = 0;
-  XBuf st_t, st_raw, st_out;
-  constexpr long kXFusedMaxRows = 29000000L;   // k_x_rowstats: 16 * 3 * (3 rows) must fit 32 bits; beyond that the three-pass post-processing runs
-  if (post && fused_on && whole && rows < kXFusedMaxRows) {
-    const long ntiles = rows_pad / kXT;
-    if (st_t.alloc(sizeof(int) * (size_t)nslabs * 128) || st_raw.alloc(sizeof(unsigned long long) * (size_t)rows_pad) || st_out.alloc(sizeof(double) * (size_t)(rows_pad + 4))) return 1;
-    MXA_HIP(hipMemsetAsync(st_raw.p, 0, sizeof(unsigned long long) * (size_t)rows_pad, s));
-    unsigned long long *raw = (unsigned long long *)st_raw.p;
-    double *out = (double *)st_out.p;
-    const long chunks = std::max<long>(1, std::min<long>(nslabs, (1024 + ntiles - 1) / ntiles));   // >= ~1024 blocks
-    const long spc = (nslabs + chunks - 1) / chunks;
-    const dim3 g_rows((unsigned)ntiles, (unsigned)((nslabs + spc - 1) / spc));
-    const unsigned g_fin = (unsigned)((rows + 255) / 256);
-    if (post == 1) {
-      hipLaunchKernelGGL(k_x_colsum, dim3((unsigned)nslabs), dim3(256), 0, s, (const uint8_t *)d_X.p, nslabs, ntiles, (int *)st_t.p);
-      hipLaunchKernelGGL((k_x_rowstats<true, false>), g_rows, dim3(256), 0, s, (const uint8_t *)d_X.p, nslabs, spc, (const int *)st_t.p, raw, (unsigned long long *)nullptr);
-      hipLaunchKernelGGL(k_x_finish_stats, dim3(g_fin), dim3(256), 0, s, raw, rows, (const double *)nullptr, 0.0, out);
-      hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, out, rows, 0, out + rows_pad);
-      if (do_scale) hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, d_f, k, 1, out + rows_pad + 1);
-      xp.u = out; xp.scal = out + rows_pad; xp.a = 1.0 / (double)rows; xp.do_scale = do_scale;
-    } else {
-      hipLaunchKernelGGL((k_x_rowstats<false, true>), g_rows, dim3(256), 0, s, (const uint8_t *)d_X.p, nslabs, spc, (const int *)nullptr, (unsigned long long *)nullptr, raw);
-      hipLaunchKernelGGL(k_x_finish_stats, dim3(g_fin), dim3(256), 0, s, raw, rows, d_f, 4.0 * (double)k, out);
-      xp.u = d_f; xp.w = out; xp.a = 4.0 * (double)k;
-    }
-    MXA_HIP(hipGetLastError());
-    post_kind = post;
-  }
-  if (use_ring && (!post || post_kind)) {
-    const int rc = crossprod_to_host_ring((const uint8_t *)d_X.p, k, rows, pitch, ans, s, f4, post_kind, &xp, start_prefault, &prefault);
-    clk.mark("slabs computed and copied out (ring)");
-    d_X.release();
-    clk.mark("device buffers released");
-    return rc;
-  }
-  if (use_ring) {   // unfused post-processing needs the whole matrix on the device after all
-    if (alloc_result(d_out, abytes)) return 1;
-    d_ans = (double *)d_out.p;
-    start_prefault();
-  }
-  if (!out_dev && (!post || post_kind) && whole && ld == rows && !getenv("MXA_XPROD_NO_PIPELINE")) {
-    const int rc = crossprod_to_host((const uint8_t *)d_X.p, k, rows, pitch, d_ans, ans, s, f4, post_kind, &xp, &prefault);
-    clk.mark("tiles computed, slabs copied out");
+  XBuf stats[3];
+  if (post_kind && fused_post_stats(g, (const uint8_t *)d_X.p, k, post, do_scale, d_f, stats, s, xp)) return 1;
+  if (slabs) {
+    const int rc = crossprod_slabs(g, (const uint8_t *)d_X.p, d_ans, ans, s, f4, post_kind, xp, ring, prefault);
+    clk.mark(ring ? "slabs computed and copied out (ring)" : "tiles computed, slabs copied out");
     d_out.release(); d_X.release();
     clk.mark("device buffers released");
     return rc;
   }
-  if (crossprod_device((const uint8_t *)d_X.p, k, rows, pitch, d_ans, s, c_begin, c_end, upper_only, ld, f4, post_kind, &xp)) return 1;
+  if (crossprod_device(g, (const uint8_t *)d_X.p, d_ans, s, c_begin, c_end, upper_only, ld, f4, post_kind, xp)) return 1;
   if (post && !post_kind && postprocess_device(d_ans, rows, k, post, do_scale, d_f, s)) return 1;
   clk.mark("tile list built, product enqueued");
   if (!out_dev) MXA_HIP(hipMemcpyAsync(ans, d_ans, abytes, hipMemcpyDeviceToHost, s));

@@ -139,7 +139,7 @@ def test_crossprod_host_result_is_pipelined_in_slabs(monkeypatch):
 
 @pytest.mark.parametrize("slab_mb,rows", [("5", 2305), ("9", 2305), ("3", 1290)])
 def test_crossprod_host_result_through_the_slab_ring(monkeypatch, slab_mb, rows):
-    """Host result without an n x n device buffer (round 4: crossprod_to_host_ring): the matrix is produced column slab by column slab into a ring
+    """Host result without an n x n device buffer (round 4: the ring form of crossprod_slabs): the matrix is produced column slab by column slab into a ring
     of three device buffers -- every slab the column panel of mxa_snp_multiply_panel -- and copied out while the next slab computes.  Forced here
     (MXA_XPROD_HOST_RING=2) with small slabs so that the ring wraps several times (10 slabs of one tile column, 5 of two, 6 of one); the default
     takes it for results of 4 GB and more whose download outlasts twice the triangular arithmetic (tests/test_fullsize_configs_gpu.py runs

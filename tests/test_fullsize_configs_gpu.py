@@ -196,7 +196,7 @@ def test_c3_sampled_tiles_vs_oracle(c3):
 
 def test_c3_host_result_through_the_plain_abi():
     """the reference's own calling convention (host snp_matrix, host ans; crossproduct.jl:54-58) at K = 500 000 with a 12.8 GB result: the
-    staged upload, the tile-row chunks and the four copier threads of the pipelined copy-out (mxa_crossprod.hip: crossprod_to_host) against the
+    staged upload, the tile-row chunks and the four copier threads of the pipelined copy-out (mxa_crossprod.hip: crossprod_slabs) against the
     device-resident result of the same rows (bitwise) and the oracle on a sampled tile"""
     import torch
     import miraculix_amd as mx

@@ -300,6 +300,23 @@ int mxa_grm(const unsigned char *plink_transposed, int snps, int indiv, double *
             const double *allele_freq);
 int mxa_ld(const unsigned char *plink, int snps, int indiv, double *R, int is_plink_format, const double *allele_freq);
 
+/* Windowed LD: the entries of mxa_ld's R within `window` SNPs of the diagonal, without the snps x snps matrix -- O(snps * window) work and memory, so
+ * LD at 1 000 000 SNPs is one call.  Arguments as mxa_ld (plink = snps rows of ceil(indiv/4) bytes; every pointer host or device); window = number of
+ * neighbours on each side, counted in SNPs, 0 <= window < snps.  A chromosome is a row range of the SNP-major matrix: a pointer offset and a smaller snps.
+ * mxa_ld_band  : band[d + i*ldb] = R(i, i+d) for 0 <= d <= window, i + d < snps; 0.0 where i + d >= snps; rows d > window of a wider ldb (>= window + 1)
+ *                are not touched.  This is LAPACK's lower symmetric band storage AB(1+i-j, j) = A(i, j) (dsbmv, dpbtrf).  kind 0: r, 1: r^2 (r*r, one rounding).
+ * mxa_ld_scores: scores[i] = sum over j, |i-j| <= window (j = i included), of t(r_ij); adjust 0: t = r^2, 1: t = r^2 - (1 - r^2) / (indiv - 2), formed as
+ *                r2 - (1 - r2) * (1 / (indiv - 2)) with every operation rounded (needs indiv >= 3).  The band is never written to memory.
+ * R is mxa_ld's R bit for bit (same staging, byte table, statistics and map), from the same two exact engines; the scores are sums in a fixed order
+ * (no atomics): identical from run to run and between the engines.  A monomorphic SNP has sigma = 0: its entries are non-finite exactly as mxa_ld's
+ * are, and a score whose window holds such an entry is non-finite -- no special case; filter such SNPs before the call.
+ * Errors (return 1, mxa_last_error() == 1, output untouched): window out of range, ldb < window + 1, kind / adjust not 0 or 1, adjust with indiv < 3,
+ * allele_freq == NULL, snps >= 29 000 000; 12: not enough device memory.  Runs on the selected device (no MIRACULIX_NUM_GPUS sharding). */
+int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind, int is_plink_format,
+                const double *allele_freq);
+int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust, int is_plink_format,
+                  const double *allele_freq);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

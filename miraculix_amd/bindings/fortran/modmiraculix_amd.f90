@@ -14,6 +14,7 @@ module modmiraculix_amd
  public :: mxa_last_error, mxa_device_count, mxa_bed2compressed, mxa_gram_matvec, mxa_set_engine, mxa_get_engine, mxa_last_path
  public :: mxa_single_orientation, mxa_num_shards, mxa_allele_freq, mxa_transpose_2bit
  public :: mxa_plink2compressed_begin, mxa_plink2compressed_rows, mxa_plink2compressed_end
+ public :: mxa_ld_band, mxa_ld_scores
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -123,6 +124,23 @@ module modmiraculix_amd
    import c_int, c_long, c_ptr
    type(c_ptr), value, intent(in) :: in, out
    integer(c_long), value, intent(in) :: rows, cols
+   integer(c_int) :: rc
+  end function
+
+  ! windowed LD (plink = snps rows of ceil(indiv/4) bytes, host or device like every pointer here; window = neighbours on each side, 0 <= window < snps):
+  ! band(d + 1, i + 1) = R(i, i + d), 0 <= d <= window -- a (ldb, snps) array in LAPACK's lower symmetric band storage (dsbmv / dpbtrf 'L'); kind 0: r, 1: r^2
+  function mxa_ld_band(plink, snps, indiv, window, band, ldb, kind, is_plink_format, allele_freq) bind(C, name='mxa_ld_band') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, band, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, window, kind, is_plink_format
+   integer(c_long), value, intent(in) :: ldb
+   integer(c_int) :: rc
+  end function
+  ! scores(i + 1) = sum over |i - j| <= window of r_ij^2 (adjust = 1: of r^2 - (1 - r^2) / (indiv - 2)); the band is never written
+  function mxa_ld_scores(plink, snps, indiv, window, scores, adjust, is_plink_format, allele_freq) bind(C, name='mxa_ld_scores') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, scores, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, window, adjust, is_plink_format
    integer(c_int) :: rc
   end function
 

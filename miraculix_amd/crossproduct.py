@@ -92,3 +92,57 @@ def ld(plink, snps, indiv, is_plink_format=False, allele_freq=None):
     if rc != 0:
         raise RuntimeError("mxa_ld failed: " + _lib.last_error()[1])
     return R
+
+
+def ld_band_tiles(snps, window):
+    """The tile plan of the windowed LD entries, restated: the 256 x 256 tiles (I, J), I <= J, that hold an element (i, j) with 0 <= j - i <= window.
+    Tile (I, J) holds the offsets j - i in [256 (J - I) - 255, 256 (J - I) + 255], so it meets the band iff J - I <= (window + 255) // 256 = ceil(window / 256)."""
+    nb = (snps + 255) // 256
+    ndiag = (window + 255) // 256
+    return [(i, j) for i in range(nb) for j in range(i, min(nb, i + ndiag + 1))]
+
+
+def _ld_window_args(plink, snps, indiv, window, allele_freq):
+    if allele_freq is None or len(allele_freq) != snps:
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    if int(np.prod(plink.shape)) != snps * ((indiv + 3) // 4):
+        raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
+    if not 0 <= int(window) < snps:
+        raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+    return allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+
+
+def ld_band(plink, snps, indiv, window, kind="r", is_plink_format=False, allele_freq=None):
+    """Additive (C entry mxa_ld_band): the band of ld()'s R within `window` SNPs of the diagonal, shape (snps, window + 1) with out[i, d] = R(i, i + d)
+    (0.0 where i + d >= snps) -- LAPACK's lower symmetric band storage, column by column.  kind "r" or "r2".  The snps x snps matrix is never formed."""
+    if kind not in ("r", "r2"):
+        raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+    f = _ld_window_args(plink, snps, indiv, window, allele_freq)
+    L = _lib.check_library_handle()
+    if _lib.is_torch_tensor(plink):
+        import torch
+        B = torch.zeros((snps, int(window) + 1), dtype=torch.float64, device=plink.device)
+    else:
+        B = np.zeros((snps, int(window) + 1), dtype=np.float64)
+    rc = L.mxa_ld_band(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0, int(bool(is_plink_format)), _lib.ptr(f))
+    if rc != 0:
+        raise RuntimeError("mxa_ld_band failed: " + _lib.last_error()[1])
+    return B
+
+
+def ld_scores(plink, snps, indiv, window, adjust=False, is_plink_format=False, allele_freq=None):
+    """Additive (C entry mxa_ld_scores): LD scores l_i = sum over |i - j| <= window of r_ij^2 (adjust: of r^2 - (1 - r^2) / (indiv - 2), the estimator of
+    LD-score regression), shape (snps,).  Neither the matrix nor the band is written to memory; the sums run in a fixed order (bitwise reproducible)."""
+    f = _ld_window_args(plink, snps, indiv, window, allele_freq)
+    if adjust and indiv < 3:
+        raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
+    L = _lib.check_library_handle()
+    if _lib.is_torch_tensor(plink):
+        import torch
+        S = torch.zeros(snps, dtype=torch.float64, device=plink.device)
+    else:
+        S = np.zeros(snps, dtype=np.float64)
+    rc = L.mxa_ld_scores(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust)), int(bool(is_plink_format)), _lib.ptr(f))
+    if rc != 0:
+        raise RuntimeError("mxa_ld_scores failed: " + _lib.last_error()[1])
+    return S

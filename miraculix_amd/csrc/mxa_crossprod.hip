@@ -131,6 +131,99 @@ __device__ __forceinline__ void xstore(double *p, double v) {
   *p = v;
 #endif
 }
+// ---- windowed LD (mxa_ld_band, mxa_ld_scores): the LD map of POST 2 on the tiles of a band, written as band storage (POST 3) or reduced to per-SNP
+// scores (POST 4).  These two instantiations reuse the kernels' arguments instead of widening XPost (the other instantiations keep their code object
+// byte for byte): ans = the band / the partial buffer P, ld = its leading dimension ldb / the row stride of P, c0 = the window, post.do_scale = kind / adjust.
+// The window predicate, in one place: element (i, j), i <= j, of R belongs to the band.  A per-SNP bound (base pairs, centimorgans) replaces `window` here.
+__device__ __forceinline__ bool ld_in_window(long i, long j, long window) { return j - i <= window; }
+// tile diagonals dt = J - I a window touches: tile (I, J) holds the offsets j - i in [256 dt - 255, 256 dt + 255], so it meets the band iff
+// 256 dt - 255 <= window, i.e. dt <= (window + 255) / 256 = ceil(window / 256) -- one more diagonal than window / 256 unless the window ends on a tile edge
+__host__ __device__ __forceinline__ int ld_band_diagonals(long window) { return (int)((window + 255) / 256); }
+// partial buffer of the scores: P[side][dt][row], side 0 = the tile's I rows (sums over gj), side 1 = its J rows (sums over gi; off the diagonal only)
+__host__ __device__ __forceinline__ size_t ld_score_slot(int side, int dt, int ndiag, long stride) { return ((size_t)side * (size_t)(ndiag + 1) + (size_t)dt) * (size_t)stride; }
+constexpr int kXScratchBytes = 4 * 32 * 33 * 8;   // the four waves' 32 x 33 epilogue scratch; the score reduction area lies behind it
+
+template <typename AccT, int POST>
+__device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
+                                                   double *__restrict__ out, long ld, long window, const XPost &post) {
+  double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
+  const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
+  constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
+  auto ldmap = [&](double v, long i, long j) -> double { return ld_scale_map(ld_center_map(v, post.u[i], post.u[j], post.a), post.w[i], post.w[j]); };
+  if constexpr (POST == 3) {
+    // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
+    const bool squared = post.do_scale != 0;
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+        const long gj = gj_base + col;
+        if (gj_base + 31 < gi_base || !ld_in_window(gi_base + 31, gj_base, window)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
+#pragma unroll
+        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = (double)acc[a][b][r] * scale;
+        if (gj < n) {
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int row = (r & 3) + 8 * (r >> 2) + rq;
+            const long gi = gi_base + row;
+            if (gi <= gj && ld_in_window(gi, gj, window)) {
+              const double v = ldmap(scratch[row * 33 + col], gj, gi);
+              xstore(&out[(size_t)(gj - gi) + (size_t)gi * ld], squared ? v * v : v);
+            }
+          }
+        }
+      }
+  } else {
+    // scores: t(r) summed along the rows of the tile (for its I rows) and, off the diagonal, along its columns (for its J rows); every sum in a fixed order:
+    // a lane over its elements, then (hh 0 + hh 1) + (second wave's hh 0 + hh 1) through the LDS; one store per slot, no atomics
+    const bool diag_tile = i0 == j0, adjust = post.do_scale != 0;
+    const double inv_adj = adjust ? 1.0 / (post.a * 0.25 - 2.0) : 0.0;     // post.a = 4 indiv: 1 / (indiv - 2)
+    auto term = [&](double v, long i, long j) -> double {                   // every operation rounded on its own (no contraction): the tests restate this line
+      const double r = ldmap(v, i, j), r2 = __dmul_rn(r, r);
+      return adjust ? __dsub_rn(r2, __dmul_rn(__dsub_rn(1.0, r2), inv_adj)) : r2;
+    };
+    double rowacc[4] = {0.0, 0.0, 0.0, 0.0}, colacc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+        const long gj = gj_base + col, gi = gi_base + col;
+        // wave-uniform: no element of the sub-block is within the window (on the diagonal tile both triangles count: |gj - gi| <= window)
+        if (gj_base >= gi_base ? !ld_in_window(gi_base + 31, gj_base, window) : !ld_in_window(gj_base + 31, gi_base, window)) continue;
+#pragma unroll
+        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = (double)acc[a][b][r] * scale;
+        if (!diag_tile && gj < n) {                            // J side: lane = column gj, its 16 rows gi (gi < gj < n)
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int row = (r & 3) + 8 * (r >> 2) + rq;
+            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += term(scratch[row * 33 + col], gj, gi_base + row);
+          }
+        }
+        if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
+#pragma unroll
+          for (int it = 0; it < 16; it++) {
+            const int cc = 2 * it + hh;
+            const long gjj = gj_base + cc;
+            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += term(scratch[col * 33 + cc], gi, gjj);
+          }
+        }
+      }
+    double *red = reinterpret_cast<double *>(smem + kXScratchBytes);   // red[side][wave][hh][a or b][32]
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      red[(((0 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = rowacc[q];
+      red[(((1 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = colacc[q];
+    }
+    __syncthreads();
+    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = ld_band_diagonals(window);
+    auto slot = [&](int side, int w) { return red[(((side * 4 + w) * 2 + 0) * 4 + q) * 32 + c] + red[(((side * 4 + w) * 2 + 1) * 4 + q) * 32 + c]; };
+    out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
+    if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
+  }
+}
+
 // POST: 0 plain crossproduct, 1 GRM map, 2 LD map (XPost above); each stored element is mapped with ITS OWN (row, column), so both images equal what
 // the unfused element-wise kernels produce.  With a map the 32 x 32 block goes to the LDS scratch first (static accumulator indices) and both images
 // are written by loops over IT, never over the accumulators: when the maps still held fp64 divisions, their 512-fold unrolled code exceeded the
@@ -142,7 +235,9 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
   double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);   // the DMA ring is dead after the last barrier
   const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
   constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
-  if constexpr (POST == 0) {
+  if constexpr (POST >= 3) {   // windowed LD: band storage / scores (ans, ld, c0 = band or partial buffer, its stride, the window)
+    xprod_store_window<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, n, ans, ld, c0, post);
+  } else if constexpr (POST == 0) {
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -631,6 +726,8 @@ static int launch_tiles(const XGeom &g, bool f4, size_t ntiles, hipStream_t s, c
   using I8 = std::true_type;
   if (post_kind == 1) return f4 ? go(F4(), std::integral_constant<int, 1>()) : go(I8(), std::integral_constant<int, 1>());
   if (post_kind == 2) return f4 ? go(F4(), std::integral_constant<int, 2>()) : go(I8(), std::integral_constant<int, 2>());
+  if (post_kind == 3) return f4 ? go(F4(), std::integral_constant<int, 3>()) : go(I8(), std::integral_constant<int, 3>());   // windowed LD: band storage
+  if (post_kind == 4) return f4 ? go(F4(), std::integral_constant<int, 4>()) : go(I8(), std::integral_constant<int, 4>());   // windowed LD: scores
   return f4 ? go(F4(), std::integral_constant<int, 0>()) : go(I8(), std::integral_constant<int, 0>());
 }
 
@@ -653,6 +750,15 @@ static std::vector<int4> row_tiles(int nb, int i0, int i1) {
   std::vector<int4> tiles;
   for (int i = i0; i < i1; i++)
     for (int j = i; j < nb; j++) tiles.push_back(make_int4(i, j, i == j ? 1 : 3, 0));
+  return tiles;
+}
+
+// The tiles of the band of `ndiag` tile diagonals above the main one (ld_band_diagonals), tile row by tile row: (i, j), i <= j <= i + ndiag.  A tile row is
+// compact (ndiag + 1 neighbours that share row block i), which is what gang_order_tiles wants: a gang of 32 tiles is cut from four adjacent tile rows.
+static std::vector<int4> band_tiles(int nb, int ndiag) {
+  std::vector<int4> tiles;
+  for (int i = 0; i < nb; i++)
+    for (int j = i; j < std::min(nb, i + ndiag + 1); j++) tiles.push_back(make_int4(i, j, 1, 0));
   return tiles;
 }
 
@@ -1050,6 +1156,18 @@ static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post
   return 0;
 }
 
+constexpr long kXFusedMaxRows = 29000000L;   // k_x_rowstats: 16 * 3 * (3 rows) must fit 32 bits
+
+// engine: FP4 while the fp32 accumulator is provably exact (sum z z' < 2^24), int8 beyond (MXA_XPROD_ENGINE=i8 forces int8, for A/B runs)
+static int pick_engine(const int *d_has3, long k, hipStream_t s, bool &f4) {
+  int has3 = 1;
+  MXA_HIP(hipMemcpyAsync(&has3, d_has3, sizeof(int), hipMemcpyDeviceToHost, s));
+  MXA_HIP(hipStreamSynchronize(s));
+  f4 = has3 ? 9 * k < (1L << 24) : 4 * k < (1L << 24);
+  if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
+  return 0;
+}
+
 static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, double *ans, bool is_plink, int post = 0, int do_scale = 0,
                          const double *freq = nullptr, long c_begin = 0, long c_end = -1, bool upper_only = false, long ld = -1, int device = -1) {
   if (c_end < 0) c_end = rows;
@@ -1110,17 +1228,13 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   clk.mark("operand buffer allocated");
   if (stage_operand(snp_matrix, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s)) return 1;
   clk.mark("operand staged (upload + k_xstage)");
-  // engine: FP4 while the fp32 accumulator is provably exact (sum z z' < 2^24), int8 beyond (MXA_XPROD_ENGINE=i8 / f4 forces one, for A/B runs)
-  int has3 = 1;
-  MXA_HIP(hipMemcpyAsync(&has3, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  MXA_HIP(hipStreamSynchronize(s));
-  bool f4 = has3 ? 9 * k < (1L << 24) : 4 * k < (1L << 24);
-  if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
+  bool f4 = false;
+  if (pick_engine((const int *)d_flag.p, k, s, f4)) return 1;
 
   // ---- the route, decided once the engine is known: the result on the device (out_dev), or a host result through ONE copy of an n x n device buffer,
   // through the slab pipeline into that buffer, or through the pipeline's ring of column slabs with no such buffer at all.
   // GRM / LD: the element-wise map is fused into the crossproduct epilogue (whole matrix; MXA_XPROD_FUSED_POST=0 keeps the three extra passes over the result).
-  constexpr long kXFusedMaxRows = 29000000L;   // k_x_rowstats: 16 * 3 * (3 rows) must fit 32 bits; beyond that the three-pass post-processing runs
+  // (rows >= kXFusedMaxRows: the three-pass post-processing runs)
   const int post_kind = post && fused_on && whole && rows < kXFusedMaxRows ? post : 0;
   const bool slabs = pipelined && (!post || post_kind);   // unfused post-processing needs the whole matrix on the device: one copy, even where the ring would go
   // the ring where the call is bound by the download anyway -- the ring computes every off-diagonal tile twice.  Estimates: triangular arithmetic at the
@@ -1178,7 +1292,106 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   return 0;
 }
 
+// ---- windowed LD: the band |i - j| <= window of R, as LAPACK lower band storage (scores == 0: out = band, leading dimension ldb, flag = kind) or reduced to
+// the LD scores (scores != 0: out = scores, flag = adjust).  O(snps * window) work and memory: the tiles of band_tiles through the same kernels as mxa_ld.
+// zeros of the band's tail band[d + i * ldb], i + d >= n: window (window + 1) / 2 elements of the last `window` SNPs, not a pass over the band
+__global__ void __launch_bounds__(256) k_ld_band_tail(double *__restrict__ band, long ldb, long n, long window) {
+  const long i = n - 1 - (long)blockIdx.x;                    // blockIdx.x < window < n
+  for (long d = n - i + threadIdx.x; d <= window; d += 256) band[(size_t)d + (size_t)i * ldb] = 0.0;
+}
+// scores[i] = the slots of row i in a fixed order: the I side of the tiles (I, I + dt), then the J side of the tiles (I - dt, I); a slot exists iff its tile does
+__global__ void __launch_bounds__(256) k_ld_score_finish(const double *__restrict__ P, long n, long stride, int nb, int ndiag, double *__restrict__ scores) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int I = (int)(i / kXT);
+  double s = 0.0;
+  for (int dt = 0; dt <= ndiag; dt++) if (I + dt < nb) s += P[ld_score_slot(0, dt, ndiag, stride) + (size_t)i];
+  for (int dt = 1; dt <= ndiag; dt++) if (I - dt >= 0) s += P[ld_score_slot(1, dt, ndiag, stride) + (size_t)i];
+  scores[i] = s;
+}
+
+static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag, bool is_plink,
+                         const double *freq) {
+  if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
+  if (!freq) { set_error(1, "%s: allele frequencies are required", who); return 1; }
+  if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
+  if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
+  if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
+  if (scores && flag && indiv < 3) { set_error(1, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3", who); return 1; }
+  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call (the fused statistics)", who, kXFusedMaxRows - 1); return 1; }
+  if (select_device() < 0) return 1;
+  const XGeom g(indiv, snps);
+  const long row_bytes = (indiv + 3) / 4;
+  const bool in_dev = ptr_location(plink, nullptr) == 1, out_dev = ptr_location(out, nullptr) == 1;
+  const int ndiag = ld_band_diagonals(window);
+  // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
+  const size_t xbytes = (size_t)g.rows_pad() * g.pitch(), obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps),
+               pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
+  size_t free_b = 0, total_b = 0;
+  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t need = xbytes + pbytes + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
+  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
+  XStream st;
+  if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
+  hipStream_t s = st.s;
+  XBuf d_X, bounce, d_out, d_flag, f_tmp, d_P;
+  if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
+  if (stage_operand(plink, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s)) return 1;
+  bool f4 = false;
+  if (pick_engine((const int *)d_flag.p, indiv, s, f4)) return 1;
+  const double *d_f = freq;
+  if (ptr_location(freq, nullptr) != 1) {
+    if (f_tmp.alloc(sizeof(double) * (size_t)snps)) return 1;
+    MXA_HIP(hipMemcpyAsync(f_tmp.p, freq, sizeof(double) * (size_t)snps, hipMemcpyHostToDevice, s));
+    d_f = (const double *)f_tmp.p;
+  }
+  XPost xp;
+  XBuf stats[3];
+  if (fused_post_stats(g, (const uint8_t *)d_X.p, indiv, 2, 0, d_f, stats, s, xp)) return 1;
+  xp.do_scale = flag;                                     // kind / adjust (xprod_store_window)
+  XTiles t;
+  if (upload_tiles({band_tiles(g.nb, ndiag)}, s, t)) return 1;
+  double *d_res = out_dev ? out : (double *)d_out.p;
+  const long ld_res = out_dev ? ldb : window + 1;
+  XEvent e0, e1;
+  if (e0.create() || e1.create()) return 1;
+  MXA_HIP(hipEventRecord(e0.e, s));
+  if (scores) {
+    if (t.launch(0, g, f4, s, (const uint8_t *)d_X.p, (double *)d_P.p, g.rows_pad(), window, nullptr, 4, xp)) return 1;
+    hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
+  } else {
+    if (t.launch(0, g, f4, s, (const uint8_t *)d_X.p, d_res, ld_res, window, nullptr, 3, xp)) return 1;
+    if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
+  }
+  MXA_HIP(hipGetLastError());
+  MXA_HIP(hipEventRecord(e1.e, s));
+  if (!out_dev) {
+    if (scores || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
+    else {   // a wider host ldb: one download, then the rows d <= window of every column (the rows beyond stay the caller's)
+      std::vector<double> h((size_t)(window + 1) * (size_t)snps);
+      MXA_HIP(hipMemcpyAsync(h.data(), d_res, obytes, hipMemcpyDeviceToHost, s));
+      MXA_HIP(hipStreamSynchronize(s));
+      for (long i = 0; i < snps; i++) memcpy(out + (size_t)i * ldb, h.data() + (size_t)i * (window + 1), sizeof(double) * (size_t)(window + 1));
+    }
+  }
+  MXA_HIP(hipStreamSynchronize(s));   // tile list / statistics lifetime
+  MXA_HIP(profile_launch(e0, e1));
+  return 0;
+}
+
 }  // namespace mxa
+
+extern "C" int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind, int is_plink_format,
+                           const double *allele_freq) {
+  mxa::clear_error();
+  return mxa::ld_window_any("mxa_ld_band", plink, snps, indiv, window, band, ldb, false, kind, is_plink_format != 0, allele_freq);
+}
+
+extern "C" int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust, int is_plink_format,
+                             const double *allele_freq) {
+  mxa::clear_error();
+  return mxa::ld_window_any("mxa_ld_scores", plink, snps, indiv, window, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
+}
 
 extern "C" int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, double *ans, bool is_plink_format) {
   // positional meaning as in the reference: arg 2 = packed (inner) dimension, arg 3 = output dimension

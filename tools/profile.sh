@@ -13,6 +13,7 @@
 #                        int8 kernels of a CG step, the whole step, and their data movement alone
 #   gram                 CG step (config-5 shard): step time + kernel timeline of three steps
 #   xprod [snps indiv]   crossproduct kernel time at config 3, both engines
+#   ld-band [snps indiv window]   windowed LD (mxa_ld_band / mxa_ld_scores): kernel time, tiles, bytes written, both engines; band vs full mxa_ld (A/B)
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -97,6 +98,14 @@ xprod)
     if [ $e = i8 ]; then export MXA_XPROD_ENGINE=i8; else unset MXA_XPROD_ENGINE; fi
     timeout -k 10 500 python3 tools/perf_crossprod.py ${1:-500000} ${2:-100000} 2 2>&1 | tee -a "$O/xprod.txt" || exit 1
   done ;;
+ld-band)
+  # band + scores at config 2's shape, both engines; then band against the full mxa_ld where the full result exists (100 000 SNPs: 80 GB), A/B alternating
+  for e in f4 i8; do
+    if [ $e = i8 ]; then export MXA_XPROD_ENGINE=i8; else unset MXA_XPROD_ENGINE; fi
+    timeout -k 10 400 python3 tools/perf_ld_band.py ${1:-1000000} ${2:-50000} ${3:-1023} 5 2>&1 | tee -a "$O/ld_band.txt" || exit 1
+  done
+  unset MXA_XPROD_ENGINE
+  timeout -k 10 400 python3 tools/perf_ld_band.py 100000 ${2:-50000} ${3:-1023} 5 --vs-full 2>&1 | tee -a "$O/ld_band.txt" || exit 1 ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

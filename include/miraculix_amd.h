@@ -317,6 +317,34 @@ int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, dou
 int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust, int is_plink_format,
                   const double *allele_freq);
 
+/* Windowed LD on data WITH missing genotypes: the pairwise-complete correlation (what PLINK's --r / --r2 report).  mxa_ld_band / mxa_ld_scores stage the
+ * matrix with the reference's byte table, under which a byte that holds a missing pair (01) becomes four 3s: their results on such data are not correlations.
+ * Here, for SNP rows i, j of the PLINK matrix, with m = 1 where the genotype is present (0 for the missing code 01), z = the allele count with missing as 0
+ * and a = 1 where the code is 11 (so z^2 = z + 2 a), all sums over the `indiv` individuals of a row:
+ *     N   = sum m_i m_j           Sxy = sum z_i z_j           Sx = sum z_i m_j           Sy = sum m_i z_j
+ *     Sxx = Sx + 2 sum a_i m_j    Syy = Sy + 2 sum m_i a_j
+ *     num = N Sxy - Sx Sy         dx  = N Sxx - Sx^2          dy = N Syy - Sy^2          r = num / sqrt(dx * dy)
+ * i.e. Pearson's r over the individuals genotyped at BOTH SNPs.  The six sums are exact integer tile products (the crossproduct engines); num, dx, dy are
+ * formed exactly (integers below 4 indiv^2 < 2^53); then ONE product dx * dy, ONE square root and ONE quotient, each correctly rounded, in that order.
+ * A pair with dx * dy = 0 -- no individual genotyped at both SNPs, or a SNP constant on the shared ones -- gives 0 / 0 = NaN: no special case (as a
+ * monomorphic SNP in mxa_ld).  r is symmetric in (i, j) bit for bit.
+ * plink: snps rows of ceil(indiv / 4) bytes in PLINK coding (00 -> 0, 01 -> missing, 10 -> 1, 11 -> 2; there is no raw 2-bit form: only PLINK coding has a
+ * missing code), host or device.  The padding bits of a row's last byte (fields at and beyond indiv) are NOT individuals, whatever they hold.  No
+ * allele_freq: every statistic comes from the data.
+ * mxa_ld_band_pairwise  : band layout, window, ldb, kind (0: r, 1: r * r, one rounding), zeros in the tail, rows beyond window of a wider ldb untouched:
+ *                         exactly as mxa_ld_band.
+ * mxa_ld_scores_pairwise: scores[i] = sum over j, |i-j| <= window (j = i included), of t(r_ij); adjust 0: t = r^2; 1: t = r^2 - (1 - r^2) / (N_ij - 2) with the
+ *                         pair's own N_ij, formed as r2 - ((1 - r2) / (N - 2)) with every operation rounded on its own.  Fixed summation order, no atomics.
+ *                         The r inside a term is bit for bit the r mxa_ld_band_pairwise returns for that pair.
+ * Results are identical from run to run, between the FP4 and the int8 engine (MXA_XPROD_ENGINE=i8), between host and device pointers, and for every size of
+ * the count scratch: the band runs in groups of tile rows whose six int32 count tiles per 256 x 256 band tile stay under MXA_LD_PAIRWISE_SCRATCH_MB (default
+ * 2048; one tile row at least).  A matrix without any missing code needs the sum z_i z_j product only (N = indiv, the rest are per-SNP sums): same bits,
+ * about the cost of mxa_ld_band; MXA_LD_PAIRWISE_DENSE=1 forces the six products.  Device memory: three 2-bit planes of the matrix (3 x mxa_ld_band's).
+ * Errors (return 1, mxa_last_error() == 1, output untouched): window out of range, ldb < window + 1, kind / adjust not 0 or 1, adjust with indiv < 3,
+ * indiv > 47 453 132 (4 indiv^2 >= 2^53), snps >= 29 000 000; 12: not enough device memory.  Runs on the selected device (no MIRACULIX_NUM_GPUS sharding). */
+int mxa_ld_band_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind);
+int mxa_ld_scores_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -15,6 +15,7 @@ module modmiraculix_amd
  public :: mxa_single_orientation, mxa_num_shards, mxa_allele_freq, mxa_transpose_2bit
  public :: mxa_plink2compressed_begin, mxa_plink2compressed_rows, mxa_plink2compressed_end
  public :: mxa_ld_band, mxa_ld_scores
+ public :: mxa_ld_band_pairwise, mxa_ld_scores_pairwise
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -141,6 +142,22 @@ module modmiraculix_amd
    import c_int, c_ptr
    type(c_ptr), value, intent(in) :: plink, scores, allele_freq
    integer(c_int), value, intent(in) :: snps, indiv, window, adjust, is_plink_format
+   integer(c_int) :: rc
+  end function
+
+  ! the same two on data with missing genotypes (PLINK code 01): the pairwise-complete r, Pearson's r over the individuals genotyped at both SNPs.
+  ! PLINK coding only, no allele frequencies; band / scores laid out as above; adjust = 1 uses the pair's own count N_ij in r^2 - (1 - r^2) / (N_ij - 2)
+  function mxa_ld_band_pairwise(plink, snps, indiv, window, band, ldb, kind) bind(C, name='mxa_ld_band_pairwise') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, band
+   integer(c_int), value, intent(in) :: snps, indiv, window, kind
+   integer(c_long), value, intent(in) :: ldb
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_scores_pairwise(plink, snps, indiv, window, scores, adjust) bind(C, name='mxa_ld_scores_pairwise') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, scores
+   integer(c_int), value, intent(in) :: snps, indiv, window, adjust
    integer(c_int) :: rc
   end function
 

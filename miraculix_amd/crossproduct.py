@@ -146,3 +146,79 @@ def ld_scores(plink, snps, indiv, window, adjust=False, is_plink_format=False, a
     if rc != 0:
         raise RuntimeError("mxa_ld_scores failed: " + _lib.last_error()[1])
     return S
+
+
+# ---- pairwise-complete windowed LD (data with missing genotypes): C entries mxa_ld_band_pairwise / mxa_ld_scores_pairwise
+PAIRWISE_PLANES = {"Z": 0, "M": 1, "A": 2}                    # planes of the stacked operand: allele count (missing as 0), present, code 11
+# the six products of a band tile in slot order: N, Sxy, Sx, Sy, sum a_i m_j, sum m_i a_j -- (plane of the I rows, plane of the J rows)
+PAIRWISE_PAIRS = (("M", "M"), ("Z", "Z"), ("Z", "M"), ("M", "Z"), ("A", "M"), ("M", "A"))
+PAIRWISE_SLOT_BYTES = 256 * 256 * 4                           # one int32 count tile
+
+
+def ld_pairwise_group_rows(snps, window, scratch_mb=2048, pairs=6):
+    """Tile rows per group of the pairwise entries: as many as keep the count scratch (pairs slots of 256 KiB per band tile, a tile row holding up to
+    min(nb, ceil(window / 256) + 1) tiles) under scratch_mb MiB -- one tile row at least, the whole band at most."""
+    nb = (snps + 255) // 256
+    row_tiles = min(nb, (window + 255) // 256 + 1)
+    return max(1, min(nb, (scratch_mb << 20) // (row_tiles * pairs * PAIRWISE_SLOT_BYTES)))
+
+
+def ld_pairwise_tiles(snps, window, group):
+    """The tile plan of the pairwise entries, restated: the band tiles of ld_band_tiles in groups of `group` tile rows; per band tile (I, J) six entries
+    (x, y, slot) over the stacked operand of 3 nb row blocks, x = plane_a * nb + I, y = plane_b * nb + J for the pairs of PAIRWISE_PAIRS, written to the
+    scratch slots 6 q .. 6 q + 5 of the tile's position q within its group.  Returns the list of groups."""
+    nb = (snps + 255) // 256
+    ndiag = (window + 255) // 256
+    groups = []
+    for i_lo in range(0, nb, group):
+        entries, q = [], 0
+        for i in range(i_lo, min(nb, i_lo + group)):
+            for j in range(i, min(nb, i + ndiag + 1)):
+                for k, (pa, pb) in enumerate(PAIRWISE_PAIRS):
+                    entries.append((PAIRWISE_PLANES[pa] * nb + i, PAIRWISE_PLANES[pb] * nb + j, 6 * q + k))
+                q += 1
+        groups.append(entries)
+    return groups
+
+
+def _ld_pairwise_args(plink, snps, indiv, window):
+    if int(np.prod(plink.shape)) != snps * ((indiv + 3) // 4):
+        raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
+    if not 0 <= int(window) < snps:
+        raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+
+
+def ld_band_pairwise(plink, snps, indiv, window, kind="r"):
+    """Additive (C entry mxa_ld_band_pairwise): ld_band() for PLINK data with missing genotypes -- the pairwise-complete r, Pearson's correlation over the
+    individuals genotyped at both SNPs (NaN where there is none, or a SNP is constant on them).  Shape (snps, window + 1), out[i, d] = r(i, i + d)."""
+    if kind not in ("r", "r2"):
+        raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+    _ld_pairwise_args(plink, snps, indiv, window)
+    L = _lib.check_library_handle()
+    if _lib.is_torch_tensor(plink):
+        import torch
+        B = torch.zeros((snps, int(window) + 1), dtype=torch.float64, device=plink.device)
+    else:
+        B = np.zeros((snps, int(window) + 1), dtype=np.float64)
+    rc = L.mxa_ld_band_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0)
+    if rc != 0:
+        raise RuntimeError("mxa_ld_band_pairwise failed: " + _lib.last_error()[1])
+    return B
+
+
+def ld_scores_pairwise(plink, snps, indiv, window, adjust=False):
+    """Additive (C entry mxa_ld_scores_pairwise): ld_scores() from the pairwise-complete r; adjust: r^2 - (1 - r^2) / (N_ij - 2) with the pair's own count of
+    shared individuals.  Shape (snps,); fixed summation order (bitwise reproducible)."""
+    _ld_pairwise_args(plink, snps, indiv, window)
+    if adjust and indiv < 3:
+        raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
+    L = _lib.check_library_handle()
+    if _lib.is_torch_tensor(plink):
+        import torch
+        S = torch.zeros(snps, dtype=torch.float64, device=plink.device)
+    else:
+        S = np.zeros(snps, dtype=np.float64)
+    rc = L.mxa_ld_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust)))
+    if rc != 0:
+        raise RuntimeError("mxa_ld_scores_pairwise failed: " + _lib.last_error()[1])
+    return S

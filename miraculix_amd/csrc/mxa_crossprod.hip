@@ -71,6 +71,39 @@ __global__ void __launch_bounds__(256) k_xstage(const uint8_t *__restrict__ src,
   }
 }
 
+// Pairwise-complete LD (mxa_ld_band_pairwise, mxa_ld_scores_pairwise): the PLINK codes of a row as THREE planes in the tiled layout, stacked as one operand
+// of 3 * rows_pad rows (plane p starts plane_bytes * p behind dst, so tile index p * nb + I addresses block I of plane p):
+//   plane 0  Z: 00 -> 0, 01 -> 0, 10 -> 1, 11 -> 2   (allele count, missing as 0)
+//   plane 1  M: 01 -> 0, else 1                        (genotype present)
+//   plane 2  A: 11 -> 1, else 0                        (z^2 = z + 2 a)
+// Fields at and beyond `indiv` -- the padding bits of a row's last byte, which read as 00 in a well-formed file -- are no individuals: they get 0 in every
+// plane, M included (else every N_ij would count them).  *has_missing |= 1 when a 01 occurs among the individuals: one atomic per wave, not per dword.
+__global__ void __launch_bounds__(256) k_xstage_planes(const uint8_t *__restrict__ src, size_t src_pitch, long row_bytes, long nrows, long indiv,
+                                                       uint8_t *__restrict__ dst, long nslabs, size_t plane_bytes, long dst_row0, int *__restrict__ has_missing) {
+  const long dpr = (row_bytes + 3) / 4;
+  const long total = nrows * dpr;
+  uint32_t seen = 0;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const long r = idx / dpr, d = idx - r * dpr, b = d * 4;
+    const uint8_t *p = src + (size_t)r * src_pitch + b;
+    uint32_t w = 0;
+    if (b + 4 <= row_bytes && (reinterpret_cast<size_t>(p) & 3) == 0) w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
+    else
+      for (int u = 0; u < 4; u++)
+        if (b + u < row_bytes) w |= (uint32_t)p[u] << (8 * u);
+    const long left = indiv - 4 * b;                                            // individuals from this dword's first field on (> 0: b < row_bytes)
+    const uint32_t vm = left >= 16 ? 0x55555555u : ((1u << (2 * left)) - 1u) & 0x55555555u;
+    const uint32_t H = (w >> 1) & vm, L = w & vm, miss = L & ~H;
+    seen |= miss;
+    const long R = dst_row0 + r;
+    uint8_t *q = dst + ((size_t)(R / kTileRows) * nslabs + (size_t)(b / kSlabBytes)) * kTileBytes + (size_t)(R % kTileRows) * kSlabBytes + b % kSlabBytes;
+    *reinterpret_cast<uint32_t *>(q) = ((H & L) << 1) | (H & ~L);
+    *reinterpret_cast<uint32_t *>(q + plane_bytes) = vm & ~miss;
+    *reinterpret_cast<uint32_t *>(q + 2 * plane_bytes) = H & L;
+  }
+  if (__any(seen != 0) && (threadIdx.x & 63) == 0) atomicOr(has_missing, 1);
+}
+
 // ---- main kernel -----------------------------------------------------------------------------------------------
 constexpr int kXT = 256;              // tile edge (rows of X per operand block)
 constexpr int kXStageK = 128;         // genotypes per LDS stage = 32 packed bytes per row
@@ -222,6 +255,103 @@ __device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char
     out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
     if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
   }
+}
+
+// The same store for the combine kernel of the pairwise-complete entries (k_ld_pw_combine), where an element's value does not come from an accumulator and needs
+// no map: prep(a, b) readies the lane's sub-block (a, b), val(a, b, r) is the finished value (POST 3: r, POST 4: t(r)) of the element that accumulator register r
+// of that sub-block holds in the crossproduct kernels.  Band layout, window tests, summation order and the slots of P are those of xprod_store_window line by
+// line (a copy and not a shared template: the epilogue above sits in kernels with 256 accumulator registers, whose register allocation changes with any
+// restructuring of it).  squared: POST 3 stores v * v.
+template <int POST, typename Prep, typename Val>
+__device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
+                                                double *__restrict__ out, long ld, long window) {
+  double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
+  const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
+  if constexpr (POST == 3) {
+    // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+        const long gj = gj_base + col;
+        if (gj_base + 31 < gi_base || !ld_in_window(gi_base + 31, gj_base, window)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
+        prep(a, b);
+#pragma unroll
+        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
+        if (gj < n) {
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int row = (r & 3) + 8 * (r >> 2) + rq;
+            const long gi = gi_base + row;
+            if (gi <= gj && ld_in_window(gi, gj, window)) {
+              const double v = scratch[row * 33 + col];
+              xstore(&out[(size_t)(gj - gi) + (size_t)gi * ld], squared ? v * v : v);
+            }
+          }
+        }
+      }
+  } else {
+    // scores: t(r) summed along the rows of the tile (for its I rows) and, off the diagonal, along its columns (for its J rows); every sum in a fixed order:
+    // a lane over its elements, then (hh 0 + hh 1) + (second wave's hh 0 + hh 1) through the LDS; one store per slot, no atomics
+    const bool diag_tile = i0 == j0;
+    double rowacc[4] = {0.0, 0.0, 0.0, 0.0}, colacc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+        const long gj = gj_base + col, gi = gi_base + col;
+        // wave-uniform: no element of the sub-block is within the window (on the diagonal tile both triangles count: |gj - gi| <= window)
+        if (gj_base >= gi_base ? !ld_in_window(gi_base + 31, gj_base, window) : !ld_in_window(gj_base + 31, gi_base, window)) continue;
+        prep(a, b);
+#pragma unroll
+        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
+        if (!diag_tile && gj < n) {                            // J side: lane = column gj, its 16 rows gi (gi < gj < n)
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int row = (r & 3) + 8 * (r >> 2) + rq;
+            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += scratch[row * 33 + col];
+          }
+        }
+        if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
+#pragma unroll
+          for (int it = 0; it < 16; it++) {
+            const int cc = 2 * it + hh;
+            const long gjj = gj_base + cc;
+            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += scratch[col * 33 + cc];
+          }
+        }
+      }
+    double *red = reinterpret_cast<double *>(smem + kXScratchBytes);   // red[side][wave][hh][a or b][32]
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      red[(((0 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = rowacc[q];
+      red[(((1 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = colacc[q];
+    }
+    __syncthreads();
+    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = ld_band_diagonals(window);
+    auto slot = [&](int side, int w) { return red[(((side * 4 + w) * 2 + 0) * 4 + q) * 32 + c] + red[(((side * 4 + w) * 2 + 1) * 4 + q) * 32 + c]; };
+    out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
+    if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
+  }
+}
+
+// Count store (POST 5, pairwise-complete LD): the raw accumulators of the tile as int32 (FP4 engine: acc x 4, exact) into the scratch slot the tile entry
+// names (its fourth field), 65 536 ints.  Lane-linear and register-major in quads: registers 4 q .. 4 q + 3 of thread t at slot + q * 1024 + 4 t, one 16-byte
+// store per lane and quad (a wave writes 1 KiB contiguous); no LDS transpose.  The combine kernel reads the same addresses with the same lane <-> element map.
+constexpr size_t kPwSlotInts = (size_t)kXT * kXT;
+template <typename AccT>
+__device__ __forceinline__ void xprod_store_counts(const AccT (&acc)[4][4], int *__restrict__ scratch, int slot) {
+  int4 *p = reinterpret_cast<int4 *>(scratch + (size_t)slot * kPwSlotInts) + threadIdx.x;
+  auto cnt = [](auto v) -> int { if constexpr (__is_same(AccT, v16f)) return (int)(v * 4.0f); else return v; };
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        p[((a * 4 + b) * 4 + q) * 256] = make_int4(cnt(acc[a][b][4 * q]), cnt(acc[a][b][4 * q + 1]), cnt(acc[a][b][4 * q + 2]), cnt(acc[a][b][4 * q + 3]));
 }
 
 // POST: 0 plain crossproduct, 1 GRM map, 2 LD map (XPost above); each stored element is mapped with ITS OWN (row, column), so both images equal what
@@ -487,7 +617,8 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0 && diag) { diag[2 * tile_index] = t1 - t0; diag[2 * tile_index + 1] = r1 - r0; }
   }
-  xprod_store<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, t.z, n, ans, ld, c0, post);
+  if constexpr (POST == 5) xprod_store_counts<AccT>(acc, reinterpret_cast<int *>(ans), t.w);   // ans = the count scratch, t.w = the tile's slot
+  else xprod_store<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, t.z, n, ans, ld, c0, post);
 }
 
 template <bool DIAG, int EXP = 0, int POST = 0>
@@ -561,7 +692,8 @@ k_crossprod_gang(const uint8_t *__restrict__ X, long nslabs, int stages, const i
     const int slot = __builtin_amdgcn_readfirstlane(sh_val), list = __builtin_amdgcn_readfirstlane(sh_list);
     if (slot < 0) break;                               // wave-uniform: every list is empty, the whole workgroup leaves
     const int4 tv = tiles[(size_t)8 * slot + list];
-    const int4 t = make_int4(__builtin_amdgcn_readfirstlane(tv.x), __builtin_amdgcn_readfirstlane(tv.y), __builtin_amdgcn_readfirstlane(tv.z), 0);   // scalar: the DMA bases live in SGPRs
+    const int4 t = make_int4(__builtin_amdgcn_readfirstlane(tv.x), __builtin_amdgcn_readfirstlane(tv.y), __builtin_amdgcn_readfirstlane(tv.z),
+                              __builtin_amdgcn_readfirstlane(tv.w));   // scalar: the DMA bases live in SGPRs (w: the scratch slot of a count store)
     // second meeting point (mid != nullptr): the members of a gang of the own list meet again half way through the tile
     GangMid gm{nullptr, 0, 0, 1, 0};
     if (mid && __builtin_amdgcn_readfirstlane(sh_own)) {
@@ -728,6 +860,7 @@ static int launch_tiles(const XGeom &g, bool f4, size_t ntiles, hipStream_t s, c
   if (post_kind == 2) return f4 ? go(F4(), std::integral_constant<int, 2>()) : go(I8(), std::integral_constant<int, 2>());
   if (post_kind == 3) return f4 ? go(F4(), std::integral_constant<int, 3>()) : go(I8(), std::integral_constant<int, 3>());   // windowed LD: band storage
   if (post_kind == 4) return f4 ? go(F4(), std::integral_constant<int, 4>()) : go(I8(), std::integral_constant<int, 4>());   // windowed LD: scores
+  if (post_kind == 5) return f4 ? go(F4(), std::integral_constant<int, 5>()) : go(I8(), std::integral_constant<int, 5>());   // pairwise LD: count store
   return f4 ? go(F4(), std::integral_constant<int, 0>()) : go(I8(), std::integral_constant<int, 0>());
 }
 
@@ -1100,15 +1233,21 @@ static int postprocess_device(double *d_M, long rows, long k, int post, int do_s
 
 // X (rows of row_bytes packed bytes, in device or host memory) -> d_X, zeroed first, in the tiled layout (k_xstage; is_plink: the reference's table);
 // *d_has3 = 1 when a staged field holds the value 3.  Host rows go through `bounce` (<= 256 MiB: kept by the caller, the pre-flight counts it).
+// planes_indiv > 0: the three planes Z, M, A of the pairwise-complete LD instead (k_xstage_planes; d_X holds 3 * rows_pad rows, *d_has3 = a missing code occurs).
 static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, bool is_plink, const XGeom &g, uint8_t *d_X, int *d_has3, XBuf &bounce,
-                         hipStream_t s) {
+                         hipStream_t s, long planes_indiv = 0) {
   const long rows = g.rows;
-  MXA_HIP(hipMemsetAsync(d_X, 0, (size_t)g.rows_pad() * g.pitch(), s));
+  const size_t plane_bytes = (size_t)g.rows_pad() * g.pitch();
+  MXA_HIP(hipMemsetAsync(d_X, 0, plane_bytes * (planes_indiv > 0 ? 3 : 1), s));
   MXA_HIP(hipMemsetAsync(d_has3, 0, sizeof(int), s));
+  // rows [r0, r0 + nr) of src (pitch row_bytes) into the staged operand
+  auto stage = [&](const uint8_t *src, long r0, long nr) {
+    const dim3 grid((unsigned)std::min<long>((nr * ((row_bytes + 3) / 4) + 255) / 256, 8192));
+    if (planes_indiv > 0) hipLaunchKernelGGL(k_xstage_planes, grid, dim3(256), 0, s, src, (size_t)row_bytes, row_bytes, nr, planes_indiv, d_X, g.nslabs, plane_bytes, r0, d_has3);
+    else hipLaunchKernelGGL(k_xstage, grid, dim3(256), 0, s, src, (size_t)row_bytes, row_bytes, nr, d_X, g.nslabs, r0, is_plink ? 1 : 0, d_has3);
+  };
   if (in_dev) {
-    const long total = rows * ((row_bytes + 3) / 4);
-    hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, snp_matrix, (size_t)row_bytes, row_bytes, rows, d_X, g.nslabs, 0L,
-                       is_plink ? 1 : 0, d_has3);
+    stage(snp_matrix, 0L, rows);
     MXA_HIP(hipGetLastError());
     return 0;
   }
@@ -1118,9 +1257,7 @@ static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_
   for (long r0 = 0; r0 < rows; r0 += chunk_rows) {
     const long nr = std::min(chunk_rows, rows - r0);
     MXA_HIP(hipMemcpyAsync(bounce.p, snp_matrix + (size_t)r0 * row_bytes, (size_t)nr * row_bytes, hipMemcpyHostToDevice, s));
-    const long total = nr * ((row_bytes + 3) / 4);
-    hipLaunchKernelGGL(k_xstage, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, s, (const uint8_t *)bounce.p, (size_t)row_bytes, row_bytes, nr, d_X,
-                       g.nslabs, r0, is_plink ? 1 : 0, d_has3);
+    stage((const uint8_t *)bounce.p, r0, nr);
     MXA_HIP(hipGetLastError());
     MXA_HIP(hipStreamSynchronize(s));
   }
@@ -1310,6 +1447,18 @@ __global__ void __launch_bounds__(256) k_ld_score_finish(const double *__restric
   scores[i] = s;
 }
 
+// a host result of the windowed entries: the scores, or the compact device band (leading dimension window + 1) into the caller's band of leading dimension ldb
+static int ld_window_download(const double *d_res, size_t obytes, long snps, long window, double *out, long ldb, bool scores, hipStream_t s) {
+  if (scores || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
+  else {   // a wider host ldb: one download, then the rows d <= window of every column (the rows beyond stay the caller's)
+    std::vector<double> h((size_t)(window + 1) * (size_t)snps);
+    MXA_HIP(hipMemcpyAsync(h.data(), d_res, obytes, hipMemcpyDeviceToHost, s));
+    MXA_HIP(hipStreamSynchronize(s));
+    for (long i = 0; i < snps; i++) memcpy(out + (size_t)i * ldb, h.data() + (size_t)i * (window + 1), sizeof(double) * (size_t)(window + 1));
+  }
+  return 0;
+}
+
 static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag, bool is_plink,
                          const double *freq) {
   if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
@@ -1365,21 +1514,220 @@ static int ld_window_any(const char *who, const unsigned char *plink, long snps,
   }
   MXA_HIP(hipGetLastError());
   MXA_HIP(hipEventRecord(e1.e, s));
-  if (!out_dev) {
-    if (scores || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
-    else {   // a wider host ldb: one download, then the rows d <= window of every column (the rows beyond stay the caller's)
-      std::vector<double> h((size_t)(window + 1) * (size_t)snps);
-      MXA_HIP(hipMemcpyAsync(h.data(), d_res, obytes, hipMemcpyDeviceToHost, s));
-      MXA_HIP(hipStreamSynchronize(s));
-      for (long i = 0; i < snps; i++) memcpy(out + (size_t)i * ldb, h.data() + (size_t)i * (window + 1), sizeof(double) * (size_t)(window + 1));
-    }
-  }
+  if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
   MXA_HIP(hipStreamSynchronize(s));   // tile list / statistics lifetime
   MXA_HIP(profile_launch(e0, e1));
   return 0;
 }
 
+// ---- pairwise-complete windowed LD (mxa_ld_band_pairwise, mxa_ld_scores_pairwise): Pearson's r of SNPs i, j over the individuals genotyped at BOTH.
+// With the planes Z, M, A of k_xstage_planes every ingredient is an exact integer crossproduct of rows:
+//   N = M_i.M_j   Sxy = Z_i.Z_j   Sx = Z_i.M_j   Sy = M_i.Z_j   Sxx = Sx + 2 A_i.M_j   Syy = Sy + 2 M_i.A_j
+//   num = N Sxy - Sx Sy   dx = N Sxx - Sx^2   dy = N Syy - Sy^2   r = num / sqrt(dx dy)
+// Six tile products per band tile (count store into a scratch slot each), then k_ld_pw_combine forms r per element and stores the band / reduces the scores
+// exactly as the epilogue of mxa_ld_band / mxa_ld_scores does (ld_window_store).  The band runs in groups of tile rows so that the scratch stays bounded.
+// num, dx, dy are formed in fp64 from the int32 counts: every product and difference is an integer below 4 indiv^2 < 2^53 (guarded by the caller), i.e. exact
+// whether or not the compiler contracts them; dx dy, the square root and the quotient are rounded once each.  The expression is symmetric in (i, j) bit for bit.
+constexpr long kPwMaxIndiv = 47453132L;   // 4 indiv^2 < 2^53
+constexpr int kPwPairs = 6;
+// the operand planes (A side from the I rows, B side from the J rows) of the six products, in slot order: N, Sxy, Sx, Sy, A_i.M_j, M_i.A_j
+__host__ __device__ constexpr int pw_plane_a(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? 0 : k == 3 ? 1 : k == 4 ? 2 : 1; }
+__host__ __device__ constexpr int pw_plane_b(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? 1 : k == 3 ? 0 : k == 4 ? 1 : 2; }
+
+__device__ __forceinline__ double pw_r(double N, double Sxy, double Sx, double Sy, double Ax, double Ay) {
+  const double Sxx = Sx + 2.0 * Ax, Syy = Sy + 2.0 * Ay;
+  const double num = N * Sxy - Sx * Sy, dx = N * Sxx - Sx * Sx, dy = N * Syy - Sy * Sy;   // exact integers
+  return __ddiv_rn(num, __dsqrt_rn(__dmul_rn(dx, dy)));                                    // dx dy = 0 (no shared individuals, or a SNP constant on them): 0 / 0 = NaN
+}
+// POST 3: the band entry r (ld_window_store squares it for kind 1); POST 4: the score term t(r) with the pair's own N, every operation rounded on its own
+template <int POST>
+__device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, double Sy, double Ax, double Ay, bool adjust) {
+  const double r = pw_r(N, Sxy, Sx, Sy, Ax, Ay);
+  if constexpr (POST == 3) return r;
+  const double r2 = __dmul_rn(r, r);
+  return adjust ? __dsub_rn(r2, __ddiv_rn(__dsub_rn(1.0, r2), __dsub_rn(N, 2.0))) : r2;
+}
+
+// One workgroup per band tile, the lane <-> element map of the crossproduct epilogue: thread t reads quad q of its sub-block (a, b) at slot + ((4 a + b) 4 + q) 1024 + 4 t,
+// where xprod_store_counts wrote it.  DENSE: the six counts of the tile's slots t.w .. t.w + 5.  !DENSE (no missing code in the whole matrix): slot t.w holds
+// Sxy only; M is all ones, so N = indiv and the other four are the per-SNP sums sz = sum z, sa = sum a (k_pw_rowsums) -- the same integers, hence the same bits.
+template <int POST, bool DENSE>
+__global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ scratch, const int4 *__restrict__ btiles, const int *__restrict__ sz, const int *__restrict__ sa,
+                                                       long n, double indiv, double *__restrict__ out, long ld, long window, int flag) {
+  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (POST == 4 ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
+  const int4 t = btiles[blockIdx.x];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
+  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
+  const int4 *base = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + threadIdx.x;
+  constexpr size_t kSlotQuads = kPwSlotInts / 4;
+  const int col = lane & 31, rq = 4 * (lane >> 5);
+  const bool adjust = flag != 0;
+  int cnt[DENSE ? kPwPairs : 1][16];                         // the counts of the current sub-block, in accumulator register order
+  long gi_base = 0, gj = 0;
+  auto prep = [&](int a, int b) {
+    gi_base = i0 + wi * 128 + a * 32; gj = j0 + wj * 128 + b * 32 + col;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int4 *p = base + ((a * 4 + b) * 4 + q) * 256;
+#pragma unroll
+      for (int k = 0; k < (DENSE ? kPwPairs : 1); k++) {
+        const int4 w = p[(size_t)k * kSlotQuads];
+        cnt[k][4 * q] = w.x; cnt[k][4 * q + 1] = w.y; cnt[k][4 * q + 2] = w.z; cnt[k][4 * q + 3] = w.w;
+      }
+    }
+  };
+  auto val = [&](int, int, int r) -> double {
+    if constexpr (DENSE) return pw_value<POST>((double)cnt[0][r], (double)cnt[1][r], (double)cnt[2][r], (double)cnt[3][r], (double)cnt[4][r], (double)cnt[5][r], adjust);
+    else {
+      const long gi = gi_base + (r & 3) + 8 * (r >> 2) + rq;     // row of accumulator register r
+      return pw_value<POST>(indiv, (double)cnt[0][r], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj], adjust);
+    }
+  };
+  ld_window_store<POST>(prep, val, POST == 3 && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld, window);
+}
+
+// per SNP row: sz = sum z (plane Z), sa = sum a (plane A) of the stacked operand, for the missing-free path.  Grid (row tiles, K chunks), thread = row of the tile
+// reading its 32-byte piece of every slab of the chunk (as k_x_rowstats); int32 atomics across the chunks (integer addition: order-independent).
+__global__ void __launch_bounds__(256) k_pw_rowsums(const uint8_t *__restrict__ X, long nslabs, long slabs_per_chunk, long nb, int *__restrict__ sz, int *__restrict__ sa) {
+  const long rt = blockIdx.x;
+  const long s0 = (long)blockIdx.y * slabs_per_chunk, s1 = min(nslabs, s0 + slabs_per_chunk);
+  int z = 0, a = 0;
+  for (long sl = s0; sl < s1; sl++) {
+    const uint4 *pz = reinterpret_cast<const uint4 *>(X + ((size_t)rt * nslabs + (size_t)sl) * kTileBytes + (size_t)threadIdx.x * kSlabBytes);
+    const uint4 *pa = reinterpret_cast<const uint4 *>(X + ((size_t)(2 * nb + rt) * nslabs + (size_t)sl) * kTileBytes + (size_t)threadIdx.x * kSlabBytes);
+    const uint4 z0 = pz[0], z1 = pz[1], a0 = pa[0], a1 = pa[1];
+    const uint32_t wz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w}, wa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+      z += __popc(wz[d] & 0x55555555u) + 2 * __popc(wz[d] & 0xAAAAAAAAu);
+      a += __popc(wa[d]);
+    }
+  }
+  const long r = rt * kTileRows + threadIdx.x;
+  if (z) atomicAdd(sz + r, z);
+  if (a) atomicAdd(sa + r, a);
+}
+
+// The plan of one group of band tile rows [i_lo, i_hi): per band tile (i, j) one entry of `band` (i, j, 1, first slot) and `pairs` entries of `prod` over the
+// stacked operand (plane_a nb + i, plane_b nb + j, 1, slot); slots are numbered from 0 within the group.  (miraculix_amd.crossproduct.ld_pairwise_tiles restates it.)
+static void pairwise_group_tiles(int nb, int ndiag, int i_lo, int i_hi, int pairs, std::vector<int4> &prod, std::vector<int4> &band) {
+  int slot = 0;
+  for (int i = i_lo; i < i_hi; i++)
+    for (int j = i; j < std::min(nb, i + ndiag + 1); j++) {
+      band.push_back(make_int4(i, j, 1, slot));
+      // pairs == 1: the (Z, Z) product alone
+      for (int k = 0; k < pairs; k++) prod.push_back(pairs == 1 ? make_int4(i, j, 1, slot) : make_int4(pw_plane_a(k) * nb + i, pw_plane_b(k) * nb + j, 1, slot + k));
+      slot += pairs;
+    }
+}
+
+static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag) {
+  if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
+  if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
+  if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
+  if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
+  if (scores && flag && indiv < 3) { set_error(1, "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", who); return 1; }
+  if (indiv > kPwMaxIndiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, kPwMaxIndiv); return 1; }
+  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call", who, kXFusedMaxRows - 1); return 1; }
+  if (select_device() < 0) return 1;
+  const XGeom g(indiv, snps);
+  const long row_bytes = (indiv + 3) / 4;
+  const bool in_dev = ptr_location(plink, nullptr) == 1, out_dev = ptr_location(out, nullptr) == 1;
+  const int ndiag = ld_band_diagonals(window);
+  // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
+  const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB"), *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
+  const size_t cap = (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
+  const size_t slot_bytes = kPwSlotInts * sizeof(int), row_tiles_max = (size_t)std::min(g.nb, ndiag + 1);
+  const size_t plane_bytes = (size_t)g.rows_pad() * g.pitch(), xbytes = 3 * plane_bytes,
+               obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps),
+               pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
+  size_t free_b = 0, total_b = 0;
+  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+  // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole band needs less)
+  const size_t need = xbytes + pbytes + std::min(std::max(cap, row_tiles_max * kPwPairs * slot_bytes), (size_t)g.nb * row_tiles_max * kPwPairs * slot_bytes) + (out_dev ? 0 : obytes) +
+                      (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
+  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
+  XStream st;
+  if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
+  hipStream_t s = st.s;
+  XBuf d_X, bounce, d_out, d_flag, d_P, d_scr, d_sums, d_bt;
+  if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
+  if (stage_operand(plink, in_dev, row_bytes, true, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s, indiv)) return 1;
+  int has_missing = 1;
+  MXA_HIP(hipMemcpyAsync(&has_missing, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  MXA_HIP(hipStreamSynchronize(s));
+  // no plane holds a 3: the FP4 engine is exact while 4 indiv < 2^24 (pick_engine's rule); MXA_XPROD_ENGINE=i8 forces int8
+  bool f4 = 4 * indiv < (1L << 24);
+  if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
+  // no missing code anywhere: the (Z, Z) product alone, the rest from per-SNP sums (MXA_LD_PAIRWISE_DENSE=1 keeps the six products; bit-identical)
+  const bool dense = has_missing || (e_dense && atoi(e_dense) != 0);
+  const int pairs = dense ? kPwPairs : 1;
+  int *d_sz = nullptr, *d_sa = nullptr;
+  if (!dense) {
+    if (d_sums.alloc(sizeof(int) * 2 * (size_t)g.rows_pad())) return 1;
+    d_sz = (int *)d_sums.p; d_sa = d_sz + g.rows_pad();
+    MXA_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int) * 2 * (size_t)g.rows_pad(), s));
+    const long chunks = std::max<long>(1, std::min<long>(g.nslabs, (1024 + g.nb - 1) / g.nb)), spc = (g.nslabs + chunks - 1) / chunks;
+    hipLaunchKernelGGL(k_pw_rowsums, dim3((unsigned)g.nb, (unsigned)((g.nslabs + spc - 1) / spc)), dim3(256), 0, s, (const uint8_t *)d_X.p, g.nslabs, spc, (long)g.nb, d_sz, d_sa);
+    MXA_HIP(hipGetLastError());
+  }
+  const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (row_tiles_max * (size_t)pairs * slot_bytes)));
+  const int ngroups = (g.nb + rows_per_group - 1) / rows_per_group;
+  std::vector<std::vector<int4>> prod((size_t)ngroups);
+  std::vector<int4> band;
+  std::vector<size_t> band_first((size_t)ngroups + 1, 0);
+  size_t group_tiles_max = 0;
+  for (int c = 0; c < ngroups; c++) {
+    band_first[(size_t)c] = band.size();
+    pairwise_group_tiles(g.nb, ndiag, c * rows_per_group, std::min(g.nb, (c + 1) * rows_per_group), pairs, prod[(size_t)c], band);
+    group_tiles_max = std::max(group_tiles_max, band.size() - band_first[(size_t)c]);
+  }
+  band_first.back() = band.size();
+  XTiles t;
+  if (upload_tiles(std::move(prod), s, t)) return 1;
+  if (d_bt.alloc(band.size() * sizeof(int4)) || d_scr.alloc(group_tiles_max * (size_t)pairs * slot_bytes)) return 1;
+  MXA_HIP(hipMemcpyAsync(d_bt.p, band.data(), band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  double *d_res = out_dev ? out : (double *)d_out.p;
+  const long ld_res = out_dev ? ldb : window + 1;
+  double *d_dst = scores ? (double *)d_P.p : d_res;
+  const long ld_dst = scores ? g.rows_pad() : ld_res;
+  XEvent e0, e1;
+  if (e0.create() || e1.create()) return 1;
+  MXA_HIP(hipEventRecord(e0.e, s));
+  const XPost none{};
+  for (int c = 0; c < ngroups; c++) {
+    // the products of the group into the scratch, then its combine, one behind the other on the call's stream (the next group reuses the scratch)
+    if (t.launch(c, g, f4, s, (const uint8_t *)d_X.p, (double *)d_scr.p, 0, 0, nullptr, 5, none)) return 1;
+    const dim3 grid((unsigned)(band_first[(size_t)c + 1] - band_first[(size_t)c]));
+    const int4 *bt = (const int4 *)d_bt.p + band_first[(size_t)c];
+    auto combine = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, d_dst, ld_dst, window, flag); };
+    if (scores) { if (dense) combine(k_ld_pw_combine<4, true>); else combine(k_ld_pw_combine<4, false>); }
+    else { if (dense) combine(k_ld_pw_combine<3, true>); else combine(k_ld_pw_combine<3, false>); }
+    MXA_HIP(hipGetLastError());
+  }
+  if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
+  else if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
+  MXA_HIP(hipGetLastError());
+  MXA_HIP(hipEventRecord(e1.e, s));
+  if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
+  MXA_HIP(hipStreamSynchronize(s));   // tile lists / scratch lifetime
+  MXA_HIP(profile_launch(e0, e1));
+  debug_info("%s: %d group(s) of %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, rows_per_group, pairs, dense ? "six counts" : "no missing code: per-SNP sums",
+             f4 ? "FP4" : "int8");
+  return 0;
+}
+
 }  // namespace mxa
+
+extern "C" int mxa_ld_band_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind) {
+  mxa::clear_error();
+  return mxa::ld_pairwise_any("mxa_ld_band_pairwise", plink, snps, indiv, window, band, ldb, false, kind);
+}
+
+extern "C" int mxa_ld_scores_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust) {
+  mxa::clear_error();
+  return mxa::ld_pairwise_any("mxa_ld_scores_pairwise", plink, snps, indiv, window, scores, 0, true, adjust);
+}
 
 extern "C" int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind, int is_plink_format,
                            const double *allele_freq) {

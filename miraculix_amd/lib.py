@@ -90,6 +90,10 @@ def load_shared_library():
     L.mxa_ld_band.restype = ctypes.c_int
     L.mxa_ld_scores.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     L.mxa_ld_scores.restype = ctypes.c_int
+    L.mxa_ld_band_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int]
+    L.mxa_ld_band_pairwise.restype = ctypes.c_int
+    L.mxa_ld_scores_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    L.mxa_ld_scores_pairwise.restype = ctypes.c_int
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

@@ -14,6 +14,7 @@
 #   gram                 CG step (config-5 shard): step time + kernel timeline of three steps
 #   xprod [snps indiv]   crossproduct kernel time at config 3, both engines
 #   ld-band [snps indiv window]   windowed LD (mxa_ld_band / mxa_ld_scores): kernel time, tiles, bytes written, both engines; band vs full mxa_ld (A/B)
+#   ld-pairwise [snps indiv window]   pairwise-complete windowed LD (mxa_ld_band_pairwise / mxa_ld_scores_pairwise) against mxa_ld_band / mxa_ld_scores, one process, both engines
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -106,6 +107,9 @@ ld-band)
   done
   unset MXA_XPROD_ENGINE
   timeout -k 10 400 python3 tools/perf_ld_band.py 100000 ${2:-50000} ${3:-1023} 5 --vs-full 2>&1 | tee -a "$O/ld_band.txt" || exit 1 ;;
+ld-pairwise)
+  # 5 % missing (six products per band tile) and the same genotypes without missing codes (fast path) against the plain entries, alternating calls
+  timeout -k 10 500 python3 tools/perf_ld_pairwise.py ${1:-1000000} ${2:-50000} ${3:-1023} 5 2>&1 | tee -a "$O/ld_pairwise.txt" || exit 1 ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

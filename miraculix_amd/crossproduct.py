@@ -5,6 +5,19 @@ import numpy as np
 from . import lib as _lib
 
 
+def _zeros_like(plink, *shape):
+    """the result of an entry: float64 zeros of `shape`, numpy or -- for a torch input -- a tensor on the input's device"""
+    if _lib.is_torch_tensor(plink):
+        import torch
+        return torch.zeros(shape, dtype=torch.float64, device=plink.device)
+    return np.zeros(shape, dtype=np.float64)
+
+
+def _check(rc, entry):
+    if rc != 0:
+        raise RuntimeError(f"{entry} failed: " + _lib.last_error()[1])
+
+
 def snp_crossprod(plink, snps, indiv, is_snpmajor, is_plink_format=False, out=None):
     """crossproduct.jl:44-64.  plink: 2-bit matrix, one row per output index: for is_snpmajor=False `indiv` rows of
     ceil(snps/4) bytes (result indiv x indiv), for is_snpmajor=True `snps` rows of ceil(indiv/4) bytes (result snps x snps).
@@ -18,16 +31,8 @@ def snp_crossprod(plink, snps, indiv, is_snpmajor, is_plink_format=False, out=No
     if nbytes != ncol * ((nrow + 3) // 4):
         raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
     L = _lib.check_library_handle()
-    if out is not None:
-        M = out
-    elif _lib.is_torch_tensor(plink):
-        import torch
-        M = torch.zeros((ncol, ncol), dtype=torch.float64, device=plink.device)
-    else:
-        M = np.zeros((ncol, ncol), dtype=np.float64)
-    rc = L.snp_multiply_gpu(_lib.ptr(plink), int(nrow), int(ncol), _lib.ptr(M), bool(is_plink_format))
-    if rc != 0:
-        raise RuntimeError("snp_multiply_gpu failed: " + _lib.last_error()[1])
+    M = out if out is not None else _zeros_like(plink, ncol, ncol)
+    _check(L.snp_multiply_gpu(_lib.ptr(plink), int(nrow), int(ncol), _lib.ptr(M), bool(is_plink_format)), "snp_multiply_gpu")
     return M
 
 
@@ -40,25 +45,10 @@ def snp_crossprod_panel(plink, inner, n_out, col_begin, col_end, upper_only=Fals
         raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
     w = col_end - col_begin
     L = _lib.check_library_handle()
-    if out is not None:
-        P = out
-    elif _lib.is_torch_tensor(plink):
-        import torch
-        P = torch.zeros((w, n_out), dtype=torch.float64, device=plink.device)
-    else:
-        P = np.zeros((w, n_out), dtype=np.float64)
-    rc = L.mxa_snp_multiply_panel(_lib.ptr(plink), int(inner), int(n_out), int(col_begin), int(col_end), int(bool(upper_only)), _lib.ptr(P), int(n_out),
-                                  int(bool(is_plink_format)))
-    if rc != 0:
-        raise RuntimeError("mxa_snp_multiply_panel failed: " + _lib.last_error()[1])
+    P = out if out is not None else _zeros_like(plink, w, n_out)
+    _check(L.mxa_snp_multiply_panel(_lib.ptr(plink), int(inner), int(n_out), int(col_begin), int(col_end), int(bool(upper_only)), _lib.ptr(P), int(n_out),
+                                    int(bool(is_plink_format))), "mxa_snp_multiply_panel")
     return P
-
-
-def _result_like(plink, n):
-    if _lib.is_torch_tensor(plink):
-        import torch
-        return torch.zeros((n, n), dtype=torch.float64, device=plink.device)
-    return np.zeros((n, n), dtype=np.float64)
 
 
 def grm(plink_transposed, snps, indiv, is_plink_format=False, do_scale=True, allele_freq=None):
@@ -69,13 +59,11 @@ def grm(plink_transposed, snps, indiv, is_plink_format=False, do_scale=True, all
     if int(np.prod(plink_transposed.shape)) != indiv * ((snps + 3) // 4):
         raise ValueError(f"Matrix has wrong dimensions: {tuple(plink_transposed.shape)}")
     L = _lib.check_library_handle()
-    G = _result_like(plink_transposed, indiv)
+    G = _zeros_like(plink_transposed, indiv, indiv)
     f = allele_freq
     if f is not None and not _lib.is_torch_tensor(f):
         f = np.ascontiguousarray(f, dtype=np.float64)
-    rc = L.mxa_grm(_lib.ptr(plink_transposed), int(snps), int(indiv), _lib.ptr(G), int(bool(is_plink_format)), int(bool(do_scale)), _lib.ptr(f))
-    if rc != 0:
-        raise RuntimeError("mxa_grm failed: " + _lib.last_error()[1])
+    _check(L.mxa_grm(_lib.ptr(plink_transposed), int(snps), int(indiv), _lib.ptr(G), int(bool(is_plink_format)), int(bool(do_scale)), _lib.ptr(f)), "mxa_grm")
     return G
 
 
@@ -86,11 +74,9 @@ def ld(plink, snps, indiv, is_plink_format=False, allele_freq=None):
     if int(np.prod(plink.shape)) != snps * ((indiv + 3) // 4):
         raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
     L = _lib.check_library_handle()
-    R = _result_like(plink, snps)
+    R = _zeros_like(plink, snps, snps)
     f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
-    rc = L.mxa_ld(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(R), int(bool(is_plink_format)), _lib.ptr(f))
-    if rc != 0:
-        raise RuntimeError("mxa_ld failed: " + _lib.last_error()[1])
+    _check(L.mxa_ld(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(R), int(bool(is_plink_format)), _lib.ptr(f)), "mxa_ld")
     return R
 
 
@@ -119,14 +105,8 @@ def ld_band(plink, snps, indiv, window, kind="r", is_plink_format=False, allele_
         raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
     f = _ld_window_args(plink, snps, indiv, window, allele_freq)
     L = _lib.check_library_handle()
-    if _lib.is_torch_tensor(plink):
-        import torch
-        B = torch.zeros((snps, int(window) + 1), dtype=torch.float64, device=plink.device)
-    else:
-        B = np.zeros((snps, int(window) + 1), dtype=np.float64)
-    rc = L.mxa_ld_band(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0, int(bool(is_plink_format)), _lib.ptr(f))
-    if rc != 0:
-        raise RuntimeError("mxa_ld_band failed: " + _lib.last_error()[1])
+    B = _zeros_like(plink, snps, int(window) + 1)
+    _check(L.mxa_ld_band(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0, int(bool(is_plink_format)), _lib.ptr(f)), "mxa_ld_band")
     return B
 
 
@@ -137,14 +117,8 @@ def ld_scores(plink, snps, indiv, window, adjust=False, is_plink_format=False, a
     if adjust and indiv < 3:
         raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
     L = _lib.check_library_handle()
-    if _lib.is_torch_tensor(plink):
-        import torch
-        S = torch.zeros(snps, dtype=torch.float64, device=plink.device)
-    else:
-        S = np.zeros(snps, dtype=np.float64)
-    rc = L.mxa_ld_scores(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust)), int(bool(is_plink_format)), _lib.ptr(f))
-    if rc != 0:
-        raise RuntimeError("mxa_ld_scores failed: " + _lib.last_error()[1])
+    S = _zeros_like(plink, snps)
+    _check(L.mxa_ld_scores(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust)), int(bool(is_plink_format)), _lib.ptr(f)), "mxa_ld_scores")
     return S
 
 
@@ -195,14 +169,8 @@ def ld_band_pairwise(plink, snps, indiv, window, kind="r"):
         raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
     _ld_pairwise_args(plink, snps, indiv, window)
     L = _lib.check_library_handle()
-    if _lib.is_torch_tensor(plink):
-        import torch
-        B = torch.zeros((snps, int(window) + 1), dtype=torch.float64, device=plink.device)
-    else:
-        B = np.zeros((snps, int(window) + 1), dtype=np.float64)
-    rc = L.mxa_ld_band_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0)
-    if rc != 0:
-        raise RuntimeError("mxa_ld_band_pairwise failed: " + _lib.last_error()[1])
+    B = _zeros_like(plink, snps, int(window) + 1)
+    _check(L.mxa_ld_band_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(B), int(window) + 1, 1 if kind == "r2" else 0), "mxa_ld_band_pairwise")
     return B
 
 
@@ -213,12 +181,6 @@ def ld_scores_pairwise(plink, snps, indiv, window, adjust=False):
     if adjust and indiv < 3:
         raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
     L = _lib.check_library_handle()
-    if _lib.is_torch_tensor(plink):
-        import torch
-        S = torch.zeros(snps, dtype=torch.float64, device=plink.device)
-    else:
-        S = np.zeros(snps, dtype=np.float64)
-    rc = L.mxa_ld_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust)))
-    if rc != 0:
-        raise RuntimeError("mxa_ld_scores_pairwise failed: " + _lib.last_error()[1])
+    S = _zeros_like(plink, snps)
+    _check(L.mxa_ld_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust))), "mxa_ld_scores_pairwise")
     return S

@@ -52,22 +52,31 @@ __global__ void __launch_bounds__(256) k_plink_lut(uint32_t *__restrict__ d, siz
 // copy rows (src pitch arbitrary) into the tiled layout (mxa_internal.h: byte b of row r -> ((r/256)*nslabs + b/32)*8192 + (r%256)*32
 // + b%32), optionally applying the table; padding bytes/rows stay zero (the buffer is memset first).  *has3 |= 1 when a staged field
 // holds the value 3 (raw 2-bit input, or a byte with a missing pair under the reference's table).
+// the staging kernels' two steps.  The dword at byte b of a packed row, p = its address: one aligned non-temporal load (read once), or byte by byte at an
+// unaligned address and in the row's tail; keep = the mask of the bytes that exist.
+__device__ __forceinline__ uint32_t xstage_load(const uint8_t *p, long b, long row_bytes, uint32_t &keep) {
+  uint32_t w = 0;
+  keep = 0;
+  if (b + 4 <= row_bytes && (reinterpret_cast<size_t>(p) & 3) == 0) { w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p)); keep = 0xFFFFFFFFu; }
+  else
+    for (int u = 0; u < 4; u++)
+      if (b + u < row_bytes) { w |= (uint32_t)p[u] << (8 * u); keep |= 0xFFu << (8 * u); }
+  return w;
+}
+// ... and where the dword at byte b of row R goes in the tiled layout
+__device__ __forceinline__ uint32_t *xstage_dst(uint8_t *dst, long nslabs, long R, long b) {
+  return reinterpret_cast<uint32_t *>(dst + ((size_t)(R / kTileRows) * nslabs + (size_t)(b / kSlabBytes)) * kTileBytes + (size_t)(R % kTileRows) * kSlabBytes + b % kSlabBytes);
+}
 __global__ void __launch_bounds__(256) k_xstage(const uint8_t *__restrict__ src, size_t src_pitch, long row_bytes, long nrows,
                                                 uint8_t *__restrict__ dst, long nslabs, long dst_row0, int apply_lut, int *__restrict__ has3) {
   const long dpr = (row_bytes + 3) / 4;
   const long total = nrows * dpr;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const long r = idx / dpr, d = idx - r * dpr, b = d * 4;
-    const uint8_t *p = src + (size_t)r * src_pitch + b;
-    uint32_t w = 0, keep = 0;
-    if (b + 4 <= row_bytes && (reinterpret_cast<size_t>(p) & 3) == 0) { w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p)); keep = 0xFFFFFFFFu; }   // one aligned dword (read once)
-    else
-      for (int u = 0; u < 4; u++)
-        if (b + u < row_bytes) { w |= (uint32_t)p[u] << (8 * u); keep |= 0xFFu << (8 * u); }
+    uint32_t keep, w = xstage_load(src + (size_t)r * src_pitch + b, b, row_bytes, keep);
     if (apply_lut) w = plink_lut4(w) & keep;
     if (w & (w >> 1) & 0x55555555u) atomicOr(has3, 1);
-    const long R = dst_row0 + r;
-    *reinterpret_cast<uint32_t *>(dst + ((size_t)(R / kTileRows) * nslabs + (size_t)(b / kSlabBytes)) * kTileBytes + (size_t)(R % kTileRows) * kSlabBytes + b % kSlabBytes) = w;
+    *xstage_dst(dst, nslabs, dst_row0 + r, b) = w;
   }
 }
 
@@ -85,21 +94,16 @@ __global__ void __launch_bounds__(256) k_xstage_planes(const uint8_t *__restrict
   uint32_t seen = 0;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const long r = idx / dpr, d = idx - r * dpr, b = d * 4;
-    const uint8_t *p = src + (size_t)r * src_pitch + b;
-    uint32_t w = 0;
-    if (b + 4 <= row_bytes && (reinterpret_cast<size_t>(p) & 3) == 0) w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
-    else
-      for (int u = 0; u < 4; u++)
-        if (b + u < row_bytes) w |= (uint32_t)p[u] << (8 * u);
+    uint32_t keep;
+    const uint32_t w = xstage_load(src + (size_t)r * src_pitch + b, b, row_bytes, keep);
     const long left = indiv - 4 * b;                                            // individuals from this dword's first field on (> 0: b < row_bytes)
     const uint32_t vm = left >= 16 ? 0x55555555u : ((1u << (2 * left)) - 1u) & 0x55555555u;
     const uint32_t H = (w >> 1) & vm, L = w & vm, miss = L & ~H;
     seen |= miss;
-    const long R = dst_row0 + r;
-    uint8_t *q = dst + ((size_t)(R / kTileRows) * nslabs + (size_t)(b / kSlabBytes)) * kTileBytes + (size_t)(R % kTileRows) * kSlabBytes + b % kSlabBytes;
-    *reinterpret_cast<uint32_t *>(q) = ((H & L) << 1) | (H & ~L);
-    *reinterpret_cast<uint32_t *>(q + plane_bytes) = vm & ~miss;
-    *reinterpret_cast<uint32_t *>(q + 2 * plane_bytes) = H & L;
+    uint32_t *q = xstage_dst(dst, nslabs, dst_row0 + r, b);
+    q[0] = ((H & L) << 1) | (H & ~L);
+    q[plane_bytes / 4] = vm & ~miss;
+    q[plane_bytes / 2] = H & L;
   }
   if (__any(seen != 0) && (threadIdx.x & 63) == 0) atomicOr(has_missing, 1);
 }
@@ -126,6 +130,15 @@ __device__ __forceinline__ v4i unpack16(uint32_t w) {
 // product: the column sums of M = X X^T are X (X^T 1) and its diagonal is the row-wise sum of squares, both exact integers computed from the staged
 // 2-bit matrix (k_x_colsum, k_x_rowstats).  The same two functions serve the unfused kernels (k_grm_update, k_ld_center / k_ld_scale: kept for
 // MXA_XPROD_FUSED_POST=0 and as the bit-identity check of the tests): i = row index, j = column index of the element as stored.
+// The epilogue kinds: the POST argument of the kernels and the post_kind of their launchers (plain ints, so that the kernels' symbols stay what they were).
+// kPostGrm and kPostLd are also the `post` of crossprod_any.
+constexpr int kPostNone = 0;        // the plain crossproduct
+constexpr int kPostGrm = 1;         // GRM map
+constexpr int kPostLd = 2;          // LD map
+constexpr int kPostLdBand = 3;      // windowed LD: the LD map into band storage
+constexpr int kPostLdScores = 4;    // windowed LD: the LD map reduced to per-SNP scores
+constexpr int kPostCounts = 5;      // pairwise-complete LD: the raw counts into a scratch slot
+constexpr int kPostKinds = 6;
 struct XPost {
   const double *u = nullptr;      // GRM: column sums cs of M;  LD: allele frequencies f
   const double *w = nullptr;      // LD: 1 / sigma
@@ -164,8 +177,8 @@ __device__ __forceinline__ void xstore(double *p, double v) {
   *p = v;
 #endif
 }
-// ---- windowed LD (mxa_ld_band, mxa_ld_scores): the LD map of POST 2 on the tiles of a band, written as band storage (POST 3) or reduced to per-SNP
-// scores (POST 4).  These two instantiations reuse the kernels' arguments instead of widening XPost (the other instantiations keep their code object
+// ---- windowed LD (mxa_ld_band, mxa_ld_scores): the LD map of kPostLd on the tiles of a band, written as band storage (kPostLdBand) or reduced to per-SNP
+// scores (kPostLdScores).  These two instantiations reuse the kernels' arguments instead of widening XPost (the other instantiations keep their code object
 // byte for byte): ans = the band / the partial buffer P, ld = its leading dimension ldb / the row stride of P, c0 = the window, post.do_scale = kind / adjust.
 // The window predicate, in one place: element (i, j), i <= j, of R belongs to the band.  A per-SNP bound (base pairs, centimorgans) replaces `window` here.
 __device__ __forceinline__ bool ld_in_window(long i, long j, long window) { return j - i <= window; }
@@ -176,98 +189,17 @@ __host__ __device__ __forceinline__ int ld_band_diagonals(long window) { return 
 __host__ __device__ __forceinline__ size_t ld_score_slot(int side, int dt, int ndiag, long stride) { return ((size_t)side * (size_t)(ndiag + 1) + (size_t)dt) * (size_t)stride; }
 constexpr int kXScratchBytes = 4 * 32 * 33 * 8;   // the four waves' 32 x 33 epilogue scratch; the score reduction area lies behind it
 
-template <typename AccT, int POST>
-__device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
-                                                   double *__restrict__ out, long ld, long window, const XPost &post) {
-  double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
-  const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
-  constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
-  auto ldmap = [&](double v, long i, long j) -> double { return ld_scale_map(ld_center_map(v, post.u[i], post.u[j], post.a), post.w[i], post.w[j]); };
-  if constexpr (POST == 3) {
-    // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
-    const bool squared = post.do_scale != 0;
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-        const long gj = gj_base + col;
-        if (gj_base + 31 < gi_base || !ld_in_window(gi_base + 31, gj_base, window)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
-#pragma unroll
-        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = (double)acc[a][b][r] * scale;
-        if (gj < n) {
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + rq;
-            const long gi = gi_base + row;
-            if (gi <= gj && ld_in_window(gi, gj, window)) {
-              const double v = ldmap(scratch[row * 33 + col], gj, gi);
-              xstore(&out[(size_t)(gj - gi) + (size_t)gi * ld], squared ? v * v : v);
-            }
-          }
-        }
-      }
-  } else {
-    // scores: t(r) summed along the rows of the tile (for its I rows) and, off the diagonal, along its columns (for its J rows); every sum in a fixed order:
-    // a lane over its elements, then (hh 0 + hh 1) + (second wave's hh 0 + hh 1) through the LDS; one store per slot, no atomics
-    const bool diag_tile = i0 == j0, adjust = post.do_scale != 0;
-    const double inv_adj = adjust ? 1.0 / (post.a * 0.25 - 2.0) : 0.0;     // post.a = 4 indiv: 1 / (indiv - 2)
-    auto term = [&](double v, long i, long j) -> double {                   // every operation rounded on its own (no contraction): the tests restate this line
-      const double r = ldmap(v, i, j), r2 = __dmul_rn(r, r);
-      return adjust ? __dsub_rn(r2, __dmul_rn(__dsub_rn(1.0, r2), inv_adj)) : r2;
-    };
-    double rowacc[4] = {0.0, 0.0, 0.0, 0.0}, colacc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-        const long gj = gj_base + col, gi = gi_base + col;
-        // wave-uniform: no element of the sub-block is within the window (on the diagonal tile both triangles count: |gj - gi| <= window)
-        if (gj_base >= gi_base ? !ld_in_window(gi_base + 31, gj_base, window) : !ld_in_window(gj_base + 31, gi_base, window)) continue;
-#pragma unroll
-        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = (double)acc[a][b][r] * scale;
-        if (!diag_tile && gj < n) {                            // J side: lane = column gj, its 16 rows gi (gi < gj < n)
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + rq;
-            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += term(scratch[row * 33 + col], gj, gi_base + row);
-          }
-        }
-        if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
-#pragma unroll
-          for (int it = 0; it < 16; it++) {
-            const int cc = 2 * it + hh;
-            const long gjj = gj_base + cc;
-            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += term(scratch[col * 33 + cc], gi, gjj);
-          }
-        }
-      }
-    double *red = reinterpret_cast<double *>(smem + kXScratchBytes);   // red[side][wave][hh][a or b][32]
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      red[(((0 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = rowacc[q];
-      red[(((1 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = colacc[q];
-    }
-    __syncthreads();
-    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = ld_band_diagonals(window);
-    auto slot = [&](int side, int w) { return red[(((side * 4 + w) * 2 + 0) * 4 + q) * 32 + c] + red[(((side * 4 + w) * 2 + 1) * 4 + q) * 32 + c]; };
-    out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
-    if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
-  }
-}
-
-// The same store for the combine kernel of the pairwise-complete entries (k_ld_pw_combine), where an element's value does not come from an accumulator and needs
-// no map: prep(a, b) readies the lane's sub-block (a, b), val(a, b, r) is the finished value (POST 3: r, POST 4: t(r)) of the element that accumulator register r
-// of that sub-block holds in the crossproduct kernels.  Band layout, window tests, summation order and the slots of P are those of xprod_store_window line by
-// line (a copy and not a shared template: the epilogue above sits in kernels with 256 accumulator registers, whose register allocation changes with any
-// restructuring of it).  squared: POST 3 stores v * v.
-template <int POST, typename Prep, typename Val>
-__device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
+// The one store of the windowed entries: the only place that knows the band layout, the window tests, the summation order and the slots of P.  It serves the
+// crossproduct kernels (xprod_store_window below) and the combine kernel of the pairwise-complete entries (k_ld_pw_combine) alike: prep(a, b) readies the
+// lane's sub-block (a, b); val(a, b, r) is what goes to the LDS scratch for the element that accumulator register r of that sub-block holds in the crossproduct
+// kernels; fin(v, i, j) finishes a value read back from the scratch into the band entry (kPostLdBand; squared: v * v is stored) or the score term
+// (kPostLdScores) of element (i, j), i, j < n.
+template <int POST, typename Prep, typename Val, typename Fin>
+__device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
                                                 double *__restrict__ out, long ld, long window) {
   double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
   const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
-  if constexpr (POST == 3) {
+  if constexpr (POST == kPostLdBand) {
     // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
 #pragma unroll
     for (int a = 0; a < 4; a++)
@@ -285,7 +217,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared
             const int row = (r & 3) + 8 * (r >> 2) + rq;
             const long gi = gi_base + row;
             if (gi <= gj && ld_in_window(gi, gj, window)) {
-              const double v = scratch[row * 33 + col];
+              const double v = fin(scratch[row * 33 + col], gj, gi);
               xstore(&out[(size_t)(gj - gi) + (size_t)gi * ld], squared ? v * v : v);
             }
           }
@@ -311,7 +243,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared
 #pragma unroll
           for (int r = 0; r < 16; r++) {
             const int row = (r & 3) + 8 * (r >> 2) + rq;
-            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += scratch[row * 33 + col];
+            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += fin(scratch[row * 33 + col], gj, gi_base + row);
           }
         }
         if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
@@ -319,7 +251,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared
           for (int it = 0; it < 16; it++) {
             const int cc = 2 * it + hh;
             const long gjj = gj_base + cc;
-            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += scratch[col * 33 + cc];
+            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += fin(scratch[col * 33 + cc], gi, gjj);
           }
         }
       }
@@ -337,7 +269,28 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, bool squared
   }
 }
 
-// Count store (POST 5, pairwise-complete LD): the raw accumulators of the tile as int32 (FP4 engine: acc x 4, exact) into the scratch slot the tile entry
+// The crossproduct kernels' side of it: the scratch takes the accumulators as fp64, and a value read back is mapped with the LD map of kPostLd (post.u is the
+// caller's freq, of length n: fin is only ever called with i, j < n) -- into the band entry r, or the score term t(r).
+template <typename AccT, int POST>
+__device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
+                                                   double *__restrict__ out, long ld, long window, const XPost &post) {
+  constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
+  const bool flag = post.do_scale != 0;                                    // kind (band) / adjust (scores)
+  // post.a = 4 indiv: 1 / (indiv - 2).  Formed here and not inside fin: there the gang kernels spill 648 / 764 bytes per lane (FP4 / int8) instead of 432 / 492
+  const double inv_adj = POST == kPostLdScores && flag ? 1.0 / (post.a * 0.25 - 2.0) : 0.0;
+  auto fin = [&](double v, long i, long j) -> double {
+    const double r = ld_scale_map(ld_center_map(v, post.u[i], post.u[j], post.a), post.w[i], post.w[j]);
+    if constexpr (POST == kPostLdBand) return r;
+    else {                                                                 // every operation rounded on its own (no contraction): the tests restate this line
+      const double r2 = __dmul_rn(r, r);
+      return flag ? __dsub_rn(r2, __dmul_rn(__dsub_rn(1.0, r2), inv_adj)) : r2;
+    }
+  };
+  ld_window_store<POST>([](int, int) {}, [&](int a, int b, int r) -> double { return (double)acc[a][b][r] * scale; }, fin, POST == kPostLdBand && flag, smem, wave, lane,
+                        wi, wj, i0, j0, n, out, ld, window);
+}
+
+// Count store (kPostCounts, pairwise-complete LD): the raw accumulators of the tile as int32 (FP4 engine: acc x 4, exact) into the scratch slot the tile entry
 // names (its fourth field), 65 536 ints.  Lane-linear and register-major in quads: registers 4 q .. 4 q + 3 of thread t at slot + q * 1024 + 4 t, one 16-byte
 // store per lane and quad (a wave writes 1 KiB contiguous); no LDS transpose.  The combine kernel reads the same addresses with the same lane <-> element map.
 constexpr size_t kPwSlotInts = (size_t)kXT * kXT;
@@ -354,7 +307,7 @@ __device__ __forceinline__ void xprod_store_counts(const AccT (&acc)[4][4], int 
         p[((a * 4 + b) * 4 + q) * 256] = make_int4(cnt(acc[a][b][4 * q]), cnt(acc[a][b][4 * q + 1]), cnt(acc[a][b][4 * q + 2]), cnt(acc[a][b][4 * q + 3]));
 }
 
-// POST: 0 plain crossproduct, 1 GRM map, 2 LD map (XPost above); each stored element is mapped with ITS OWN (row, column), so both images equal what
+// POST: kPostNone, kPostGrm, kPostLd (XPost above); each stored element is mapped with ITS OWN (row, column), so both images equal what
 // the unfused element-wise kernels produce.  With a map the 32 x 32 block goes to the LDS scratch first (static accumulator indices) and both images
 // are written by loops over IT, never over the accumulators: when the maps still held fp64 divisions, their 512-fold unrolled code exceeded the
 // compiler's full-unroll budget, the loops stayed rolled, and a rolled loop over the accumulators indexes them dynamically, i.e. moves them to
@@ -365,9 +318,9 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
   double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);   // the DMA ring is dead after the last barrier
   const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
   constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
-  if constexpr (POST >= 3) {   // windowed LD: band storage / scores (ans, ld, c0 = band or partial buffer, its stride, the window)
+  if constexpr (POST == kPostLdBand || POST == kPostLdScores) {   // windowed LD: band storage / scores (ans, ld, c0 = band or partial buffer, its stride, the window)
     xprod_store_window<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, n, ans, ld, c0, post);
-  } else if constexpr (POST == 0) {
+  } else if constexpr (POST == kPostNone) {
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -393,9 +346,9 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
       }
   } else {
     double tot_nn = 0.0, cc_scale = 1.0;
-    if (POST == 1) { tot_nn = post.scal[0] / ((double)n * (double)n); cc_scale = post.do_scale ? 1.0 / post.scal[1] : 1.0; }
+    if (POST == kPostGrm) { tot_nn = post.scal[0] / ((double)n * (double)n); cc_scale = post.do_scale ? 1.0 / post.scal[1] : 1.0; }
     auto map = [&](double v, long i, long j) -> double {       // element M[i][j] (i, j < n)
-      if (POST == 1) return grm_map(v, post.u[i], post.u[j], post.a, tot_nn, cc_scale, post.do_scale);
+      if (POST == kPostGrm) return grm_map(v, post.u[i], post.u[j], post.a, tot_nn, cc_scale, post.do_scale);
       return ld_scale_map(ld_center_map(v, post.u[i], post.u[j], post.a), post.w[i], post.w[j]);
     };
 #pragma unroll
@@ -617,11 +570,11 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0 && diag) { diag[2 * tile_index] = t1 - t0; diag[2 * tile_index + 1] = r1 - r0; }
   }
-  if constexpr (POST == 5) xprod_store_counts<AccT>(acc, reinterpret_cast<int *>(ans), t.w);   // ans = the count scratch, t.w = the tile's slot
+  if constexpr (POST == kPostCounts) xprod_store_counts<AccT>(acc, reinterpret_cast<int *>(ans), t.w);   // ans = the count scratch, t.w = the tile's slot
   else xprod_store<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, t.z, n, ans, ld, c0, post);
 }
 
-template <bool DIAG, int EXP = 0, int POST = 0>
+template <bool DIAG, int EXP = 0, int POST = kPostNone>
 __global__ void __launch_bounds__(256, 1)
 k_crossprod_f4(const uint8_t *__restrict__ X, long nslabs, int stages, const int4 *__restrict__ tiles, long n, double *__restrict__ ans,
                long ld, long c0, unsigned long long *__restrict__ diag, XPost post) {
@@ -629,7 +582,7 @@ k_crossprod_f4(const uint8_t *__restrict__ X, long nslabs, int stages, const int
   if (t.z == 0) return;                         // padding entry of the XCD-aware tile order (whole workgroup, before any barrier)
   xprod_tile<DIAG, EXP, false, POST>(X, nslabs, stages, t, blockIdx.x, n, ans, ld, c0, diag, post);
 }
-template <bool DIAG, int POST = 0>
+template <bool DIAG, int POST = kPostNone>
 __global__ void __launch_bounds__(256, 1)
 k_crossprod_i8(const uint8_t *__restrict__ X, long nslabs, int stages, const int4 *__restrict__ tiles, long n, double *__restrict__ ans,
                long ld, long c0, unsigned long long *__restrict__ diag, XPost post) {
@@ -808,6 +761,10 @@ static int launch_lds(dim3 grid, hipStream_t s, A... a) {
 // the one-workgroup-per-tile instantiation of an engine
 template <bool I8, bool DIAG, int POST> constexpr auto k_tiles = I8 ? &k_crossprod_i8<DIAG, POST> : &k_crossprod_f4<DIAG, 0, POST>;
 
+// f(std::integral_constant<int, K>()) for every epilogue kind K
+template <int... K, typename F>
+static void for_each_post_kind(std::integer_sequence<int, K...>, F f) { (f(std::integral_constant<int, K>()), ...); }
+
 // one launch over a tile list with either engine (f4: FP4 MFMA, else int8 MFMA); d_diag: in-kernel clocks of the DIAG instantiation
 // gang_mid_capacity: ints available behind d_gang[32] for the per-gang counters of the second meeting point (0: none)
 static int launch_tiles(const XGeom &g, bool f4, size_t ntiles, hipStream_t s, const uint8_t *d_X, const int4 *d_tiles, double *d_ans, long ld, long c0,
@@ -851,17 +808,15 @@ static int launch_tiles(const XGeom &g, bool f4, size_t ntiles, hipStream_t s, c
     constexpr int POST = decltype(pk)::value;
     if (gang)
       return launch_lds<&k_crossprod_gang<I8, POST>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, slots, g.rows, d_ans, ld, c0, post, d_gang, join_ticks, xcc_mask, d_mid, mid_parts);
-    if (POST == 0 && d_diag) return launch_lds<k_tiles<I8, true, 0>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, g.rows, d_ans, ld, c0, d_diag, post);
+    if (POST == kPostNone && d_diag) return launch_lds<k_tiles<I8, true, kPostNone>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, g.rows, d_ans, ld, c0, d_diag, post);
     return launch_lds<k_tiles<I8, false, POST>>(grid, s, d_X, g.nslabs, g.stages, d_tiles, g.rows, d_ans, ld, c0, nullptr, post);
   };
-  using F4 = std::false_type;
-  using I8 = std::true_type;
-  if (post_kind == 1) return f4 ? go(F4(), std::integral_constant<int, 1>()) : go(I8(), std::integral_constant<int, 1>());
-  if (post_kind == 2) return f4 ? go(F4(), std::integral_constant<int, 2>()) : go(I8(), std::integral_constant<int, 2>());
-  if (post_kind == 3) return f4 ? go(F4(), std::integral_constant<int, 3>()) : go(I8(), std::integral_constant<int, 3>());   // windowed LD: band storage
-  if (post_kind == 4) return f4 ? go(F4(), std::integral_constant<int, 4>()) : go(I8(), std::integral_constant<int, 4>());   // windowed LD: scores
-  if (post_kind == 5) return f4 ? go(F4(), std::integral_constant<int, 5>()) : go(I8(), std::integral_constant<int, 5>());   // pairwise LD: count store
-  return f4 ? go(F4(), std::integral_constant<int, 0>()) : go(I8(), std::integral_constant<int, 0>());
+  int rc = -1;
+  for_each_post_kind(std::make_integer_sequence<int, kPostKinds>(), [&](auto pk) {
+    if (post_kind == decltype(pk)::value) rc = f4 ? go(std::false_type(), pk) : go(std::true_type(), pk);
+  });
+  if (rc < 0) { set_error(1, "crossproduct: no epilogue kind %d", post_kind); return 1; }
+  return rc;
 }
 
 // ---- tile lists.  Tile (i, j), i <= j, with flags bit 1: it writes its direct image M[J rows, I cols] (columns of tile i), bit 2: its mirror image
@@ -1209,14 +1164,14 @@ __global__ void __launch_bounds__(256) k_x_finish_stats(const unsigned long long
   out[i] = f ? 1.0 / sqrt(ld_center_map(v, f[i], f[i], four_indiv)) : v;
 }
 
-// post: 0 none, 1 GRM (do_scale as given, f = allele frequencies of length k), 2 LD (f of length rows, k = number of individuals)
+// post: kPostNone, kPostGrm (do_scale as given, f = allele frequencies of length k), kPostLd (f of length rows, k = number of individuals)
 static int postprocess_device(double *d_M, long rows, long k, int post, int do_scale, const double *d_f, hipStream_t s) {
-  if (post == 0) return 0;
+  if (post == kPostNone) return 0;
   XBuf tmp_buf;
   if (tmp_buf.alloc(sizeof(double) * (size_t)(rows + 4))) return 1;
   double *tmp = (double *)tmp_buf.p;
   dim3 g2((unsigned)rows, (unsigned)((rows + 255) / 256));   // x = column (unbounded), y = row chunk (<= 65535)
-  if (post == 1) {
+  if (post == kPostGrm) {
     hipLaunchKernelGGL(k_sym_colsum, dim3((unsigned)rows), dim3(256), 0, s, d_M, rows, tmp);
     hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, tmp, rows, 0, tmp + rows);
     if (do_scale) hipLaunchKernelGGL(k_vec_reduce, dim3(1), dim3(1024), 0, s, d_f, k, 1, tmp + rows + 1);
@@ -1264,7 +1219,14 @@ static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_
   return 0;
 }
 
-// What the GRM (post 1) / LD (post 2) map fused into the epilogue needs, from the staged 2-bit matrix: ~2 passes over rows * k / 4 bytes instead of 3 over
+// grid of the per-row passes over the staged operand (k_x_rowstats, k_pw_rowsums): (row tiles, K chunks of *spc slabs each), ~1024 blocks at least
+static dim3 rowstats_grid(const XGeom &g, long *spc) {
+  const long chunks = std::max<long>(1, std::min<long>(g.nslabs, (1024 + g.nb - 1) / g.nb));
+  *spc = (g.nslabs + chunks - 1) / chunks;
+  return dim3((unsigned)g.nb, (unsigned)((g.nslabs + *spc - 1) / *spc));
+}
+
+// What the GRM (kPostGrm) / LD (kPostLd) map fused into the epilogue needs, from the staged 2-bit matrix: ~2 passes over rows * k / 4 bytes instead of 3 over
 // 8 * rows^2.  xp points into st[2]; st[0..2] are kept by the caller until the product has run.
 static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post, int do_scale, const double *d_f, XBuf (&st)[3], hipStream_t s, XPost &xp) {
   const long rows = g.rows, rows_pad = g.rows_pad(), nslabs = g.nslabs, ntiles = g.nb;
@@ -1273,11 +1235,10 @@ static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post
   int *t = (int *)st[0].p;
   unsigned long long *raw = (unsigned long long *)st[1].p;
   double *out = (double *)st[2].p;
-  const long chunks = std::max<long>(1, std::min<long>(nslabs, (1024 + ntiles - 1) / ntiles));   // >= ~1024 blocks
-  const long spc = (nslabs + chunks - 1) / chunks;
-  const dim3 g_rows((unsigned)ntiles, (unsigned)((nslabs + spc - 1) / spc));
+  long spc = 0;
+  const dim3 g_rows = rowstats_grid(g, &spc);
   const unsigned g_fin = (unsigned)((rows + 255) / 256);
-  if (post == 1) {
+  if (post == kPostGrm) {
     hipLaunchKernelGGL(k_x_colsum, dim3((unsigned)nslabs), dim3(256), 0, s, d_X, nslabs, ntiles, t);
     hipLaunchKernelGGL((k_x_rowstats<true, false>), g_rows, dim3(256), 0, s, d_X, nslabs, spc, (const int *)t, raw, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(k_x_finish_stats, dim3(g_fin), dim3(256), 0, s, raw, rows, (const double *)nullptr, 0.0, out);
@@ -1305,7 +1266,7 @@ static int pick_engine(const int *d_has3, long k, hipStream_t s, bool &f4) {
   return 0;
 }
 
-static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, double *ans, bool is_plink, int post = 0, int do_scale = 0,
+static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, double *ans, bool is_plink, int post = kPostNone, int do_scale = 0,
                          const double *freq = nullptr, long c_begin = 0, long c_end = -1, bool upper_only = false, long ld = -1, int device = -1) {
   if (c_end < 0) c_end = rows;
   if (ld < 0) ld = rows;
@@ -1372,7 +1333,7 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   // through the slab pipeline into that buffer, or through the pipeline's ring of column slabs with no such buffer at all.
   // GRM / LD: the element-wise map is fused into the crossproduct epilogue (whole matrix; MXA_XPROD_FUSED_POST=0 keeps the three extra passes over the result).
   // (rows >= kXFusedMaxRows: the three-pass post-processing runs)
-  const int post_kind = post && fused_on && whole && rows < kXFusedMaxRows ? post : 0;
+  const int post_kind = post && fused_on && whole && rows < kXFusedMaxRows ? post : kPostNone;
   const bool slabs = pipelined && (!post || post_kind);   // unfused post-processing needs the whole matrix on the device: one copy, even where the ring would go
   // the ring where the call is bound by the download anyway -- the ring computes every off-diagonal tile twice.  Estimates: triangular arithmetic at the
   // measured tile rate against the download at ~55 GB/s of four copiers.  MXA_XPROD_HOST_RING: 0 never, 1 by this estimate (default), 2 always (tests).
@@ -1405,7 +1366,7 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   }
   const double *d_f = freq;
   if (post && freq && ptr_location(freq, nullptr) != 1) {
-    const long flen = post == 1 ? k : rows;
+    const long flen = post == kPostGrm ? k : rows;
     if (f_tmp.alloc(sizeof(double) * flen)) return 1;
     MXA_HIP(hipMemcpyAsync(f_tmp.p, freq, sizeof(double) * flen, hipMemcpyHostToDevice, s));
     d_f = (const double *)f_tmp.p;
@@ -1459,35 +1420,93 @@ static int ld_window_download(const double *d_res, size_t obytes, long snps, lon
   return 0;
 }
 
+namespace {
+// One call of a windowed entry: everything around the route's own staging and tile launches.  begin(): the shared argument checks, the sizes, the
+// pre-flight, the stream, the operand / result / partial buffers and the events; start() and finish() enclose the launches: d_dst (leading dimension
+// ld_dst) is where they write -- the band, or the scores' partial buffer P -- and finish() turns it into the result at d_res and delivers that.
+struct LdWindow {
+  const char *who;
+  const unsigned char *plink;
+  long snps, indiv, window;
+  double *out;
+  long ldb;
+  bool scores;
+  int flag;                    // kind (band) / adjust (scores)
+  XGeom g;
+  long row_bytes = 0;
+  int ndiag;
+  bool in_dev = false, out_dev = false;
+  size_t plane_bytes = 0, obytes = 0;
+  XStream st;
+  hipStream_t s = nullptr;
+  XBuf d_X, bounce, d_out, d_flag, d_P;
+  XEvent e0, e1;
+  double *d_res = nullptr, *d_dst = nullptr;
+  long ld_res = 0, ld_dst = 0;
+  LdWindow(const char *who_, const unsigned char *plink_, long snps_, long indiv_, long window_, double *out_, long ldb_, bool scores_, int flag_)
+      : who(who_), plink(plink_), snps(snps_), indiv(indiv_), window(window_), out(out_), ldb(ldb_), scores(scores_), flag(flag_), g(indiv_, snps_),
+        ndiag(ld_band_diagonals(window_)) {}
+  const uint8_t *X() const { return (const uint8_t *)d_X.p; }
+
+  // planes: of the staged operand; extra_bytes: what the route allocates beyond the operand, the result and the partial buffer, for the pre-flight.
+  // The checks run in the order in which the entries have always reported them, so the two that only one route has are passed in: route_error (a complete
+  // message, or nullptr) is reported behind "bad arguments", max_indiv (0: no bound) in front of the SNP bound; adj_msg, snps_msg: the route's wording.
+  int begin(int planes, size_t extra_bytes, const char *route_error, long max_indiv, const char *adj_msg, const char *snps_msg) {
+    if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
+    if (route_error) { set_error(1, route_error, who); return 1; }
+    if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
+    if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
+    if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
+    if (scores && flag && indiv < 3) { set_error(1, adj_msg, who); return 1; }
+    if (max_indiv && indiv > max_indiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, max_indiv); return 1; }
+    if (snps >= kXFusedMaxRows) { set_error(1, snps_msg, who, kXFusedMaxRows - 1); return 1; }
+    if (select_device() < 0) return 1;
+    row_bytes = (indiv + 3) / 4;
+    in_dev = ptr_location(plink, nullptr) == 1;
+    out_dev = ptr_location(out, nullptr) == 1;
+    // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
+    plane_bytes = (size_t)g.rows_pad() * g.pitch();
+    obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps);
+    const size_t pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
+    size_t free_b = 0, total_b = 0;
+    MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = planes * plane_bytes + pbytes + extra_bytes + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
+    if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
+    if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
+    s = st.s;
+    if (d_X.alloc(planes * plane_bytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
+    d_res = out_dev ? out : (double *)d_out.p;
+    ld_res = out_dev ? ldb : window + 1;
+    d_dst = scores ? (double *)d_P.p : d_res;
+    ld_dst = scores ? g.rows_pad() : ld_res;
+    return e0.create() || e1.create();
+  }
+  int start() { MXA_HIP(hipEventRecord(e0.e, s)); return 0; }
+  int finish() {
+    if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
+    else if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
+    MXA_HIP(hipGetLastError());
+    MXA_HIP(hipEventRecord(e1.e, s));
+    if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
+    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
+    MXA_HIP(profile_launch(e0, e1));
+    return 0;
+  }
+};
+}  // namespace
+
+// the plain route: the operand staged as it is, the LD map's statistics, and one launch of the band's tiles with the window epilogue
 static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag, bool is_plink,
                          const double *freq) {
-  if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (!freq) { set_error(1, "%s: allele frequencies are required", who); return 1; }
-  if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
-  if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
-  if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
-  if (scores && flag && indiv < 3) { set_error(1, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3", who); return 1; }
-  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call (the fused statistics)", who, kXFusedMaxRows - 1); return 1; }
-  if (select_device() < 0) return 1;
-  const XGeom g(indiv, snps);
-  const long row_bytes = (indiv + 3) / 4;
-  const bool in_dev = ptr_location(plink, nullptr) == 1, out_dev = ptr_location(out, nullptr) == 1;
-  const int ndiag = ld_band_diagonals(window);
-  // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
-  const size_t xbytes = (size_t)g.rows_pad() * g.pitch(), obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps),
-               pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
-  size_t free_b = 0, total_b = 0;
-  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t need = xbytes + pbytes + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
-  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
-  XStream st;
-  if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
-  hipStream_t s = st.s;
-  XBuf d_X, bounce, d_out, d_flag, f_tmp, d_P;
-  if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
-  if (stage_operand(plink, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s)) return 1;
+  LdWindow c(who, plink, snps, indiv, window, out, ldb, scores, flag);
+  if (c.begin(1, 0, freq ? nullptr : "%s: allele frequencies are required", 0, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3",
+              "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
+  const XGeom &g = c.g;
+  hipStream_t s = c.s;
+  if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s)) return 1;
   bool f4 = false;
-  if (pick_engine((const int *)d_flag.p, indiv, s, f4)) return 1;
+  if (pick_engine((const int *)c.d_flag.p, indiv, s, f4)) return 1;
+  XBuf f_tmp;
   const double *d_f = freq;
   if (ptr_location(freq, nullptr) != 1) {
     if (f_tmp.alloc(sizeof(double) * (size_t)snps)) return 1;
@@ -1496,28 +1515,12 @@ static int ld_window_any(const char *who, const unsigned char *plink, long snps,
   }
   XPost xp;
   XBuf stats[3];
-  if (fused_post_stats(g, (const uint8_t *)d_X.p, indiv, 2, 0, d_f, stats, s, xp)) return 1;
+  if (fused_post_stats(g, c.X(), indiv, kPostLd, 0, d_f, stats, s, xp)) return 1;
   xp.do_scale = flag;                                     // kind / adjust (xprod_store_window)
   XTiles t;
-  if (upload_tiles({band_tiles(g.nb, ndiag)}, s, t)) return 1;
-  double *d_res = out_dev ? out : (double *)d_out.p;
-  const long ld_res = out_dev ? ldb : window + 1;
-  XEvent e0, e1;
-  if (e0.create() || e1.create()) return 1;
-  MXA_HIP(hipEventRecord(e0.e, s));
-  if (scores) {
-    if (t.launch(0, g, f4, s, (const uint8_t *)d_X.p, (double *)d_P.p, g.rows_pad(), window, nullptr, 4, xp)) return 1;
-    hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
-  } else {
-    if (t.launch(0, g, f4, s, (const uint8_t *)d_X.p, d_res, ld_res, window, nullptr, 3, xp)) return 1;
-    if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
-  }
-  MXA_HIP(hipGetLastError());
-  MXA_HIP(hipEventRecord(e1.e, s));
-  if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
-  MXA_HIP(hipStreamSynchronize(s));   // tile list / statistics lifetime
-  MXA_HIP(profile_launch(e0, e1));
-  return 0;
+  if (upload_tiles({band_tiles(g.nb, c.ndiag)}, s, t)) return 1;
+  if (c.start() || t.launch(0, g, f4, s, c.X(), c.d_dst, c.ld_dst, window, nullptr, scores ? kPostLdScores : kPostLdBand, xp)) return 1;
+  return c.finish();
 }
 
 // ---- pairwise-complete windowed LD (mxa_ld_band_pairwise, mxa_ld_scores_pairwise): Pearson's r of SNPs i, j over the individuals genotyped at BOTH.
@@ -1525,7 +1528,7 @@ static int ld_window_any(const char *who, const unsigned char *plink, long snps,
 //   N = M_i.M_j   Sxy = Z_i.Z_j   Sx = Z_i.M_j   Sy = M_i.Z_j   Sxx = Sx + 2 A_i.M_j   Syy = Sy + 2 M_i.A_j
 //   num = N Sxy - Sx Sy   dx = N Sxx - Sx^2   dy = N Syy - Sy^2   r = num / sqrt(dx dy)
 // Six tile products per band tile (count store into a scratch slot each), then k_ld_pw_combine forms r per element and stores the band / reduces the scores
-// exactly as the epilogue of mxa_ld_band / mxa_ld_scores does (ld_window_store).  The band runs in groups of tile rows so that the scratch stays bounded.
+// through the epilogue of mxa_ld_band / mxa_ld_scores itself (ld_window_store).  The band runs in groups of tile rows so that the scratch stays bounded.
 // num, dx, dy are formed in fp64 from the int32 counts: every product and difference is an integer below 4 indiv^2 < 2^53 (guarded by the caller), i.e. exact
 // whether or not the compiler contracts them; dx dy, the square root and the quotient are rounded once each.  The expression is symmetric in (i, j) bit for bit.
 constexpr long kPwMaxIndiv = 47453132L;   // 4 indiv^2 < 2^53
@@ -1539,11 +1542,11 @@ __device__ __forceinline__ double pw_r(double N, double Sxy, double Sx, double S
   const double num = N * Sxy - Sx * Sy, dx = N * Sxx - Sx * Sx, dy = N * Syy - Sy * Sy;   // exact integers
   return __ddiv_rn(num, __dsqrt_rn(__dmul_rn(dx, dy)));                                    // dx dy = 0 (no shared individuals, or a SNP constant on them): 0 / 0 = NaN
 }
-// POST 3: the band entry r (ld_window_store squares it for kind 1); POST 4: the score term t(r) with the pair's own N, every operation rounded on its own
+// kPostLdBand: the band entry r (ld_window_store squares it for kind 1); kPostLdScores: the score term t(r) with the pair's own N, every operation rounded on its own
 template <int POST>
 __device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, double Sy, double Ax, double Ay, bool adjust) {
   const double r = pw_r(N, Sxy, Sx, Sy, Ax, Ay);
-  if constexpr (POST == 3) return r;
+  if constexpr (POST == kPostLdBand) return r;
   const double r2 = __dmul_rn(r, r);
   return adjust ? __dsub_rn(r2, __ddiv_rn(__dsub_rn(1.0, r2), __dsub_rn(N, 2.0))) : r2;
 }
@@ -1554,7 +1557,7 @@ __device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, doub
 template <int POST, bool DENSE>
 __global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ scratch, const int4 *__restrict__ btiles, const int *__restrict__ sz, const int *__restrict__ sa,
                                                        long n, double indiv, double *__restrict__ out, long ld, long window, int flag) {
-  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (POST == 4 ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
+  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (POST == kPostLdScores ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
   const int4 t = btiles[blockIdx.x];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
   const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
@@ -1583,7 +1586,7 @@ __global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ s
       return pw_value<POST>(indiv, (double)cnt[0][r], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj], adjust);
     }
   };
-  ld_window_store<POST>(prep, val, POST == 3 && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld, window);
+  ld_window_store<POST>(prep, val, [](double v, long, long) { return v; }, POST == kPostLdBand && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld, window);
 }
 
 // per SNP row: sz = sum z (plane Z), sa = sum a (plane A) of the stacked operand, for the missing-free path.  Grid (row tiles, K chunks), thread = row of the tile
@@ -1621,40 +1624,24 @@ static void pairwise_group_tiles(int nb, int ndiag, int i_lo, int i_hi, int pair
     }
 }
 
+// the pairwise route: the three planes staged, per group of tile rows the count products and their combine
 static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag) {
-  if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
-  if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
-  if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
-  if (scores && flag && indiv < 3) { set_error(1, "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", who); return 1; }
-  if (indiv > kPwMaxIndiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, kPwMaxIndiv); return 1; }
-  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call", who, kXFusedMaxRows - 1); return 1; }
-  if (select_device() < 0) return 1;
-  const XGeom g(indiv, snps);
-  const long row_bytes = (indiv + 3) / 4;
-  const bool in_dev = ptr_location(plink, nullptr) == 1, out_dev = ptr_location(out, nullptr) == 1;
-  const int ndiag = ld_band_diagonals(window);
   // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
   const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB"), *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
   const size_t cap = (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
-  const size_t slot_bytes = kPwSlotInts * sizeof(int), row_tiles_max = (size_t)std::min(g.nb, ndiag + 1);
-  const size_t plane_bytes = (size_t)g.rows_pad() * g.pitch(), xbytes = 3 * plane_bytes,
-               obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps),
-               pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
-  size_t free_b = 0, total_b = 0;
-  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t slot_bytes = kPwSlotInts * sizeof(int);
+  LdWindow c(who, plink, snps, indiv, window, out, ldb, scores, flag);
+  const size_t row_tiles_max = (size_t)std::min(c.g.nb, c.ndiag + 1);
   // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole band needs less)
-  const size_t need = xbytes + pbytes + std::min(std::max(cap, row_tiles_max * kPwPairs * slot_bytes), (size_t)g.nb * row_tiles_max * kPwPairs * slot_bytes) + (out_dev ? 0 : obytes) +
-                      (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
-  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
-  XStream st;
-  if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
-  hipStream_t s = st.s;
-  XBuf d_X, bounce, d_out, d_flag, d_P, d_scr, d_sums, d_bt;
-  if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
-  if (stage_operand(plink, in_dev, row_bytes, true, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s, indiv)) return 1;
+  if (c.begin(3, std::min(std::max(cap, row_tiles_max * kPwPairs * slot_bytes), (size_t)c.g.nb * row_tiles_max * kPwPairs * slot_bytes), nullptr, kPwMaxIndiv,
+              "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", "%s: at most %ld SNPs per call")) return 1;
+  const XGeom &g = c.g;
+  hipStream_t s = c.s;
+  const int ndiag = c.ndiag;
+  XBuf d_scr, d_sums, d_bt;
+  if (stage_operand(plink, c.in_dev, c.row_bytes, true, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, indiv)) return 1;
   int has_missing = 1;
-  MXA_HIP(hipMemcpyAsync(&has_missing, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  MXA_HIP(hipMemcpyAsync(&has_missing, c.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
   MXA_HIP(hipStreamSynchronize(s));
   // no plane holds a 3: the FP4 engine is exact while 4 indiv < 2^24 (pick_engine's rule); MXA_XPROD_ENGINE=i8 forces int8
   bool f4 = 4 * indiv < (1L << 24);
@@ -1667,8 +1654,9 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
     if (d_sums.alloc(sizeof(int) * 2 * (size_t)g.rows_pad())) return 1;
     d_sz = (int *)d_sums.p; d_sa = d_sz + g.rows_pad();
     MXA_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int) * 2 * (size_t)g.rows_pad(), s));
-    const long chunks = std::max<long>(1, std::min<long>(g.nslabs, (1024 + g.nb - 1) / g.nb)), spc = (g.nslabs + chunks - 1) / chunks;
-    hipLaunchKernelGGL(k_pw_rowsums, dim3((unsigned)g.nb, (unsigned)((g.nslabs + spc - 1) / spc)), dim3(256), 0, s, (const uint8_t *)d_X.p, g.nslabs, spc, (long)g.nb, d_sz, d_sa);
+    long spc = 0;
+    const dim3 g_rows = rowstats_grid(g, &spc);
+    hipLaunchKernelGGL(k_pw_rowsums, g_rows, dim3(256), 0, s, c.X(), g.nslabs, spc, (long)g.nb, d_sz, d_sa);
     MXA_HIP(hipGetLastError());
   }
   const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (row_tiles_max * (size_t)pairs * slot_bytes)));
@@ -1677,41 +1665,29 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
   std::vector<int4> band;
   std::vector<size_t> band_first((size_t)ngroups + 1, 0);
   size_t group_tiles_max = 0;
-  for (int c = 0; c < ngroups; c++) {
-    band_first[(size_t)c] = band.size();
-    pairwise_group_tiles(g.nb, ndiag, c * rows_per_group, std::min(g.nb, (c + 1) * rows_per_group), pairs, prod[(size_t)c], band);
-    group_tiles_max = std::max(group_tiles_max, band.size() - band_first[(size_t)c]);
+  for (int q = 0; q < ngroups; q++) {
+    band_first[(size_t)q] = band.size();
+    pairwise_group_tiles(g.nb, ndiag, q * rows_per_group, std::min(g.nb, (q + 1) * rows_per_group), pairs, prod[(size_t)q], band);
+    group_tiles_max = std::max(group_tiles_max, band.size() - band_first[(size_t)q]);
   }
   band_first.back() = band.size();
   XTiles t;
   if (upload_tiles(std::move(prod), s, t)) return 1;
   if (d_bt.alloc(band.size() * sizeof(int4)) || d_scr.alloc(group_tiles_max * (size_t)pairs * slot_bytes)) return 1;
   MXA_HIP(hipMemcpyAsync(d_bt.p, band.data(), band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  double *d_res = out_dev ? out : (double *)d_out.p;
-  const long ld_res = out_dev ? ldb : window + 1;
-  double *d_dst = scores ? (double *)d_P.p : d_res;
-  const long ld_dst = scores ? g.rows_pad() : ld_res;
-  XEvent e0, e1;
-  if (e0.create() || e1.create()) return 1;
-  MXA_HIP(hipEventRecord(e0.e, s));
+  if (c.start()) return 1;
   const XPost none{};
-  for (int c = 0; c < ngroups; c++) {
+  for (int q = 0; q < ngroups; q++) {
     // the products of the group into the scratch, then its combine, one behind the other on the call's stream (the next group reuses the scratch)
-    if (t.launch(c, g, f4, s, (const uint8_t *)d_X.p, (double *)d_scr.p, 0, 0, nullptr, 5, none)) return 1;
-    const dim3 grid((unsigned)(band_first[(size_t)c + 1] - band_first[(size_t)c]));
-    const int4 *bt = (const int4 *)d_bt.p + band_first[(size_t)c];
-    auto combine = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, d_dst, ld_dst, window, flag); };
-    if (scores) { if (dense) combine(k_ld_pw_combine<4, true>); else combine(k_ld_pw_combine<4, false>); }
-    else { if (dense) combine(k_ld_pw_combine<3, true>); else combine(k_ld_pw_combine<3, false>); }
+    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
+    const dim3 grid((unsigned)(band_first[(size_t)q + 1] - band_first[(size_t)q]));
+    const int4 *bt = (const int4 *)d_bt.p + band_first[(size_t)q];
+    auto combine = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, c.d_dst, c.ld_dst, window, flag); };
+    if (scores) { if (dense) combine(k_ld_pw_combine<kPostLdScores, true>); else combine(k_ld_pw_combine<kPostLdScores, false>); }
+    else { if (dense) combine(k_ld_pw_combine<kPostLdBand, true>); else combine(k_ld_pw_combine<kPostLdBand, false>); }
     MXA_HIP(hipGetLastError());
   }
-  if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
-  else if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
-  MXA_HIP(hipGetLastError());
-  MXA_HIP(hipEventRecord(e1.e, s));
-  if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
-  MXA_HIP(hipStreamSynchronize(s));   // tile lists / scratch lifetime
-  MXA_HIP(profile_launch(e0, e1));
+  if (c.finish()) return 1;
   debug_info("%s: %d group(s) of %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, rows_per_group, pairs, dense ? "six counts" : "no missing code: per-SNP sums",
              f4 ? "FP4" : "int8");
   return 0;
@@ -1759,7 +1735,7 @@ extern "C" int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, 
       mxa::tl_xprod_shared_device = ndev > 0 && parts > ndev;   // worker threads are pooled: set on every job
       const long c0 = std::min<long>(indiv, nb * g / parts * mxa::kXT), c1 = std::min<long>(indiv, nb * (g + 1) / parts * mxa::kXT);
       if (c1 <= c0) return 0;
-      return mxa::crossprod_any(snp_matrix, snps, indiv, ans + (size_t)c0 * indiv, is_plink_format, 0, 0, nullptr, c0, c1, false, indiv, dev);
+      return mxa::crossprod_any(snp_matrix, snps, indiv, ans + (size_t)c0 * indiv, is_plink_format, mxa::kPostNone, 0, nullptr, c0, c1, false, indiv, dev);
     });
   }
   return mxa::crossprod_any(snp_matrix, snps, indiv, ans, is_plink_format);
@@ -1768,17 +1744,17 @@ extern "C" int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, 
 extern "C" int mxa_snp_multiply_panel(const unsigned char *snp_matrix, int snps, int indiv, int col_begin, int col_end, int upper_only, double *panel,
                                       long ld, int is_plink_format) {
   mxa::clear_error();
-  return mxa::crossprod_any(snp_matrix, snps, indiv, panel, is_plink_format != 0, 0, 0, nullptr, col_begin, col_end, upper_only != 0, ld);
+  return mxa::crossprod_any(snp_matrix, snps, indiv, panel, is_plink_format != 0, mxa::kPostNone, 0, nullptr, col_begin, col_end, upper_only != 0, ld);
 }
 
 extern "C" int mxa_grm(const unsigned char *plink_transposed, int snps, int indiv, double *G, int is_plink_format, int do_scale, const double *allele_freq) {
   mxa::clear_error();
   if (do_scale && !allele_freq) { mxa::set_error(1, "mxa_grm: allele frequencies are required when do_scale is set"); return 1; }
-  return mxa::crossprod_any(plink_transposed, snps, indiv, G, is_plink_format != 0, 1, do_scale, allele_freq);
+  return mxa::crossprod_any(plink_transposed, snps, indiv, G, is_plink_format != 0, mxa::kPostGrm, do_scale, allele_freq);
 }
 
 extern "C" int mxa_ld(const unsigned char *plink, int snps, int indiv, double *R, int is_plink_format, const double *allele_freq) {
   mxa::clear_error();
   if (!allele_freq) { mxa::set_error(1, "mxa_ld: allele frequencies are required"); return 1; }
-  return mxa::crossprod_any(plink, indiv, snps, R, is_plink_format != 0, 2, 0, allele_freq);
+  return mxa::crossprod_any(plink, indiv, snps, R, is_plink_format != 0, mxa::kPostLd, 0, allele_freq);
 }

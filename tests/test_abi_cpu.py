@@ -192,20 +192,28 @@ def test_planner_sweep_host_build():
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-2000:]
 
 
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+def _gfx950_code_object(obj_name, tmp_path):
+    """the gfx950 code object bundled in an object file of the library's build"""
+    obj = os.path.join(ROOT, "miraculix_amd", "lib", obj_name)
+    if not os.path.exists(obj):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "miraculix_amd", "csrc"), "-j4"])
+    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "dev.co")
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}", "--unbundle"])
+    return co
+
+
 def test_kernels_with_hand_counted_vmcnt_have_no_scratch_traffic(built, tmp_path):
     """k_gemm_i8_tn waits for its LDS DMA with hand-written `s_waitcnt vmcnt(N)` that count only what the source issues.  A register the compiler spills in
     such a kernel is scratch traffic on the same counter: the compiler then adds its own waits, counted WITHOUT the DMA it cannot see, and one of them in the
     stage loop serialises the ring (round 6: digit registers that lived across the epilogue were spilled -- 84..136 bytes of scratch per lane -- and the
     two-tile instantiation ran 1.86 ms where 1.45 had been measured; nothing failed, only the clock).  The code object's metadata states what was spilled:
     at most 16 bytes of scratch per lane and 4 spilled registers are allowed here (two address registers of the prologue), none in the one-tile form."""
-    obj = os.path.join(ROOT, "miraculix_amd", "lib", "mxa_gemm_i8.o")
-    if not os.path.exists(obj):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "miraculix_amd", "csrc"), "-j4"])
-    llvm = "/opt/rocm/lib/llvm/bin"
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "dev.co")
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}", "--unbundle"])
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    co = _gfx950_code_object("mxa_gemm_i8.o", tmp_path)
+    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     seen = 0
     for block in notes.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
@@ -217,6 +225,28 @@ def test_kernels_with_hand_counted_vmcnt_have_no_scratch_traffic(built, tmp_path
         one_tile = "ILi4ELi1E" in name
         assert scratch <= (0 if one_tile else 16) and spilled <= (0 if one_tile else 4), (name, scratch, spilled)
     assert seen == 2
+
+
+def test_crossproduct_kernels_have_no_scratch_access_inside_the_mfma_range(built, tmp_path):
+    """The k_crossprod_* kernels count their LDS DMA with hand-written `s_waitcnt vmcnt(N)` too, and they do spill: 256 accumulator registers leave the prologue
+    and the epilogues (the window epilogue of the LD band / scores most of all) short of registers.  That is harmless exactly as long as no spill or reload
+    lies between the first and the last MFMA, i.e. inside the stage loop, where a scratch access would join the DMA on the vmcnt counter and bring the
+    compiler's own waits with it.  Disassembly of the built code object: every instantiation has MFMAs, and no scratch_ instruction between its first and
+    its last one."""
+    co = _gfx950_code_object("mxa_crossprod.o", tmp_path)
+    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], capture_output=True, text=True, check=True).stdout
+    seen = 0
+    for block in re.split(r"^[0-9a-f]+ <", dis, flags=re.M)[1:]:
+        name, body = block.split(">:", 1)
+        if "k_crossprod" not in name:
+            continue
+        ops = [ln.split()[0] for ln in body.splitlines() if ln.startswith("\t")]
+        mfma = [i for i, op in enumerate(ops) if op.startswith("v_mfma")]
+        assert mfma, name
+        inside = [i for i, op in enumerate(ops) if op.startswith("scratch_") and mfma[0] < i < mfma[-1]]
+        assert not inside, (name, len(inside))
+        seen += 1
+    assert seen == 26          # f4: 6 kinds + DIAG, i8: 6 + DIAG, gang: 2 engines x 6 kinds
 
 
 def test_reference_fortran_programs_bind_only_symbols_this_library_exports(built):

@@ -345,6 +345,39 @@ int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, d
 int mxa_ld_band_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind);
 int mxa_ld_scores_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust);
 
+/* Windowed LD by distance: windows in base pairs or centimorgans that stop at chromosome ends, for a whole genome in one call.  The window is data: an array
+ * `last` of snps ints with i <= last[i] < snps and last[i] <= last[i+1]; SNP j >= i is in the window of i iff j <= last[i].  The relation is symmetric by
+ * construction (the score of j counts i < j iff j <= last[i]) and covers bp, cM and SNP-count windows and chromosome breaks alike.
+ *
+ * mxa_ld_window_bounds (host only, no device needed; O(snps), a two-pointer sweep): last[i] = the largest j >= i with chrom[j] == chrom[i],
+ *   pos[j] - pos[i] <= max_dist (ONE rounded fp64 subtraction, inclusive comparison) and j - i <= max_snps.  chrom == NULL: one chromosome; pos == NULL: no
+ *   distance bound (max_snps >= 0 is then required); max_snps < 0: no SNP bound.  rowptr (optional, snps + 1 longs): the exclusive prefix sum of
+ *   last[i] - i + 1, so rowptr[snps] is the number of entries mxa_ld_window_rows stores.  Returns 1 (mxa_last_error() == 1, outputs untouched) for snps <= 0,
+ *   last == NULL, max_dist negative or NaN, a NaN position, a position that decreases inside a chromosome, a chromosome code that returns after another one
+ *   (chromosomes must be contiguous), neither bound given.
+ *
+ * The four device entries take `last` (host or device pointer, like every pointer here; it is copied to the host, checked, and the tile plan made from it):
+ * mxa_ld_window_rows  : ragged rows, rows[rowptr[i] + d] = R(i, i + d) for 0 <= d <= last[i] - i, rowptr as above (formed by the entry; the caller allocates
+ *                       rowptr[snps] doubles).  No zero fill, no leading dimension, nothing written beyond rowptr[snps]: a dense region with a reach of 20 000
+ *                       SNPs costs its own rows only.  kind 0: r, 1: r * r (one rounding).
+ * mxa_ld_window_scores: scores[i] = sum of t(r_ij) over first[i] <= j <= last[i], first[i] = min{k : last[k] >= i}; t and adjust as mxa_ld_scores.
+ * mxa_ld_window_rows_pairwise, mxa_ld_window_scores_pairwise: the same from the pairwise-complete r of mxa_ld_band_pairwise (per-pair N_ij in the adjusted
+ *                       term; MXA_LD_PAIRWISE_SCRATCH_MB bounds the count scratch of a group of consecutive tile rows, one tile row at least; the results do
+ *                       not depend on it; the missing-free shortcut and MXA_LD_PAIRWISE_DENSE as there).
+ * R, the terms, kind, adjust and the NaN behaviour are those of the fixed entries: the same kernels, engines, map and store, with the window read from
+ * last[] instead of one number.  Tile row I holds the 256 x 256 tiles (I, J), I <= J <= last[min(256 I + 255, snps - 1)] / 256.  With
+ * last[i] = min(i + w, snps - 1) this is the tile set and the summation order of the fixed entries: rows and scores are the same bits as theirs.
+ * Errors (return 1, mxa_last_error() == 1, output untouched): NULL pointers, last out of range or decreasing, kind / adjust not 0 or 1, adjust with
+ * indiv < 3, the fixed entries' snps and indiv bounds, allele_freq == NULL on the plain route; 12: not enough device memory (last, rowptr and the scores'
+ * partial buffer are counted).  Runs on the selected device (no MIRACULIX_NUM_GPUS sharding). */
+int mxa_ld_window_bounds(int snps, const double *pos, const int *chrom, double max_dist, int max_snps, int *last, long *rowptr);
+int mxa_ld_window_rows(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind, int is_plink_format,
+                       const double *allele_freq);
+int mxa_ld_window_scores(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust, int is_plink_format,
+                         const double *allele_freq);
+int mxa_ld_window_rows_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind);
+int mxa_ld_window_scores_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -16,6 +16,7 @@ module modmiraculix_amd
  public :: mxa_plink2compressed_begin, mxa_plink2compressed_rows, mxa_plink2compressed_end
  public :: mxa_ld_band, mxa_ld_scores
  public :: mxa_ld_band_pairwise, mxa_ld_scores_pairwise
+ public :: mxa_ld_window_bounds, mxa_ld_window_rows, mxa_ld_window_scores, mxa_ld_window_rows_pairwise, mxa_ld_window_scores_pairwise
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -158,6 +159,42 @@ module modmiraculix_amd
    import c_int, c_ptr
    type(c_ptr), value, intent(in) :: plink, scores
    integer(c_int), value, intent(in) :: snps, indiv, window, adjust
+   integer(c_int) :: rc
+  end function
+
+  ! windows by distance: the window of SNP i (0-based) ends at last(i + 1), i <= last <= snps - 1, non-decreasing.  mxa_ld_window_bounds (host only) makes
+  ! last -- and rowptr, snps + 1 C longs, the exclusive prefix sum of last(i + 1) - i + 1 -- from positions (base pairs or centimorgans; c_null_ptr: none),
+  ! chromosome codes (c_null_ptr: one chromosome), max_dist and max_snps (< 0: none).  rows(rowptr(i + 1) + d + 1) = R(i, i + d), 0 <= d <= last(i + 1) - i;
+  ! scores as mxa_ld_scores over the window; the _pairwise pair on data with missing genotypes.  last: host or device, c_loc of integer(c_int).
+  function mxa_ld_window_bounds(snps, pos, chrom, max_dist, max_snps, last, rowptr) bind(C, name='mxa_ld_window_bounds') result(rc)
+   import c_int, c_double, c_ptr
+   integer(c_int), value, intent(in) :: snps, max_snps
+   type(c_ptr), value, intent(in) :: pos, chrom, last, rowptr
+   real(c_double), value, intent(in) :: max_dist
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_rows(plink, snps, indiv, last, rows, kind, is_plink_format, allele_freq) bind(C, name='mxa_ld_window_rows') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, rows, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, kind, is_plink_format
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_scores(plink, snps, indiv, last, scores, adjust, is_plink_format, allele_freq) bind(C, name='mxa_ld_window_scores') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, scores, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, adjust, is_plink_format
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_rows_pairwise(plink, snps, indiv, last, rows, kind) bind(C, name='mxa_ld_window_rows_pairwise') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, rows
+   integer(c_int), value, intent(in) :: snps, indiv, kind
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_scores_pairwise(plink, snps, indiv, last, scores, adjust) bind(C, name='mxa_ld_window_scores_pairwise') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, scores
+   integer(c_int), value, intent(in) :: snps, indiv, adjust
    integer(c_int) :: rc
   end function
 

@@ -184,3 +184,115 @@ def ld_scores_pairwise(plink, snps, indiv, window, adjust=False):
     S = _zeros_like(plink, snps)
     _check(L.mxa_ld_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), int(window), _lib.ptr(S), int(bool(adjust))), "mxa_ld_scores_pairwise")
     return S
+
+
+# ---- windowed LD by distance: C entries mxa_ld_window_bounds (host only) and mxa_ld_window_rows / _scores / _rows_pairwise / _scores_pairwise.
+# The window of SNP i is [i, last[i]] (and, by symmetry, every k < i with last[k] >= i); last is non-decreasing with i <= last[i] < snps.
+def ld_window_bounds(pos, chrom=None, max_dist=None, max_snps=None, snps=None):
+    """Additive (C entry mxa_ld_window_bounds; no device needed): (last, rowptr) of a window by distance.  last[i] is the largest j >= i on i's chromosome
+    with pos[j] - pos[i] <= max_dist and j - i <= max_snps; rowptr is the exclusive prefix sum of last[i] - i + 1 (int64, snps + 1 long).  pos: base pairs or
+    centimorgans, non-decreasing inside a chromosome (None: no distance bound; then max_snps is required and `snps`, or chrom, gives the length); chrom: int
+    codes, contiguous (None: one chromosome); max_snps None: no SNP bound."""
+    if pos is not None:
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        n = len(pos)
+        if max_dist is None:
+            raise ValueError("max_dist is required with pos")
+    else:
+        n = len(chrom) if chrom is not None else snps
+        if n is None:
+            raise ValueError("without pos, snps (or chrom) gives the number of SNPs")
+    if chrom is not None:
+        chrom = np.ascontiguousarray(chrom, dtype=np.int32)
+        if len(chrom) != n:
+            raise ValueError(f"chrom needs one code per SNP: {len(chrom)} for {n}")
+    L = _lib.check_library_handle()
+    last = np.zeros(max(int(n), 0), dtype=np.int32)
+    rowptr = np.zeros(max(int(n), 0) + 1, dtype=np.int64)
+    _check(L.mxa_ld_window_bounds(int(n), _lib.ptr(pos), _lib.ptr(chrom), 0.0 if pos is None else float(max_dist), -1 if max_snps is None else int(max_snps),
+                                  _lib.ptr(last), _lib.ptr(rowptr)), "mxa_ld_window_bounds")
+    return last, rowptr
+
+
+def ld_window_tiles(last):
+    """The tile plan of the entries over `last`, restated: tile row I holds the tiles (I, J), I <= J <= jmax[I] = last[min(256 I + 255, snps - 1)] // 256 -- last
+    is non-decreasing, so the tile row reaches as far as its last SNP does, and every listed tile holds a window element.  With last[i] = min(i + w, snps - 1)
+    this is ld_band_tiles(snps, w)."""
+    last = np.asarray(last)
+    snps = len(last)
+    nb = (snps + 255) // 256
+    return [(i, j) for i in range(nb) for j in range(i, int(last[min(256 * i + 255, snps - 1)]) // 256 + 1)]
+
+
+def _ld_last_args(plink, snps, indiv, last):
+    """(last in the form the C entry takes, number of stored entries rowptr[snps]); the host copy is checked here, the library checks again"""
+    if int(np.prod(plink.shape)) != snps * ((indiv + 3) // 4):
+        raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
+    if _lib.is_torch_tensor(last):
+        import torch
+        if last.dtype != torch.int32 or last.numel() != snps:
+            raise ValueError(f"last needs to be {snps} int32 values")
+        h = last.cpu().numpy()
+        last = last.contiguous()
+    else:
+        h = last = np.ascontiguousarray(last, dtype=np.int32)
+        if last.shape != (snps,):
+            raise ValueError(f"last needs to be {snps} int32 values")
+    i = np.arange(snps)
+    if np.any(h < i) or np.any(h >= snps) or np.any(np.diff(h) < 0):
+        raise ValueError("last needs i <= last[i] < snps, non-decreasing")
+    return last, int((h.astype(np.int64) - i + 1).sum())
+
+
+def ld_window_rows(plink, snps, indiv, last, kind="r", is_plink_format=False, allele_freq=None):
+    """Additive (C entry mxa_ld_window_rows): the entries R(i, i + d), 0 <= d <= last[i] - i, of ld()'s R as ragged rows: a flat array of rowptr[snps] values
+    with out[rowptr[i] + d] = R(i, i + d) (rowptr as ld_window_bounds returns it).  No padding to the widest window.  kind "r" or "r2"."""
+    if kind not in ("r", "r2"):
+        raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+    if allele_freq is None or len(allele_freq) != snps:
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    last, total = _ld_last_args(plink, snps, indiv, last)
+    f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+    L = _lib.check_library_handle()
+    B = _zeros_like(plink, total)
+    _check(L.mxa_ld_window_rows(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), _lib.ptr(B), 1 if kind == "r2" else 0, int(bool(is_plink_format)), _lib.ptr(f)),
+           "mxa_ld_window_rows")
+    return B
+
+
+def ld_window_scores(plink, snps, indiv, last, adjust=False, is_plink_format=False, allele_freq=None):
+    """Additive (C entry mxa_ld_window_scores): ld_scores() over the window `last`: l_i = sum of t(r_ij) over first[i] <= j <= last[i], first[i] = the smallest k
+    with last[k] >= i.  Shape (snps,); fixed summation order (bitwise reproducible)."""
+    if allele_freq is None or len(allele_freq) != snps:
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    if adjust and indiv < 3:
+        raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
+    last, _ = _ld_last_args(plink, snps, indiv, last)
+    f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+    L = _lib.check_library_handle()
+    S = _zeros_like(plink, snps)
+    _check(L.mxa_ld_window_scores(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), _lib.ptr(S), int(bool(adjust)), int(bool(is_plink_format)), _lib.ptr(f)),
+           "mxa_ld_window_scores")
+    return S
+
+
+def ld_window_rows_pairwise(plink, snps, indiv, last, kind="r"):
+    """Additive (C entry mxa_ld_window_rows_pairwise): ld_window_rows() from the pairwise-complete r of ld_band_pairwise() (PLINK data with missing genotypes)."""
+    if kind not in ("r", "r2"):
+        raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+    last, total = _ld_last_args(plink, snps, indiv, last)
+    L = _lib.check_library_handle()
+    B = _zeros_like(plink, total)
+    _check(L.mxa_ld_window_rows_pairwise(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), _lib.ptr(B), 1 if kind == "r2" else 0), "mxa_ld_window_rows_pairwise")
+    return B
+
+
+def ld_window_scores_pairwise(plink, snps, indiv, last, adjust=False):
+    """Additive (C entry mxa_ld_window_scores_pairwise): ld_window_scores() from the pairwise-complete r, the adjustment with the pair's own N_ij."""
+    if adjust and indiv < 3:
+        raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
+    last, _ = _ld_last_args(plink, snps, indiv, last)
+    L = _lib.check_library_handle()
+    S = _zeros_like(plink, snps)
+    _check(L.mxa_ld_window_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), _lib.ptr(S), int(bool(adjust))), "mxa_ld_window_scores_pairwise")
+    return S

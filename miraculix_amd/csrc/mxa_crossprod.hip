@@ -145,6 +145,8 @@ struct XPost {
   const double *scal = nullptr;   // GRM: scal[0] = sum(cs), scal[1] = 2 sum f (1 - f)
   double a = 0.0;                 // GRM: 1 / n;  LD: 4 * indiv
   int do_scale = 0;
+  const int *last = nullptr;      // kPostLdBand, kPostLdScores: the general window's ends last[] (LdVarWindow; nullptr: the fixed window) ...
+  const long *rowptr = nullptr;   // ... and the row starts of its ragged storage; read by no other instantiation
 };
 // The two divisions of the reference (by the scalar c, by sigma_i and sigma_j) are multiplications by reciprocals formed once (<= 1 ulp from the
 // quotient; the stated tolerance of this path is 1e-12): an fp64 division is ~15 instructions on the pipe the epilogue shares with nothing else.
@@ -177,14 +179,36 @@ __device__ __forceinline__ void xstore(double *p, double v) {
   *p = v;
 #endif
 }
-// ---- windowed LD (mxa_ld_band, mxa_ld_scores): the LD map of kPostLd on the tiles of a band, written as band storage (kPostLdBand) or reduced to per-SNP
-// scores (kPostLdScores).  These two instantiations reuse the kernels' arguments instead of widening XPost (the other instantiations keep their code object
-// byte for byte): ans = the band / the partial buffer P, ld = its leading dimension ldb / the row stride of P, c0 = the window, post.do_scale = kind / adjust.
-// The window predicate, in one place: element (i, j), i <= j, of R belongs to the band.  A per-SNP bound (base pairs, centimorgans) replaces `window` here.
-__device__ __forceinline__ bool ld_in_window(long i, long j, long window) { return j - i <= window; }
+// ---- windowed LD (mxa_ld_band, mxa_ld_scores; by distance: mxa_ld_window_rows, mxa_ld_window_scores): the LD map of kPostLd on the tiles of a window,
+// written as band storage or ragged rows (kPostLdBand), or reduced to per-SNP scores (kPostLdScores).  These two instantiations reuse the kernels' arguments:
+// ans = the band / the rows / the partial buffer P, ld = its leading dimension ldb / the row stride of P, c0 = the window, post.do_scale = kind / adjust.
+// The general window arrives in post.last and post.rowptr (c0 = the ndiag of P then); post.last == nullptr is the fixed window: one wave-uniform branch.
 // tile diagonals dt = J - I a window touches: tile (I, J) holds the offsets j - i in [256 dt - 255, 256 dt + 255], so it meets the band iff
 // 256 dt - 255 <= window, i.e. dt <= (window + 255) / 256 = ceil(window / 256) -- one more diagonal than window / 256 unless the window ends on a tile edge
 __host__ __device__ __forceinline__ int ld_band_diagonals(long window) { return (int)((window + 255) / 256); }
+// The window, in one place, as a small object with two instances.  in(i, j): element (i, j), i <= j < n, of R belongs to the window of i; beyond(i_base, j_base, n),
+// wave-uniform: no row of the 32-row sub-block that starts at row i_base reaches column j_base >= i_base (i_base or j_base may lie in the padding at or
+// beyond n: nothing is indexed out of range); at(gi, gj, ld): where row gi stores its element gj; ndiag(): tile diagonals in the scores' partial buffer.
+// Fixed (mxa_ld_band, mxa_ld_scores and the pairwise pair): `window` SNPs on each side; the band band[(gj - gi) + gi * ld].
+struct LdFixedWindow {
+  long window;
+  __device__ __forceinline__ bool in(long i, long j) const { return j - i <= window; }
+  __device__ __forceinline__ bool beyond(long i_base, long j_base, long) const { return !in(i_base + 31, j_base); }
+  __device__ __forceinline__ size_t at(long gi, long gj, long ld) const { return (size_t)(gj - gi) + (size_t)gi * ld; }
+  __device__ __forceinline__ int ndiag() const { return ld_band_diagonals(window); }
+};
+// General (mxa_ld_window_*): j is in the window of i <= j iff j <= last[i], with i <= last[i] < n non-decreasing (base pairs, centimorgans, SNP counts and
+// chromosome ends alike: mxa_ld_window_bounds); ragged rows rows[(gj - gi) + rowptr[gi]], rowptr = the exclusive prefix sum of last[i] - i + 1.  A sub-block
+// is judged by its last row below n (last is non-decreasing); with i_base >= n that is row n - 1, whose last[n - 1] = n - 1 < i_base <= j_base.
+struct LdVarWindow {
+  const int *__restrict__ last;
+  const long *__restrict__ rowptr;
+  int nd;
+  __device__ __forceinline__ bool in(long i, long j) const { return j <= (long)last[i]; }
+  __device__ __forceinline__ bool beyond(long i_base, long j_base, long n) const { return j_base > (long)last[min(i_base + 31, n - 1)]; }
+  __device__ __forceinline__ size_t at(long gi, long gj, long) const { return (size_t)(gj - gi) + (size_t)rowptr[gi]; }
+  __device__ __forceinline__ int ndiag() const { return nd; }
+};
 // partial buffer of the scores: P[side][dt][row], side 0 = the tile's I rows (sums over gj), side 1 = its J rows (sums over gi; off the diagonal only)
 __host__ __device__ __forceinline__ size_t ld_score_slot(int side, int dt, int ndiag, long stride) { return ((size_t)side * (size_t)(ndiag + 1) + (size_t)dt) * (size_t)stride; }
 constexpr int kXScratchBytes = 4 * 32 * 33 * 8;   // the four waves' 32 x 33 epilogue scratch; the score reduction area lies behind it
@@ -193,13 +217,13 @@ constexpr int kXScratchBytes = 4 * 32 * 33 * 8;   // the four waves' 32 x 33 epi
 // crossproduct kernels (xprod_store_window below) and the combine kernel of the pairwise-complete entries (k_ld_pw_combine) alike: prep(a, b) readies the
 // lane's sub-block (a, b); val(a, b, r) is what goes to the LDS scratch for the element that accumulator register r of that sub-block holds in the crossproduct
 // kernels; fin(v, i, j) finishes a value read back from the scratch into the band entry (kPostLdBand; squared: v * v is stored) or the score term
-// (kPostLdScores) of element (i, j), i, j < n.
-template <int POST, typename Prep, typename Val, typename Fin>
-__device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0, long n,
-                                                double *__restrict__ out, long ld, long window) {
+// (kPostLdScores) of element (i, j), i, j < n.  SCORES: the reduction, else the store; win: the window object (LdFixedWindow, LdVarWindow).
+template <bool SCORES, typename Win, typename Prep, typename Val, typename Fin>
+__device__ __forceinline__ void ld_window_store(const Win win, Prep prep, Val val, Fin fin, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0,
+                                                long n, double *__restrict__ out, long ld) {
   double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
   const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
-  if constexpr (POST == kPostLdBand) {
+  if constexpr (!SCORES) {
     // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
 #pragma unroll
     for (int a = 0; a < 4; a++)
@@ -207,7 +231,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
       for (int b = 0; b < 4; b++) {
         const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
         const long gj = gj_base + col;
-        if (gj_base + 31 < gi_base || !ld_in_window(gi_base + 31, gj_base, window)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
+        if (gj_base + 31 < gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
         prep(a, b);
 #pragma unroll
         for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
@@ -216,9 +240,9 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
           for (int r = 0; r < 16; r++) {
             const int row = (r & 3) + 8 * (r >> 2) + rq;
             const long gi = gi_base + row;
-            if (gi <= gj && ld_in_window(gi, gj, window)) {
+            if (gi <= gj && win.in(gi, gj)) {
               const double v = fin(scratch[row * 33 + col], gj, gi);
-              xstore(&out[(size_t)(gj - gi) + (size_t)gi * ld], squared ? v * v : v);
+              xstore(&out[win.at(gi, gj, ld)], squared ? v * v : v);
             }
           }
         }
@@ -235,7 +259,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
         const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
         const long gj = gj_base + col, gi = gi_base + col;
         // wave-uniform: no element of the sub-block is within the window (on the diagonal tile both triangles count: |gj - gi| <= window)
-        if (gj_base >= gi_base ? !ld_in_window(gi_base + 31, gj_base, window) : !ld_in_window(gj_base + 31, gi_base, window)) continue;
+        if (gj_base >= gi_base ? win.beyond(gi_base, gj_base, n) : win.beyond(gj_base, gi_base, n)) continue;
         prep(a, b);
 #pragma unroll
         for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
@@ -243,7 +267,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
 #pragma unroll
           for (int r = 0; r < 16; r++) {
             const int row = (r & 3) + 8 * (r >> 2) + rq;
-            if (ld_in_window(gi_base + row, gj, window)) colacc[b] += fin(scratch[row * 33 + col], gj, gi_base + row);
+            if (win.in(gi_base + row, gj)) colacc[b] += fin(scratch[row * 33 + col], gj, gi_base + row);
           }
         }
         if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
@@ -251,7 +275,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
           for (int it = 0; it < 16; it++) {
             const int cc = 2 * it + hh;
             const long gjj = gj_base + cc;
-            if (gjj < n && ld_in_window(min(gi, gjj), max(gi, gjj), window)) rowacc[a] += fin(scratch[col * 33 + cc], gi, gjj);
+            if (gjj < n && win.in(min(gi, gjj), max(gi, gjj))) rowacc[a] += fin(scratch[col * 33 + cc], gi, gjj);
           }
         }
       }
@@ -262,7 +286,7 @@ __device__ __forceinline__ void ld_window_store(Prep prep, Val val, Fin fin, boo
       red[(((1 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = colacc[q];
     }
     __syncthreads();
-    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = ld_band_diagonals(window);
+    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = win.ndiag();
     auto slot = [&](int side, int w) { return red[(((side * 4 + w) * 2 + 0) * 4 + q) * 32 + c] + red[(((side * 4 + w) * 2 + 1) * 4 + q) * 32 + c]; };
     out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
     if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
@@ -277,17 +301,24 @@ __device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char
   constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
   const bool flag = post.do_scale != 0;                                    // kind (band) / adjust (scores)
   // post.a = 4 indiv: 1 / (indiv - 2).  Formed here and not inside fin: there the gang kernels spill 648 / 764 bytes per lane (FP4 / int8) instead of 432 / 492
-  const double inv_adj = POST == kPostLdScores && flag ? 1.0 / (post.a * 0.25 - 2.0) : 0.0;
+  constexpr bool kScores = POST == kPostLdScores;
+  const double inv_adj = kScores && flag ? 1.0 / (post.a * 0.25 - 2.0) : 0.0;
   auto fin = [&](double v, long i, long j) -> double {
     const double r = ld_scale_map(ld_center_map(v, post.u[i], post.u[j], post.a), post.w[i], post.w[j]);
-    if constexpr (POST == kPostLdBand) return r;
+    if constexpr (!kScores) return r;
     else {                                                                 // every operation rounded on its own (no contraction): the tests restate this line
       const double r2 = __dmul_rn(r, r);
       return flag ? __dsub_rn(r2, __dmul_rn(__dsub_rn(1.0, r2), inv_adj)) : r2;
     }
   };
-  ld_window_store<POST>([](int, int) {}, [&](int a, int b, int r) -> double { return (double)acc[a][b][r] * scale; }, fin, POST == kPostLdBand && flag, smem, wave, lane,
-                        wi, wj, i0, j0, n, out, ld, window);
+  auto store = [&](auto win) {
+    ld_window_store<kScores>(win, [](int, int) {}, [&](int a, int b, int r) -> double { return (double)acc[a][b][r] * scale; }, fin, !kScores && flag, smem, wave, lane,
+                             wi, wj, i0, j0, n, out, ld);
+  };
+  // Both instances of the store side by side behind one wave-uniform test of a kernel argument (post.last == nullptr: the fixed window); for the general one
+  // `window` carries the partial buffer's ndiag.  (Choosing per sub-block instead, around the loops over the LDS scratch, puts scratch accesses into the stage loop.)
+  if (post.last) store(LdVarWindow{post.last, post.rowptr, (int)window});
+  else store(LdFixedWindow{window});
 }
 
 // Count store (kPostCounts, pairwise-complete LD): the raw accumulators of the tile as int32 (FP4 engine: acc x 4, exact) into the scratch slot the tile entry
@@ -318,7 +349,7 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
   double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);   // the DMA ring is dead after the last barrier
   const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
   constexpr double scale = __is_same(AccT, v16f) ? 4.0 : 1.0;
-  if constexpr (POST == kPostLdBand || POST == kPostLdScores) {   // windowed LD: band storage / scores (ans, ld, c0 = band or partial buffer, its stride, the window)
+  if constexpr (POST == kPostLdBand || POST == kPostLdScores) {   // windowed LD: band or row storage / scores (ans, ld, c0 = band or partial buffer, its stride, the window)
     xprod_store_window<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, n, ans, ld, c0, post);
   } else if constexpr (POST == kPostNone) {
 #pragma unroll
@@ -841,12 +872,13 @@ static std::vector<int4> row_tiles(int nb, int i0, int i1) {
   return tiles;
 }
 
-// The tiles of the band of `ndiag` tile diagonals above the main one (ld_band_diagonals), tile row by tile row: (i, j), i <= j <= i + ndiag.  A tile row is
-// compact (ndiag + 1 neighbours that share row block i), which is what gang_order_tiles wants: a gang of 32 tiles is cut from four adjacent tile rows.
-static std::vector<int4> band_tiles(int nb, int ndiag) {
+// The tiles of a window, tile row by tile row: (i, j), i <= j <= jmax[i] (LdWindow::plan: a band of ld_band_diagonals tile diagonals, or the reach of the
+// tile row's last SNP).  A tile row is compact (neighbours that share row block i), which is what gang_order_tiles wants: a gang of 32 tiles is cut from
+// four adjacent tile rows.
+static std::vector<int4> window_tiles(const std::vector<int> &jmax) {
   std::vector<int4> tiles;
-  for (int i = 0; i < nb; i++)
-    for (int j = i; j < std::min(nb, i + ndiag + 1); j++) tiles.push_back(make_int4(i, j, 1, 0));
+  for (int i = 0; i < (int)jmax.size(); i++)
+    for (int j = i; j <= jmax[(size_t)i]; j++) tiles.push_back(make_int4(i, j, 1, 0));
   return tiles;
 }
 
@@ -1397,20 +1429,22 @@ __global__ void __launch_bounds__(256) k_ld_band_tail(double *__restrict__ band,
   const long i = n - 1 - (long)blockIdx.x;                    // blockIdx.x < window < n
   for (long d = n - i + threadIdx.x; d <= window; d += 256) band[(size_t)d + (size_t)i * ldb] = 0.0;
 }
-// scores[i] = the slots of row i in a fixed order: the I side of the tiles (I, I + dt), then the J side of the tiles (I - dt, I); a slot exists iff its tile does
-__global__ void __launch_bounds__(256) k_ld_score_finish(const double *__restrict__ P, long n, long stride, int nb, int ndiag, double *__restrict__ scores) {
+// scores[i] = the slots of row i in a fixed order: the I side of the tiles (I, I + dt), then the J side of the tiles (I - dt, I); a slot exists iff its tile
+// does, and tile row I holds the tiles up to column jmax[I] (nb ints, non-decreasing)
+__global__ void __launch_bounds__(256) k_ld_score_finish(const double *__restrict__ P, long n, long stride, const int *__restrict__ jmax, int ndiag, double *__restrict__ scores) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int I = (int)(i / kXT);
   double s = 0.0;
-  for (int dt = 0; dt <= ndiag; dt++) if (I + dt < nb) s += P[ld_score_slot(0, dt, ndiag, stride) + (size_t)i];
-  for (int dt = 1; dt <= ndiag; dt++) if (I - dt >= 0) s += P[ld_score_slot(1, dt, ndiag, stride) + (size_t)i];
+  for (int dt = 0; dt <= ndiag; dt++) if (I + dt <= jmax[I]) s += P[ld_score_slot(0, dt, ndiag, stride) + (size_t)i];
+  for (int dt = 1; dt <= ndiag; dt++) if (I - dt >= 0 && jmax[I - dt] >= I) s += P[ld_score_slot(1, dt, ndiag, stride) + (size_t)i];
   scores[i] = s;
 }
 
-// a host result of the windowed entries: the scores, or the compact device band (leading dimension window + 1) into the caller's band of leading dimension ldb
-static int ld_window_download(const double *d_res, size_t obytes, long snps, long window, double *out, long ldb, bool scores, hipStream_t s) {
-  if (scores || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
+// a host result of the windowed entries: the scores or the ragged rows as they are, or the compact device band (leading dimension window + 1) into the
+// caller's band of leading dimension ldb
+static int ld_window_download(const double *d_res, size_t obytes, long snps, long window, double *out, long ldb, bool compact, hipStream_t s) {
+  if (compact || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
   else {   // a wider host ldb: one download, then the rows d <= window of every column (the rows beyond stay the caller's)
     std::vector<double> h((size_t)(window + 1) * (size_t)snps);
     MXA_HIP(hipMemcpyAsync(h.data(), d_res, obytes, hipMemcpyDeviceToHost, s));
@@ -1421,60 +1455,120 @@ static int ld_window_download(const double *d_res, size_t obytes, long snps, lon
 }
 
 namespace {
-// One call of a windowed entry: everything around the route's own staging and tile launches.  begin(): the shared argument checks, the sizes, the
-// pre-flight, the stream, the operand / result / partial buffers and the events; start() and finish() enclose the launches: d_dst (leading dimension
-// ld_dst) is where they write -- the band, or the scores' partial buffer P -- and finish() turns it into the result at d_res and delivers that.
+// One call of a windowed entry: everything around the route's own staging and tile launches.  begin(): the shared argument checks, the tile plan, the sizes,
+// the pre-flight, the stream, the operand / result / partial buffers and the events; start() and finish() enclose the launches: d_dst (leading dimension
+// ld_dst) is where they write -- the band, the rows, or the scores' partial buffer P -- and finish() turns it into the result at d_res and delivers that.
+// Two ways of constructing it: the fixed window (`window` SNPs on each side; result = band of leading dimension ldb, or scores) and the general one
+// (last != nullptr: the window of SNP i ends at last[i]; result = ragged rows, or scores).  Both end in the same plan, jmax[] per tile row.
 struct LdWindow {
   const char *who;
   const unsigned char *plink;
   long snps, indiv, window;
+  const int *last;             // the caller's, host or device; nullptr: the fixed window
   double *out;
   long ldb;
   bool scores;
-  int flag;                    // kind (band) / adjust (scores)
+  int flag;                    // kind (band, rows) / adjust (scores)
   XGeom g;
   long row_bytes = 0;
-  int ndiag;
+  int ndiag = 0;               // tile diagonals of the partial buffer: the kernels' (ld_band_diagonals(window)), or max(jmax[I] - I)
+  std::vector<int> jmax;       // tile row I holds the tiles (I, I .. jmax[I])
+  size_t ntiles = 0, row_tiles_max = 0;
   bool in_dev = false, out_dev = false;
   size_t plane_bytes = 0, obytes = 0;
   XStream st;
   hipStream_t s = nullptr;
-  XBuf d_X, bounce, d_out, d_flag, d_P;
+  XBuf d_X, bounce, d_out, d_flag, d_P, d_jmax, d_last, d_rowptr;
   XEvent e0, e1;
   double *d_res = nullptr, *d_dst = nullptr;
   long ld_res = 0, ld_dst = 0;
-  LdWindow(const char *who_, const unsigned char *plink_, long snps_, long indiv_, long window_, double *out_, long ldb_, bool scores_, int flag_)
-      : who(who_), plink(plink_), snps(snps_), indiv(indiv_), window(window_), out(out_), ldb(ldb_), scores(scores_), flag(flag_), g(indiv_, snps_),
-        ndiag(ld_band_diagonals(window_)) {}
+  LdWindow(const char *who_, const unsigned char *plink_, long snps_, long indiv_, long window_, const int *last_, double *out_, long ldb_, bool scores_, int flag_)
+      : who(who_), plink(plink_), snps(snps_), indiv(indiv_), window(window_), last(last_), out(out_), ldb(ldb_), scores(scores_), flag(flag_), g(indiv_, snps_) {}
   const uint8_t *X() const { return (const uint8_t *)d_X.p; }
+  bool general() const { return last != nullptr; }
+  // the epilogue kind of the crossproduct kernels and what they take for `c0`
+  int post_kind() const { return scores ? kPostLdScores : kPostLdBand; }
+  long post_c0() const { return general() ? (long)ndiag : window; }
+  void set_post(XPost &xp) const { xp.do_scale = flag; xp.last = (const int *)d_last.p; xp.rowptr = (const long *)d_rowptr.p; }
+  std::vector<int4> tiles() const { return window_tiles(jmax); }
 
-  // planes: of the staged operand; extra_bytes: what the route allocates beyond the operand, the result and the partial buffer, for the pre-flight.
-  // The checks run in the order in which the entries have always reported them, so the two that only one route has are passed in: route_error (a complete
-  // message, or nullptr) is reported behind "bad arguments", max_indiv (0: no bound) in front of the SNP bound; adj_msg, snps_msg: the route's wording.
-  int begin(int planes, size_t extra_bytes, const char *route_error, long max_indiv, const char *adj_msg, const char *snps_msg) {
+  // The tile plan.  Fixed: the band of ndiag tile diagonals.  General: `last` is fetched (host or device pointer) and checked, rowptr formed, and tile row I
+  // reaches as far as its last SNP does (last is non-decreasing), so every tile (I, I .. jmax[I]) holds a window element.
+  int plan(std::vector<long> &h_rowptr, std::vector<int> &h_last) {
+    jmax.resize((size_t)g.nb);
+    if (!general()) {
+      ndiag = ld_band_diagonals(window);
+      for (int I = 0; I < g.nb; I++) jmax[(size_t)I] = std::min(g.nb - 1, I + ndiag);
+    } else {
+      h_last.resize((size_t)snps);
+      MXA_HIP(hipMemcpy(h_last.data(), last, sizeof(int) * (size_t)snps, hipMemcpyDefault));
+      h_rowptr.resize((size_t)snps + 1);
+      h_rowptr[0] = 0;
+      for (long i = 0; i < snps; i++) {
+        const long l = h_last[(size_t)i];
+        if (l < i || l >= snps || (i > 0 && l < h_last[(size_t)i - 1])) {
+          set_error(1, "%s: need i <= last[i] < snps, non-decreasing (last[%ld] = %ld, snps %ld)", who, i, l, snps);
+          return 1;
+        }
+        h_rowptr[(size_t)i + 1] = h_rowptr[(size_t)i] + (l - i + 1);
+      }
+      ndiag = 0;
+      for (int I = 0; I < g.nb; I++) {
+        jmax[(size_t)I] = h_last[(size_t)std::min<long>((long)I * kXT + kXT - 1, snps - 1)] / kXT;
+        ndiag = std::max(ndiag, jmax[(size_t)I] - I);
+      }
+    }
+    for (int I = 0; I < g.nb; I++) {
+      const size_t t = (size_t)(jmax[(size_t)I] - I + 1);
+      ntiles += t;
+      row_tiles_max = std::max(row_tiles_max, t);
+    }
+    return 0;
+  }
+
+  // planes: of the staged operand; extra_bytes(): what the route allocates beyond the operand, the result and the partial buffer, for the pre-flight (called
+  // once the plan stands).  The checks run in the order in which the entries have always reported them, so the two that only one route has are passed in:
+  // route_error (a complete message, or nullptr) is reported behind "bad arguments", max_indiv (0: no bound) in front of the SNP bound; adj_msg, snps_msg:
+  // the route's wording.
+  template <typename Extra>
+  int begin(int planes, Extra extra_bytes, const char *route_error, long max_indiv, const char *adj_msg, const char *snps_msg) {
     if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
     if (route_error) { set_error(1, route_error, who); return 1; }
-    if (window < 0 || window >= snps) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
+    if (!general() && (window < 0 || window >= snps)) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
     if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
-    if (!scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
+    if (!general() && !scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
     if (scores && flag && indiv < 3) { set_error(1, adj_msg, who); return 1; }
     if (max_indiv && indiv > max_indiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, max_indiv); return 1; }
     if (snps >= kXFusedMaxRows) { set_error(1, snps_msg, who, kXFusedMaxRows - 1); return 1; }
     if (select_device() < 0) return 1;
+    std::vector<long> h_rowptr;
+    std::vector<int> h_last;
+    if (plan(h_rowptr, h_last)) return 1;
     row_bytes = (indiv + 3) / 4;
     in_dev = ptr_location(plink, nullptr) == 1;
     out_dev = ptr_location(out, nullptr) == 1;
     // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
     plane_bytes = (size_t)g.rows_pad() * g.pitch();
-    obytes = sizeof(double) * (scores ? (size_t)snps : (size_t)(window + 1) * (size_t)snps);
+    obytes = sizeof(double) * (scores ? (size_t)snps : general() ? (size_t)h_rowptr.back() : (size_t)(window + 1) * (size_t)snps);
     const size_t pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
+    const size_t wbytes = sizeof(int) * (size_t)g.nb + (general() ? sizeof(int) * (size_t)snps + sizeof(long) * ((size_t)snps + 1) : 0);   // jmax, last, rowptr
     size_t free_b = 0, total_b = 0;
     MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t need = planes * plane_bytes + pbytes + extra_bytes + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
+    const size_t need = planes * plane_bytes + pbytes + wbytes + extra_bytes() + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
     if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
     if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
     s = st.s;
     if (d_X.alloc(planes * plane_bytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
+    // the plan's arrays: synchronous copies (the host vectors end with this function)
+    if (scores) {
+      if (d_jmax.alloc(sizeof(int) * (size_t)g.nb)) return 1;
+      MXA_HIP(hipMemcpy(d_jmax.p, jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice));
+    }
+    if (general()) {
+      if (d_last.alloc(sizeof(int) * (size_t)snps) || (!scores && d_rowptr.alloc(sizeof(long) * ((size_t)snps + 1)))) return 1;
+      MXA_HIP(hipMemcpy(d_last.p, h_last.data(), sizeof(int) * (size_t)snps, hipMemcpyHostToDevice));
+      if (!scores) MXA_HIP(hipMemcpy(d_rowptr.p, h_rowptr.data(), sizeof(long) * ((size_t)snps + 1), hipMemcpyHostToDevice));
+    }
     d_res = out_dev ? out : (double *)d_out.p;
     ld_res = out_dev ? ldb : window + 1;
     d_dst = scores ? (double *)d_P.p : d_res;
@@ -1483,11 +1577,11 @@ struct LdWindow {
   }
   int start() { MXA_HIP(hipEventRecord(e0.e, s)); return 0; }
   int finish() {
-    if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), g.nb, ndiag, d_res);
-    else if (window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
+    if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), (const int *)d_jmax.p, ndiag, d_res);
+    else if (!general() && window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
     MXA_HIP(hipGetLastError());
     MXA_HIP(hipEventRecord(e1.e, s));
-    if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores, s)) return 1;
+    if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores || general(), s)) return 1;
     MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
     MXA_HIP(profile_launch(e0, e1));
     return 0;
@@ -1495,11 +1589,11 @@ struct LdWindow {
 };
 }  // namespace
 
-// the plain route: the operand staged as it is, the LD map's statistics, and one launch of the band's tiles with the window epilogue
-static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag, bool is_plink,
-                         const double *freq) {
-  LdWindow c(who, plink, snps, indiv, window, out, ldb, scores, flag);
-  if (c.begin(1, 0, freq ? nullptr : "%s: allele frequencies are required", 0, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3",
+// the plain route: the operand staged as it is, the LD map's statistics, and one launch of the window's tiles with the window epilogue
+static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
+                         bool is_plink, const double *freq) {
+  LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
+  if (c.begin(1, [] { return (size_t)0; }, freq ? nullptr : "%s: allele frequencies are required", 0, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3",
               "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
   const XGeom &g = c.g;
   hipStream_t s = c.s;
@@ -1516,10 +1610,10 @@ static int ld_window_any(const char *who, const unsigned char *plink, long snps,
   XPost xp;
   XBuf stats[3];
   if (fused_post_stats(g, c.X(), indiv, kPostLd, 0, d_f, stats, s, xp)) return 1;
-  xp.do_scale = flag;                                     // kind / adjust (xprod_store_window)
+  c.set_post(xp);                                         // kind / adjust, the general window's arrays (xprod_store_window)
   XTiles t;
-  if (upload_tiles({band_tiles(g.nb, c.ndiag)}, s, t)) return 1;
-  if (c.start() || t.launch(0, g, f4, s, c.X(), c.d_dst, c.ld_dst, window, nullptr, scores ? kPostLdScores : kPostLdBand, xp)) return 1;
+  if (upload_tiles({c.tiles()}, s, t)) return 1;
+  if (c.start() || t.launch(0, g, f4, s, c.X(), c.d_dst, c.ld_dst, c.post_c0(), nullptr, c.post_kind(), xp)) return 1;
   return c.finish();
 }
 
@@ -1542,11 +1636,11 @@ __device__ __forceinline__ double pw_r(double N, double Sxy, double Sx, double S
   const double num = N * Sxy - Sx * Sy, dx = N * Sxx - Sx * Sx, dy = N * Syy - Sy * Sy;   // exact integers
   return __ddiv_rn(num, __dsqrt_rn(__dmul_rn(dx, dy)));                                    // dx dy = 0 (no shared individuals, or a SNP constant on them): 0 / 0 = NaN
 }
-// kPostLdBand: the band entry r (ld_window_store squares it for kind 1); kPostLdScores: the score term t(r) with the pair's own N, every operation rounded on its own
-template <int POST>
+// !SCORES: the stored entry r (ld_window_store squares it for kind 1); SCORES: the score term t(r) with the pair's own N, every operation rounded on its own
+template <bool SCORES>
 __device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, double Sy, double Ax, double Ay, bool adjust) {
   const double r = pw_r(N, Sxy, Sx, Sy, Ax, Ay);
-  if constexpr (POST == kPostLdBand) return r;
+  if constexpr (!SCORES) return r;
   const double r2 = __dmul_rn(r, r);
   return adjust ? __dsub_rn(r2, __ddiv_rn(__dsub_rn(1.0, r2), __dsub_rn(N, 2.0))) : r2;
 }
@@ -1554,10 +1648,11 @@ __device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, doub
 // One workgroup per band tile, the lane <-> element map of the crossproduct epilogue: thread t reads quad q of its sub-block (a, b) at slot + ((4 a + b) 4 + q) 1024 + 4 t,
 // where xprod_store_counts wrote it.  DENSE: the six counts of the tile's slots t.w .. t.w + 5.  !DENSE (no missing code in the whole matrix): slot t.w holds
 // Sxy only; M is all ones, so N = indiv and the other four are the per-SNP sums sz = sum z, sa = sum a (k_pw_rowsums) -- the same integers, hence the same bits.
-template <int POST, bool DENSE>
+// Win: the window object, by value (LdFixedWindow: the band or its scores; LdVarWindow: ragged rows or their scores).
+template <bool SCORES, bool DENSE, typename Win>
 __global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ scratch, const int4 *__restrict__ btiles, const int *__restrict__ sz, const int *__restrict__ sa,
-                                                       long n, double indiv, double *__restrict__ out, long ld, long window, int flag) {
-  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (POST == kPostLdScores ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
+                                                       long n, double indiv, double *__restrict__ out, long ld, Win win, int flag) {
+  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (SCORES ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
   const int4 t = btiles[blockIdx.x];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
   const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
@@ -1580,13 +1675,13 @@ __global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ s
     }
   };
   auto val = [&](int, int, int r) -> double {
-    if constexpr (DENSE) return pw_value<POST>((double)cnt[0][r], (double)cnt[1][r], (double)cnt[2][r], (double)cnt[3][r], (double)cnt[4][r], (double)cnt[5][r], adjust);
+    if constexpr (DENSE) return pw_value<SCORES>((double)cnt[0][r], (double)cnt[1][r], (double)cnt[2][r], (double)cnt[3][r], (double)cnt[4][r], (double)cnt[5][r], adjust);
     else {
       const long gi = gi_base + (r & 3) + 8 * (r >> 2) + rq;     // row of accumulator register r
-      return pw_value<POST>(indiv, (double)cnt[0][r], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj], adjust);
+      return pw_value<SCORES>(indiv, (double)cnt[0][r], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj], adjust);
     }
   };
-  ld_window_store<POST>(prep, val, [](double v, long, long) { return v; }, POST == kPostLdBand && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld, window);
+  ld_window_store<SCORES>(win, prep, val, [](double v, long, long) { return v; }, !SCORES && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld);
 }
 
 // per SNP row: sz = sum z (plane Z), sa = sum a (plane A) of the stacked operand, for the missing-free path.  Grid (row tiles, K chunks), thread = row of the tile
@@ -1611,12 +1706,12 @@ __global__ void __launch_bounds__(256) k_pw_rowsums(const uint8_t *__restrict__ 
   if (a) atomicAdd(sa + r, a);
 }
 
-// The plan of one group of band tile rows [i_lo, i_hi): per band tile (i, j) one entry of `band` (i, j, 1, first slot) and `pairs` entries of `prod` over the
-// stacked operand (plane_a nb + i, plane_b nb + j, 1, slot); slots are numbered from 0 within the group.  (miraculix_amd.crossproduct.ld_pairwise_tiles restates it.)
-static void pairwise_group_tiles(int nb, int ndiag, int i_lo, int i_hi, int pairs, std::vector<int4> &prod, std::vector<int4> &band) {
+// The plan of one group of window tile rows [i_lo, i_hi): per window tile (i, j <= jmax[i]) one entry of `band` (i, j, 1, first slot) and `pairs` entries of `prod`
+// over the stacked operand (plane_a nb + i, plane_b nb + j, 1, slot); slots are numbered from 0 within the group.  (miraculix_amd.crossproduct.ld_pairwise_tiles restates it.)
+static void pairwise_group_tiles(int nb, const std::vector<int> &jmax, int i_lo, int i_hi, int pairs, std::vector<int4> &prod, std::vector<int4> &band) {
   int slot = 0;
   for (int i = i_lo; i < i_hi; i++)
-    for (int j = i; j < std::min(nb, i + ndiag + 1); j++) {
+    for (int j = i; j <= jmax[(size_t)i]; j++) {
       band.push_back(make_int4(i, j, 1, slot));
       // pairs == 1: the (Z, Z) product alone
       for (int k = 0; k < pairs; k++) prod.push_back(pairs == 1 ? make_int4(i, j, 1, slot) : make_int4(pw_plane_a(k) * nb + i, pw_plane_b(k) * nb + j, 1, slot + k));
@@ -1625,19 +1720,17 @@ static void pairwise_group_tiles(int nb, int ndiag, int i_lo, int i_hi, int pair
 }
 
 // the pairwise route: the three planes staged, per group of tile rows the count products and their combine
-static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, double *out, long ldb, bool scores, int flag) {
+static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag) {
   // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
   const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB"), *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
   const size_t cap = (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
   const size_t slot_bytes = kPwSlotInts * sizeof(int);
-  LdWindow c(who, plink, snps, indiv, window, out, ldb, scores, flag);
-  const size_t row_tiles_max = (size_t)std::min(c.g.nb, c.ndiag + 1);
-  // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole band needs less)
-  if (c.begin(3, std::min(std::max(cap, row_tiles_max * kPwPairs * slot_bytes), (size_t)c.g.nb * row_tiles_max * kPwPairs * slot_bytes), nullptr, kPwMaxIndiv,
+  LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
+  // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole window needs less)
+  if (c.begin(3, [&] { return std::min(std::max(cap, c.row_tiles_max * kPwPairs * slot_bytes), c.ntiles * kPwPairs * slot_bytes); }, nullptr, kPwMaxIndiv,
               "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", "%s: at most %ld SNPs per call")) return 1;
   const XGeom &g = c.g;
   hipStream_t s = c.s;
-  const int ndiag = c.ndiag;
   XBuf d_scr, d_sums, d_bt;
   if (stage_operand(plink, c.in_dev, c.row_bytes, true, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, indiv)) return 1;
   int has_missing = 1;
@@ -1659,15 +1752,30 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
     hipLaunchKernelGGL(k_pw_rowsums, g_rows, dim3(256), 0, s, c.X(), g.nslabs, spc, (long)g.nb, d_sz, d_sa);
     MXA_HIP(hipGetLastError());
   }
-  const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (row_tiles_max * (size_t)pairs * slot_bytes)));
-  const int ngroups = (g.nb + rows_per_group - 1) / rows_per_group;
+  // groups of consecutive tile rows.  Fixed window: equally many rows each, sized by the longest tile row; general window (tile rows of different
+  // lengths): as many rows as keep the group's own tiles under the cap.  One tile row at least either way; the results do not depend on the groups.
+  std::vector<int> group_row0{0};
+  if (!c.general()) {
+    const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * (size_t)pairs * slot_bytes)));
+    for (int i = rows_per_group; i < g.nb; i += rows_per_group) group_row0.push_back(i);
+  } else {
+    const size_t cap_tiles = cap / ((size_t)pairs * slot_bytes);
+    size_t held = 0;
+    for (int i = 0; i < g.nb; i++) {
+      const size_t t = (size_t)(c.jmax[(size_t)i] - i + 1);
+      if (held && held + t > cap_tiles) { group_row0.push_back(i); held = 0; }
+      held += t;
+    }
+  }
+  const int ngroups = (int)group_row0.size();
+  group_row0.push_back(g.nb);
   std::vector<std::vector<int4>> prod((size_t)ngroups);
   std::vector<int4> band;
   std::vector<size_t> band_first((size_t)ngroups + 1, 0);
   size_t group_tiles_max = 0;
   for (int q = 0; q < ngroups; q++) {
     band_first[(size_t)q] = band.size();
-    pairwise_group_tiles(g.nb, ndiag, q * rows_per_group, std::min(g.nb, (q + 1) * rows_per_group), pairs, prod[(size_t)q], band);
+    pairwise_group_tiles(g.nb, c.jmax, group_row0[(size_t)q], group_row0[(size_t)q + 1], pairs, prod[(size_t)q], band);
     group_tiles_max = std::max(group_tiles_max, band.size() - band_first[(size_t)q]);
   }
   band_first.back() = band.size();
@@ -1682,13 +1790,19 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
     if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
     const dim3 grid((unsigned)(band_first[(size_t)q + 1] - band_first[(size_t)q]));
     const int4 *bt = (const int4 *)d_bt.p + band_first[(size_t)q];
-    auto combine = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, c.d_dst, c.ld_dst, window, flag); };
-    if (scores) { if (dense) combine(k_ld_pw_combine<kPostLdScores, true>); else combine(k_ld_pw_combine<kPostLdScores, false>); }
-    else { if (dense) combine(k_ld_pw_combine<kPostLdBand, true>); else combine(k_ld_pw_combine<kPostLdBand, false>); }
+    // the instantiation for (scores, dense, window object)
+    auto combine = [&](auto win) {
+      using Win = decltype(win);
+      auto go = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, c.d_dst, c.ld_dst, win, flag); };
+      if (scores) { if (dense) go(k_ld_pw_combine<true, true, Win>); else go(k_ld_pw_combine<true, false, Win>); }
+      else { if (dense) go(k_ld_pw_combine<false, true, Win>); else go(k_ld_pw_combine<false, false, Win>); }
+    };
+    if (c.general()) combine(LdVarWindow{(const int *)c.d_last.p, (const long *)c.d_rowptr.p, c.ndiag});
+    else combine(LdFixedWindow{window});
     MXA_HIP(hipGetLastError());
   }
   if (c.finish()) return 1;
-  debug_info("%s: %d group(s) of %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, rows_per_group, pairs, dense ? "six counts" : "no missing code: per-SNP sums",
+  debug_info("%s: %d group(s) of up to %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, group_row0[1], pairs, dense ? "six counts" : "no missing code: per-SNP sums",
              f4 ? "FP4" : "int8");
   return 0;
 }
@@ -1697,24 +1811,84 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
 
 extern "C" int mxa_ld_band_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind) {
   mxa::clear_error();
-  return mxa::ld_pairwise_any("mxa_ld_band_pairwise", plink, snps, indiv, window, band, ldb, false, kind);
+  return mxa::ld_pairwise_any("mxa_ld_band_pairwise", plink, snps, indiv, window, nullptr, band, ldb, false, kind);
 }
 
 extern "C" int mxa_ld_scores_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust) {
   mxa::clear_error();
-  return mxa::ld_pairwise_any("mxa_ld_scores_pairwise", plink, snps, indiv, window, scores, 0, true, adjust);
+  return mxa::ld_pairwise_any("mxa_ld_scores_pairwise", plink, snps, indiv, window, nullptr, scores, 0, true, adjust);
 }
 
 extern "C" int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind, int is_plink_format,
                            const double *allele_freq) {
   mxa::clear_error();
-  return mxa::ld_window_any("mxa_ld_band", plink, snps, indiv, window, band, ldb, false, kind, is_plink_format != 0, allele_freq);
+  return mxa::ld_window_any("mxa_ld_band", plink, snps, indiv, window, nullptr, band, ldb, false, kind, is_plink_format != 0, allele_freq);
 }
 
 extern "C" int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust, int is_plink_format,
                              const double *allele_freq) {
   mxa::clear_error();
-  return mxa::ld_window_any("mxa_ld_scores", plink, snps, indiv, window, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
+  return mxa::ld_window_any("mxa_ld_scores", plink, snps, indiv, window, nullptr, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
+}
+
+// ---- windowed LD by distance: the window of SNP i ends at last[i] (mxa_ld_window_bounds makes it from base pairs / centimorgans / SNP counts and chromosomes)
+extern "C" int mxa_ld_window_rows(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind, int is_plink_format, const double *allele_freq) {
+  mxa::clear_error();
+  if (!last) { mxa::set_error(1, "mxa_ld_window_rows: bad arguments"); return 1; }
+  return mxa::ld_window_any("mxa_ld_window_rows", plink, snps, indiv, 0, last, rows, 0, false, kind, is_plink_format != 0, allele_freq);
+}
+
+extern "C" int mxa_ld_window_scores(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust, int is_plink_format,
+                                    const double *allele_freq) {
+  mxa::clear_error();
+  if (!last) { mxa::set_error(1, "mxa_ld_window_scores: bad arguments"); return 1; }
+  return mxa::ld_window_any("mxa_ld_window_scores", plink, snps, indiv, 0, last, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
+}
+
+extern "C" int mxa_ld_window_rows_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind) {
+  mxa::clear_error();
+  if (!last) { mxa::set_error(1, "mxa_ld_window_rows_pairwise: bad arguments"); return 1; }
+  return mxa::ld_pairwise_any("mxa_ld_window_rows_pairwise", plink, snps, indiv, 0, last, rows, 0, false, kind);
+}
+
+extern "C" int mxa_ld_window_scores_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust) {
+  mxa::clear_error();
+  if (!last) { mxa::set_error(1, "mxa_ld_window_scores_pairwise: bad arguments"); return 1; }
+  return mxa::ld_pairwise_any("mxa_ld_window_scores_pairwise", plink, snps, indiv, 0, last, scores, 0, true, adjust);
+}
+
+// The window ends of a distance window, on the host (no device is touched): last[i] = the largest j >= i on i's chromosome with pos[j] - pos[i] <= max_dist
+// (one rounded fp64 subtraction, inclusive) and j - i <= max_snps.  All three bounds are monotone in j for fixed i and the end never moves back as i grows,
+// so one two-pointer sweep finds every end: O(snps).
+extern "C" int mxa_ld_window_bounds(int snps, const double *pos, const int *chrom, double max_dist, int max_snps, int *last, long *rowptr) {
+  mxa::clear_error();
+  const char *who = "mxa_ld_window_bounds";
+  if (snps <= 0 || !last) { mxa::set_error(1, "%s: bad arguments", who); return 1; }
+  if (!pos && max_snps < 0) { mxa::set_error(1, "%s: neither a distance bound (pos) nor a SNP bound (max_snps >= 0) is given", who); return 1; }
+  if (!(max_dist >= 0.0)) { mxa::set_error(1, "%s: max_dist must not be negative or NaN", who); return 1; }
+  if (pos)
+    for (long i = 0; i < snps; i++) {
+      if (pos[i] != pos[i]) { mxa::set_error(1, "%s: position %ld is NaN", who, i); return 1; }
+      if (i > 0 && (!chrom || chrom[i] == chrom[i - 1]) && pos[i] < pos[i - 1]) { mxa::set_error(1, "%s: position %ld decreases inside a chromosome", who, i); return 1; }
+    }
+  if (chrom) {   // contiguous: a code that starts a run has not been seen before
+    std::vector<int> seen;
+    for (long i = 0; i < snps; i++)
+      if (i == 0 || chrom[i] != chrom[i - 1]) seen.push_back(chrom[i]);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { mxa::set_error(1, "%s: the SNPs of a chromosome are not contiguous", who); return 1; }
+  }
+  long j = 0;                                               // the end of the window of i - 1: the window of i reaches at least as far
+  for (long i = 0; i < snps; i++) {
+    if (j < i) j = i;
+    while (j + 1 < snps && (!chrom || chrom[j + 1] == chrom[i]) && (!pos || pos[j + 1] - pos[i] <= max_dist) && (max_snps < 0 || j + 1 - i <= (long)max_snps)) j++;
+    last[i] = (int)j;
+  }
+  if (rowptr) {
+    rowptr[0] = 0;
+    for (long i = 0; i < snps; i++) rowptr[i + 1] = rowptr[i] + ((long)last[i] - i + 1);
+  }
+  return 0;
 }
 
 extern "C" int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, double *ans, bool is_plink_format) {

@@ -94,6 +94,16 @@ def load_shared_library():
     L.mxa_ld_band_pairwise.restype = ctypes.c_int
     L.mxa_ld_scores_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     L.mxa_ld_scores_pairwise.restype = ctypes.c_int
+    L.mxa_ld_window_bounds.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.mxa_ld_window_bounds.restype = ctypes.c_int
+    L.mxa_ld_window_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.mxa_ld_window_rows.restype = ctypes.c_int
+    L.mxa_ld_window_scores.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.mxa_ld_window_scores.restype = ctypes.c_int
+    L.mxa_ld_window_rows_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    L.mxa_ld_window_rows_pairwise.restype = ctypes.c_int
+    L.mxa_ld_window_scores_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    L.mxa_ld_window_scores_pairwise.restype = ctypes.c_int
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

@@ -27,6 +27,25 @@ def read_bed(path, snps=None, indiv=None):
     return data.reshape(snps, bps).copy(), snps, indiv
 
 
+def read_bim(path):
+    """The map of a PLINK fileset: (chrom, cm, bp) of its .bim, one entry per SNP in file order.  A .bim line is six whitespace-separated columns -- chromosome,
+    SNP id, genetic position in centimorgans, base-pair position, allele 1, allele 2.  chrom: int32 codes 0, 1, 2, ... in order of first appearance (the names
+    themselves -- "1", "X", "chr2" -- are not interpreted); cm, bp: float64.  What miraculix_amd.crossproduct.ld_window_bounds takes."""
+    base = path[:-4] if path.endswith((".bed", ".bim")) else path
+    codes, chrom, cm, bp = {}, [], [], []
+    with open(base + ".bim") as fh:
+        for n, line in enumerate(fh, 1):
+            col = line.split()
+            if not col:
+                continue
+            if len(col) != 6:
+                raise ValueError(f"{base}.bim line {n}: six columns expected, found {len(col)}")
+            chrom.append(codes.setdefault(col[0], len(codes)))
+            cm.append(float(col[2]))
+            bp.append(float(col[3]))
+    return np.asarray(chrom, dtype=np.int32), np.asarray(cm, dtype=np.float64), np.asarray(bp, dtype=np.float64)
+
+
 def write_bed(path, plink):
     with open(path, "wb") as fh:
         fh.write(BED_MAGIC)

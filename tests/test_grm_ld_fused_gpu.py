@@ -7,6 +7,7 @@ host and device results, ragged sizes, PLINK and raw 2-bit input, and through th
 import numpy as np
 import pytest
 
+import _ld_ref as ldref
 from _util import Oracle, make_problem, pack_plink, synth_genotypes
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +72,12 @@ def test_fused_grm_and_ld_equal_the_unfused_kernels_and_the_dense_restatement(mx
     ok = np.isfinite(ref)                     # a monomorphic SNP has sigma = 0 in the reference too
     assert np.array_equal(np.isfinite(R), ok)
     assert np.abs(R[ok] - ref[ok]).max() <= 1e-11
+    # ... and element by element: the bound derived from the map's own roundings (tests/_ld_ref.py), against the exact integer product and long double
+    case = ldref.plain_case(prob["plink"], indiv, f)
+    assert ok.all() and np.isfinite(case["b"]).all()
+    ratio = ldref.worst_ratio(R, case["r"], case["b"])
+    print(f"mxa_ld {snps}x{indiv} {engine}: worst |r - r_ref| / bound = {ratio:.3f}")
+    assert ratio <= 1.0, ratio
 
 
 def test_fused_grm_device_resident_and_through_the_host_slab_pipeline(mx, monkeypatch):

@@ -1,6 +1,6 @@
 """Pairwise-complete windowed LD on data with missing genotypes: mxa_ld_band_pairwise / mxa_ld_scores_pairwise.
 
-The reference for every value is the numpy restatement below (_restate), from the unpacked PLINK codes: m = present, z = allele count with missing as 0,
+The reference for every value is the numpy restatement of tests/_ld_ref.py (pairwise_restate), from the unpacked PLINK codes: m = present, z = allele count with missing as 0,
 a = code 11; N = M M^T, Sxy = Z Z^T, Sx = Z M^T, Sy = Sx^T, Sxx = Sx + 2 A M^T, Syy = Sxx^T as int64 matrices; num = N Sxy - Sx Sy, dx = N Sxx - Sx^2,
 dy = dx^T in int64; r_ref = num / sqrt(dx dy) in np.longdouble.  (The matrix products run through the fp64 BLAS and are converted to int64: every partial
 sum is an integer below 4 * 1031 < 2^53, so they are the int64 products; a block of rows is recomputed with numpy's own int64 product and must be equal.)
@@ -17,6 +17,7 @@ import math
 import numpy as np
 import pytest
 
+from _ld_ref import PAIRWISE_UNITS, codes, pairwise_restate
 from _util import pack_plink, synth_genotypes
 
 pytestmark = pytest.mark.gpu
@@ -44,32 +45,12 @@ def _problem(snps, indiv, missing_frac):
 
 
 def _codes(plink, indiv):
-    P = np.ascontiguousarray(plink, dtype=np.uint8)
-    return np.stack([(P >> (2 * q)) & 3 for q in range(4)], axis=-1).reshape(P.shape[0], -1)[:, :indiv]
+    return codes(plink, indiv)
 
 
 def _restate(plink, indiv):
-    """dict(N, Sxy: int64 snps x snps; r: longdouble, NaN where dx dy = 0) -- the formulas of the issue on the unpacked codes"""
-    C = _codes(plink, indiv)
-    M, Z, A = (C != 1).astype(np.float64), np.where(C >= 2, C - 1, 0).astype(np.float64), (C == 3).astype(np.float64)
-
-    def prod(X, Y):
-        P = X @ Y.T
-        Pi = P.astype(np.int64)
-        assert np.array_equal(Pi, P)
-        k = min(16, X.shape[0])
-        assert np.array_equal(Pi[:k], X[:k].astype(np.int64) @ Y.T.astype(np.int64))       # numpy's own int64 product on a block of rows
-        return Pi
-
-    N, Sxy, Sx = prod(M, M), prod(Z, Z), prod(Z, M)
-    Sxx = Sx + 2 * prod(A, M)
-    Sy = Sx.T
-    num = N * Sxy - Sx * Sy
-    dx = N * Sxx - Sx * Sx
-    assert dx.min() >= 0
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = num.astype(LD) / np.sqrt(dx.astype(LD) * dx.T.astype(LD))
-    return dict(N=N, Sxy=Sxy, r=r)
+    """dict(N, Sxy: int64 snps x snps; r: longdouble, NaN where dx dy = 0) -- the formulas of the issue on the unpacked codes (tests/_ld_ref.py)"""
+    return pairwise_restate(plink, indiv)
 
 
 def _band_of(R, window, fill=0.0):
@@ -108,7 +89,7 @@ def _assert_band(B, ref_r, window, what):
     unit = (U * np.abs(want))[ok]
     worst = float((err / np.where(unit > 0, unit, 1)).max()) if err.size else 0.0
     print(f"band {what}: worst |r - r_ref| = {worst:.2f} units of 2^-53 |r_ref| over {int(ok.sum())} entries")
-    assert np.all(err <= 8 * unit), (what, worst)
+    assert np.all(err <= PAIRWISE_UNITS * unit), (what, worst)
     assert np.all(got[~inband] == 0.0) and not np.signbit(got[~inband]).any(), what
     assert np.all(B[:, window + 1:] == SENTINEL), what
 

@@ -19,6 +19,7 @@ import math
 import numpy as np
 import pytest
 
+from _ld_ref import first_of as _first, pairs as _pairs          # the stored-pair enumeration and first[], shared with the tests from the definition
 from _util import make_problem, pack_plink, synth_genotypes
 
 pytestmark = pytest.mark.gpu
@@ -83,19 +84,6 @@ def _cluster_window(mx, snps, seed=17):
     assert reach.min() == 0 and reach.max() >= 513 and reach[200] == run - 1
     assert np.any(np.diff(per_row[:-1]) != 0), per_row
     return last, rowptr
-
-
-def _pairs(last):
-    """(ii, jj) of the stored entries in storage order: row i holds j = i .. last[i]"""
-    n = len(last)
-    cnt = last.astype(np.int64) - np.arange(n) + 1
-    ii = np.repeat(np.arange(n), cnt)
-    jj = ii + (np.arange(len(ii)) - np.repeat(np.cumsum(cnt) - cnt, cnt))
-    return ii, jj
-
-
-def _first(last):
-    return np.searchsorted(last, np.arange(len(last)), side="left")              # the smallest k with last[k] >= i (last is non-decreasing)
 
 
 def _terms(R, indiv, adjust):

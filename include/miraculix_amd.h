@@ -378,6 +378,33 @@ int mxa_ld_window_scores(const unsigned char *plink, int snps, int indiv, const 
 int mxa_ld_window_rows_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind);
 int mxa_ld_window_scores_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust);
 
+/* The pairs of a window with r^2 at or above a cutoff, as a sparse list compacted on the device (what PLINK's --r2 --ld-window-kb .. --ld-window-r2 gives): the
+ * fourth output form of the general window, next to band, ragged rows and scores.  The rows never exist; the result costs its own pairs only.
+ * plink, snps, indiv, last, is_plink_format, allele_freq: exactly as for mxa_ld_window_rows / mxa_ld_window_rows_pairwise (same staging, byte table,
+ * statistics, engines and bounds).  A fixed window of w SNPs is last[i] = min(i + w, snps - 1).
+ * Candidates: the pairs (i, j), i < j <= last[i] (the diagonal is not a pair).  With r^ = bit for bit the value mxa_ld_window_rows(_pairwise) stores for the
+ * pair at kind 0, and q = fl(r^ * r^) (one rounding: the kind-1 value), the pair is kept iff q >= min_r2.  A NaN r^ is never kept (the comparison is false): a
+ * monomorphic SNP on the plain route, a pair with dx * dy = 0 on the pairwise route; no special case.
+ * Result, CSR of the strict upper triangle: rowptr (snps + 1 longs, rowptr[0] = 0); the kept pairs of row i at rowptr[i] .. rowptr[i + 1] - 1, col strictly
+ * ascending; val = r^ (kind 0) or q (kind 1); *total = rowptr[snps] (total: a host pointer, required).
+ * Count-only call (col == NULL and val == NULL): rowptr and *total are written, capacity is ignored, returns 0.
+ * Filling call (col and val given, `capacity` entries each): nothing at or beyond capacity is written.  total <= capacity: returns 0, nothing at or beyond
+ * total is written.  total > capacity: returns 1 with mxa_last_error() == 25; rowptr and *total are valid (the message names both numbers), the contents of
+ * col / val are unspecified.
+ * rowptr, col, val: all host or all device pointers; plink, last, allele_freq host or device independently.
+ * The window's tile products run once, into int32 count tiles of 256 KiB in groups of tile rows under MXA_LD_PAIRWISE_SCRATCH_MB (as the pairwise entries:
+ * six per window tile, or one on data without a missing code; one on the plain route); per group a count pass, a scan and a write pass.  Every position is a
+ * sum of counts in a fixed order (no atomics): rowptr, col and val are identical from run to run, between the FP4 and the int8 engine (MXA_XPROD_ENGINE=i8),
+ * between host and device pointers, and for every scratch size.
+ * Errors (return 1, mxa_last_error() == 1, outputs untouched): everything mxa_ld_window_rows(_pairwise) rejects; rowptr == NULL or total == NULL; exactly one
+ * of col / val NULL; capacity < 0 on a filling call; min_r2 negative, NaN or infinite (min_r2 > 1 is legal: the result is normally empty); kind not 0 or 1;
+ * rowptr, col, val not all host or all device.  12: not enough device memory (the scratch, the per-(tile, row) counters and, for host outputs, the device
+ * copies of rowptr / col / val are counted). */
+int mxa_ld_window_pairs(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
+                        long capacity, long *total, int is_plink_format, const double *allele_freq);
+int mxa_ld_window_pairs_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col,
+                                 double *val, long capacity, long *total);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

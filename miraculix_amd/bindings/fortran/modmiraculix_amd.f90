@@ -17,6 +17,7 @@ module modmiraculix_amd
  public :: mxa_ld_band, mxa_ld_scores
  public :: mxa_ld_band_pairwise, mxa_ld_scores_pairwise
  public :: mxa_ld_window_bounds, mxa_ld_window_rows, mxa_ld_window_scores, mxa_ld_window_rows_pairwise, mxa_ld_window_scores_pairwise
+ public :: mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -195,6 +196,28 @@ module modmiraculix_amd
    import c_int, c_ptr
    type(c_ptr), value, intent(in) :: plink, last, scores
    integer(c_int), value, intent(in) :: snps, indiv, adjust
+   integer(c_int) :: rc
+  end function
+
+  ! the pairs i < j <= last(i + 1) of a window with r * r >= min_r2 as CSR, 0-based as in C: rowptr (snps + 1 C longs), col (C ints, ascending in a row), val
+  ! (kind 0: r, 1: r * r), `capacity` entries each; total: c_loc of an integer(c_long) on the host.  col = val = c_null_ptr: the count-only call (rowptr and
+  ! total).  rc = 1 with mxa_last_error() = 25: total > capacity (rowptr and total are valid).  rowptr, col, val: all host or all device.
+  function mxa_ld_window_pairs(plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, is_plink_format, allele_freq) &
+      bind(C, name='mxa_ld_window_pairs') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, rowptr, col, val, total, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, kind, is_plink_format
+   real(c_double), value, intent(in) :: min_r2
+   integer(c_long), value, intent(in) :: capacity
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_pairs_pairwise(plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total) &
+      bind(C, name='mxa_ld_window_pairs_pairwise') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, rowptr, col, val, total
+   integer(c_int), value, intent(in) :: snps, indiv, kind
+   real(c_double), value, intent(in) :: min_r2
+   integer(c_long), value, intent(in) :: capacity
    integer(c_int) :: rc
   end function
 

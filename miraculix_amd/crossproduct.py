@@ -296,3 +296,52 @@ def ld_window_scores_pairwise(plink, snps, indiv, last, adjust=False):
     S = _zeros_like(plink, snps)
     _check(L.mxa_ld_window_scores_pairwise(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), _lib.ptr(S), int(bool(adjust))), "mxa_ld_window_scores_pairwise")
     return S
+
+
+# ---- the pairs of a window above an r^2 cutoff as CSR: C entries mxa_ld_window_pairs / mxa_ld_window_pairs_pairwise
+def ld_pairs(plink, snps, indiv, last=None, window=None, min_r2=0.2, kind="r2", pairwise=False, is_plink_format=False, allele_freq=None, capacity=None):
+    """Additive (C entries mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise): the pairs i < j <= last[i] with r^2 >= min_r2 as CSR of the strict upper
+    triangle, compacted on the device -- what PLINK's --r2 --ld-window-kb .. --ld-window-r2 lists.  Returns (rowptr int64 of snps + 1, col int32, val float64),
+    numpy or torch tensors on the input's device: the kept pairs of SNP i are col[rowptr[i]: rowptr[i + 1]] (ascending) with val = r (kind "r") or r * r
+    (kind "r2"); r is the value ld_window_rows() / ld_window_rows_pairwise() (pairwise=True: data with missing genotypes) stores for the pair, bit for bit.
+    Exactly one of `last` (as ld_window_bounds returns it) and `window` (a fixed number of SNPs: last[i] = min(i + window, snps - 1)) is given.
+    capacity=None: a count-only call, then an exactly sized filling call -- the tile products run twice.  capacity=k: one call into arrays of k entries,
+    trimmed to the total; raises RuntimeError naming the needed total when it exceeds k."""
+    if kind not in ("r", "r2"):
+        raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+    if (last is None) == (window is None):
+        raise ValueError("exactly one of last and window is needed")
+    if not pairwise and (allele_freq is None or len(allele_freq) != snps):
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    if window is not None:
+        if not 0 <= int(window) < snps:
+            raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+        last = np.minimum(np.arange(snps, dtype=np.int64) + int(window), snps - 1).astype(np.int32)
+    last, _ = _ld_last_args(plink, snps, indiv, last)
+    import ctypes
+    L = _lib.check_library_handle()
+    if _lib.is_torch_tensor(plink):
+        import torch
+        new = lambda n, dt: torch.zeros(n, dtype={np.int64: torch.int64, np.int32: torch.int32, np.float64: torch.float64}[dt], device=plink.device)
+    else:
+        new = lambda n, dt: np.zeros(n, dtype=dt)
+    entry = "mxa_ld_window_pairs_pairwise" if pairwise else "mxa_ld_window_pairs"
+    tail = []
+    if not pairwise:
+        f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+        tail = [int(bool(is_plink_format)), _lib.ptr(f)]
+    rowptr = new(snps + 1, np.int64)
+    total = ctypes.c_long(0)
+
+    def call(col, val, cap):
+        return getattr(L, entry)(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), float(min_r2), 1 if kind == "r2" else 0, _lib.ptr(rowptr), _lib.ptr(col),
+                                 _lib.ptr(val), int(cap), ctypes.byref(total), *tail)
+
+    if capacity is None:
+        _check(call(None, None, 0), entry)
+        capacity = total.value
+    elif int(capacity) < 0:
+        raise ValueError(f"capacity must not be negative: {capacity}")
+    col, val = new(int(capacity), np.int32), new(int(capacity), np.float64)
+    _check(call(col, val, int(capacity)), entry)               # error 25: the message names the total and the capacity
+    return rowptr, col[: total.value], val[: total.value]

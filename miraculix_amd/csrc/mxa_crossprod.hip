@@ -19,6 +19,7 @@
 #include <chrono>
 #include <thread>
 #include <algorithm>
+#include <cfloat>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -1460,6 +1461,8 @@ namespace {
 // ld_dst) is where they write -- the band, the rows, or the scores' partial buffer P -- and finish() turns it into the result at d_res and delivers that.
 // Two ways of constructing it: the fixed window (`window` SNPs on each side; result = band of leading dimension ldb, or scores) and the general one
 // (last != nullptr: the window of SNP i ends at last[i]; result = ragged rows, or scores).  Both end in the same plan, jmax[] per tile row.
+// A third result of the general window, set_pairs(): the pairs above a cutoff as CSR (mxa_ld_window_pairs*).  `out` is then the caller's rowptr, and a host
+// result leaves from one device buffer d_out = rowptr (snps + 1 longs), val (capacity doubles), col (capacity ints); finish_pairs() instead of finish().
 struct LdWindow {
   const char *who;
   const unsigned char *plink;
@@ -1468,7 +1471,11 @@ struct LdWindow {
   double *out;
   long ldb;
   bool scores;
-  int flag;                    // kind (band, rows) / adjust (scores)
+  int flag;                    // kind (band, rows, pairs) / adjust (scores)
+  bool pairs = false, fill = false;   // the CSR result; fill: col / val are written (else the count-only call)
+  int *col = nullptr;
+  double *val = nullptr;
+  long capacity = 0;           // entries of col / val (0 on a count-only call)
   XGeom g;
   long row_bytes = 0;
   int ndiag = 0;               // tile diagonals of the partial buffer: the kernels' (ld_band_diagonals(window)), or max(jmax[I] - I)
@@ -1491,6 +1498,11 @@ struct LdWindow {
   long post_c0() const { return general() ? (long)ndiag : window; }
   void set_post(XPost &xp) const { xp.do_scale = flag; xp.last = (const int *)d_last.p; xp.rowptr = (const long *)d_rowptr.p; }
   std::vector<int4> tiles() const { return window_tiles(jmax); }
+  void set_pairs(int *col_, double *val_, long capacity_) { pairs = true; fill = col_ != nullptr; col = col_; val = val_; capacity = fill ? capacity_ : 0; }
+  // where the CSR result is formed on the device: the caller's arrays, or the pieces of d_out
+  long *d_pairs_rowptr() const { return out_dev ? reinterpret_cast<long *>(out) : (long *)d_out.p; }
+  double *d_pairs_val() const { return out_dev ? val : reinterpret_cast<double *>((long *)d_out.p + snps + 1); }
+  int *d_pairs_col() const { return out_dev ? col : reinterpret_cast<int *>(d_pairs_val() + capacity); }
 
   // The tile plan.  Fixed: the band of ndiag tile diagonals.  General: `last` is fetched (host or device pointer) and checked, rowptr formed, and tile row I
   // reaches as far as its last SNP does (last is non-decreasing), so every tile (I, I .. jmax[I]) holds a window element.
@@ -1547,9 +1559,14 @@ struct LdWindow {
     row_bytes = (indiv + 3) / 4;
     in_dev = ptr_location(plink, nullptr) == 1;
     out_dev = ptr_location(out, nullptr) == 1;
+    if (pairs && fill && ((ptr_location(col, nullptr) == 1) != out_dev || (ptr_location(val, nullptr) == 1) != out_dev)) {
+      set_error(1, "%s: rowptr, col and val must be all host or all device pointers", who);
+      return 1;
+    }
     // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
     plane_bytes = (size_t)g.rows_pad() * g.pitch();
     obytes = sizeof(double) * (scores ? (size_t)snps : general() ? (size_t)h_rowptr.back() : (size_t)(window + 1) * (size_t)snps);
+    if (pairs) obytes = sizeof(long) * ((size_t)snps + 1) + (sizeof(double) + sizeof(int)) * (size_t)capacity;
     const size_t pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
     const size_t wbytes = sizeof(int) * (size_t)g.nb + (general() ? sizeof(int) * (size_t)snps + sizeof(long) * ((size_t)snps + 1) : 0);   // jmax, last, rowptr
     size_t free_b = 0, total_b = 0;
@@ -1565,9 +1582,10 @@ struct LdWindow {
       MXA_HIP(hipMemcpy(d_jmax.p, jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice));
     }
     if (general()) {
-      if (d_last.alloc(sizeof(int) * (size_t)snps) || (!scores && d_rowptr.alloc(sizeof(long) * ((size_t)snps + 1)))) return 1;
+      const bool rows = !scores && !pairs;   // the ragged rows' starts
+      if (d_last.alloc(sizeof(int) * (size_t)snps) || (rows && d_rowptr.alloc(sizeof(long) * ((size_t)snps + 1)))) return 1;
       MXA_HIP(hipMemcpy(d_last.p, h_last.data(), sizeof(int) * (size_t)snps, hipMemcpyHostToDevice));
-      if (!scores) MXA_HIP(hipMemcpy(d_rowptr.p, h_rowptr.data(), sizeof(long) * ((size_t)snps + 1), hipMemcpyHostToDevice));
+      if (rows) MXA_HIP(hipMemcpy(d_rowptr.p, h_rowptr.data(), sizeof(long) * ((size_t)snps + 1), hipMemcpyHostToDevice));
     }
     d_res = out_dev ? out : (double *)d_out.p;
     ld_res = out_dev ? ldb : window + 1;
@@ -1586,6 +1604,46 @@ struct LdWindow {
     MXA_HIP(profile_launch(e0, e1));
     return 0;
   }
+  // the CSR result: the total (d_total, the running base after the last group) is read once; a host result is rowptr and the first min(total, capacity)
+  // entries of col / val.  total > capacity: error 25, rowptr and *total valid.
+  int finish_pairs(const long *d_total, long *total) {
+    MXA_HIP(hipEventRecord(e1.e, s));
+    long h_total = 0;
+    MXA_HIP(hipMemcpyAsync(&h_total, d_total, sizeof(long), hipMemcpyDeviceToHost, s));
+    if (!out_dev) MXA_HIP(hipMemcpyAsync(out, d_pairs_rowptr(), sizeof(long) * ((size_t)snps + 1), hipMemcpyDeviceToHost, s));
+    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
+    const size_t filled = (size_t)std::min(h_total, capacity);
+    if (!out_dev && filled) {
+      MXA_HIP(hipMemcpyAsync(val, d_pairs_val(), sizeof(double) * filled, hipMemcpyDeviceToHost, s));
+      MXA_HIP(hipMemcpyAsync(col, d_pairs_col(), sizeof(int) * filled, hipMemcpyDeviceToHost, s));
+      MXA_HIP(hipStreamSynchronize(s));
+    }
+    MXA_HIP(profile_launch(e0, e1));
+    *total = h_total;
+    if (fill && h_total > capacity) { set_error(25, "%s: %ld pairs pass the cutoff, capacity is %ld", who, h_total, capacity); return 1; }
+    return 0;
+  }
+};
+}  // namespace
+
+// the operand of the plain route: staged as it is, the engine, the frequencies on the device and the LD map's statistics (xp.u, xp.w, xp.a)
+namespace {
+struct LdPlainOperand {
+  bool f4 = false;
+  XBuf f_tmp, stats[3];
+  XPost xp;
+  int stage(LdWindow &c, const unsigned char *plink, bool is_plink, const double *freq) {
+    hipStream_t s = c.s;
+    if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, c.g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s)) return 1;
+    if (pick_engine((const int *)c.d_flag.p, c.indiv, s, f4)) return 1;
+    const double *d_f = freq;
+    if (ptr_location(freq, nullptr) != 1) {
+      if (f_tmp.alloc(sizeof(double) * (size_t)c.snps)) return 1;
+      MXA_HIP(hipMemcpyAsync(f_tmp.p, freq, sizeof(double) * (size_t)c.snps, hipMemcpyHostToDevice, s));
+      d_f = (const double *)f_tmp.p;
+    }
+    return fused_post_stats(c.g, c.X(), c.indiv, kPostLd, 0, d_f, stats, s, xp);
+  }
 };
 }  // namespace
 
@@ -1597,23 +1655,13 @@ static int ld_window_any(const char *who, const unsigned char *plink, long snps,
               "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
   const XGeom &g = c.g;
   hipStream_t s = c.s;
-  if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s)) return 1;
-  bool f4 = false;
-  if (pick_engine((const int *)c.d_flag.p, indiv, s, f4)) return 1;
-  XBuf f_tmp;
-  const double *d_f = freq;
-  if (ptr_location(freq, nullptr) != 1) {
-    if (f_tmp.alloc(sizeof(double) * (size_t)snps)) return 1;
-    MXA_HIP(hipMemcpyAsync(f_tmp.p, freq, sizeof(double) * (size_t)snps, hipMemcpyHostToDevice, s));
-    d_f = (const double *)f_tmp.p;
-  }
-  XPost xp;
-  XBuf stats[3];
-  if (fused_post_stats(g, c.X(), indiv, kPostLd, 0, d_f, stats, s, xp)) return 1;
+  LdPlainOperand op;
+  if (op.stage(c, plink, is_plink, freq)) return 1;
+  XPost &xp = op.xp;
   c.set_post(xp);                                         // kind / adjust, the general window's arrays (xprod_store_window)
   XTiles t;
   if (upload_tiles({c.tiles()}, s, t)) return 1;
-  if (c.start() || t.launch(0, g, f4, s, c.X(), c.d_dst, c.ld_dst, c.post_c0(), nullptr, c.post_kind(), xp)) return 1;
+  if (c.start() || t.launch(0, g, op.f4, s, c.X(), c.d_dst, c.ld_dst, c.post_c0(), nullptr, c.post_kind(), xp)) return 1;
   return c.finish();
 }
 
@@ -1719,70 +1767,108 @@ static void pairwise_group_tiles(int nb, const std::vector<int> &jmax, int i_lo,
     }
 }
 
+// The groups of a window whose tile products go through the count scratch (the pairwise-complete entries: pairs = 6 or 1; the CSR entries of the plain route:
+// pairs = 1): consecutive tile rows whose `pairs` slots of 256 KiB per window tile stay under `cap` bytes.  Fixed window: equally many rows each, sized by
+// the longest tile row; general window (tile rows of different lengths): as many rows as keep the group's own tiles under the cap.  One tile row at least
+// either way; the results do not depend on the groups.  Group q: tile rows [row0[q], row0[q + 1]), products prod[q], window tiles band[band_first[q] ..).
+namespace {
+constexpr size_t kPwSlotBytes = kPwSlotInts * sizeof(int);
+static size_t ld_scratch_cap() {   // MXA_LD_PAIRWISE_SCRATCH_MB, read per call
+  const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB");
+  return (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
+}
+struct LdGroups {
+  std::vector<int> row0;
+  int n = 0;
+  std::vector<std::vector<int4>> prod;
+  std::vector<int4> band;
+  std::vector<size_t> band_first;
+  size_t tiles_max = 0;
+  LdGroups(const LdWindow &c, size_t cap, int pairs) : row0{0} {
+    const XGeom &g = c.g;
+    if (!c.general()) {
+      const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * (size_t)pairs * kPwSlotBytes)));
+      for (int i = rows_per_group; i < g.nb; i += rows_per_group) row0.push_back(i);
+    } else {
+      const size_t cap_tiles = cap / ((size_t)pairs * kPwSlotBytes);
+      size_t held = 0;
+      for (int i = 0; i < g.nb; i++) {
+        const size_t t = (size_t)(c.jmax[(size_t)i] - i + 1);
+        if (held && held + t > cap_tiles) { row0.push_back(i); held = 0; }
+        held += t;
+      }
+    }
+    n = (int)row0.size();
+    row0.push_back(g.nb);
+    prod.resize((size_t)n);
+    band_first.assign((size_t)n + 1, 0);
+    for (int q = 0; q < n; q++) {
+      band_first[(size_t)q] = band.size();
+      pairwise_group_tiles(g.nb, c.jmax, row0[(size_t)q], row0[(size_t)q + 1], pairs, prod[(size_t)q], band);
+      tiles_max = std::max(tiles_max, band.size() - band_first[(size_t)q]);
+    }
+    band_first.back() = band.size();
+  }
+};
+// the operand of the pairwise route: the three planes staged, the engine, and -- no missing code anywhere -- the per-SNP sums that replace five products
+struct LdPairwiseOperand {
+  bool f4 = false, dense = true;
+  int pairs = kPwPairs;
+  XBuf d_sums;
+  int *d_sz = nullptr, *d_sa = nullptr;
+  int stage(LdWindow &c, const unsigned char *plink) {
+    const XGeom &g = c.g;
+    hipStream_t s = c.s;
+    const char *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
+    if (stage_operand(plink, c.in_dev, c.row_bytes, true, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, c.indiv)) return 1;
+    int has_missing = 1;
+    MXA_HIP(hipMemcpyAsync(&has_missing, c.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    MXA_HIP(hipStreamSynchronize(s));
+    // no plane holds a 3: the FP4 engine is exact while 4 indiv < 2^24 (pick_engine's rule); MXA_XPROD_ENGINE=i8 forces int8
+    f4 = 4 * c.indiv < (1L << 24);
+    if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
+    // no missing code anywhere: the (Z, Z) product alone, the rest from per-SNP sums (MXA_LD_PAIRWISE_DENSE=1 keeps the six products; bit-identical)
+    dense = has_missing || (e_dense && atoi(e_dense) != 0);
+    pairs = dense ? kPwPairs : 1;
+    if (!dense) {
+      if (d_sums.alloc(sizeof(int) * 2 * (size_t)g.rows_pad())) return 1;
+      d_sz = (int *)d_sums.p; d_sa = d_sz + g.rows_pad();
+      MXA_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int) * 2 * (size_t)g.rows_pad(), s));
+      long spc = 0;
+      const dim3 g_rows = rowstats_grid(g, &spc);
+      hipLaunchKernelGGL(k_pw_rowsums, g_rows, dim3(256), 0, s, c.X(), g.nslabs, spc, (long)g.nb, d_sz, d_sa);
+      MXA_HIP(hipGetLastError());
+    }
+    return 0;
+  }
+};
+}  // namespace
+
 // the pairwise route: the three planes staged, per group of tile rows the count products and their combine
 static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag) {
   // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
-  const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB"), *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
-  const size_t cap = (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
-  const size_t slot_bytes = kPwSlotInts * sizeof(int);
+  const size_t cap = ld_scratch_cap();
+  const size_t slot_bytes = kPwSlotBytes;
   LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
   // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole window needs less)
   if (c.begin(3, [&] { return std::min(std::max(cap, c.row_tiles_max * kPwPairs * slot_bytes), c.ntiles * kPwPairs * slot_bytes); }, nullptr, kPwMaxIndiv,
               "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", "%s: at most %ld SNPs per call")) return 1;
   const XGeom &g = c.g;
   hipStream_t s = c.s;
-  XBuf d_scr, d_sums, d_bt;
-  if (stage_operand(plink, c.in_dev, c.row_bytes, true, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, indiv)) return 1;
-  int has_missing = 1;
-  MXA_HIP(hipMemcpyAsync(&has_missing, c.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  MXA_HIP(hipStreamSynchronize(s));
-  // no plane holds a 3: the FP4 engine is exact while 4 indiv < 2^24 (pick_engine's rule); MXA_XPROD_ENGINE=i8 forces int8
-  bool f4 = 4 * indiv < (1L << 24);
-  if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
-  // no missing code anywhere: the (Z, Z) product alone, the rest from per-SNP sums (MXA_LD_PAIRWISE_DENSE=1 keeps the six products; bit-identical)
-  const bool dense = has_missing || (e_dense && atoi(e_dense) != 0);
-  const int pairs = dense ? kPwPairs : 1;
-  int *d_sz = nullptr, *d_sa = nullptr;
-  if (!dense) {
-    if (d_sums.alloc(sizeof(int) * 2 * (size_t)g.rows_pad())) return 1;
-    d_sz = (int *)d_sums.p; d_sa = d_sz + g.rows_pad();
-    MXA_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int) * 2 * (size_t)g.rows_pad(), s));
-    long spc = 0;
-    const dim3 g_rows = rowstats_grid(g, &spc);
-    hipLaunchKernelGGL(k_pw_rowsums, g_rows, dim3(256), 0, s, c.X(), g.nslabs, spc, (long)g.nb, d_sz, d_sa);
-    MXA_HIP(hipGetLastError());
-  }
-  // groups of consecutive tile rows.  Fixed window: equally many rows each, sized by the longest tile row; general window (tile rows of different
-  // lengths): as many rows as keep the group's own tiles under the cap.  One tile row at least either way; the results do not depend on the groups.
-  std::vector<int> group_row0{0};
-  if (!c.general()) {
-    const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * (size_t)pairs * slot_bytes)));
-    for (int i = rows_per_group; i < g.nb; i += rows_per_group) group_row0.push_back(i);
-  } else {
-    const size_t cap_tiles = cap / ((size_t)pairs * slot_bytes);
-    size_t held = 0;
-    for (int i = 0; i < g.nb; i++) {
-      const size_t t = (size_t)(c.jmax[(size_t)i] - i + 1);
-      if (held && held + t > cap_tiles) { group_row0.push_back(i); held = 0; }
-      held += t;
-    }
-  }
-  const int ngroups = (int)group_row0.size();
-  group_row0.push_back(g.nb);
-  std::vector<std::vector<int4>> prod((size_t)ngroups);
-  std::vector<int4> band;
-  std::vector<size_t> band_first((size_t)ngroups + 1, 0);
-  size_t group_tiles_max = 0;
-  for (int q = 0; q < ngroups; q++) {
-    band_first[(size_t)q] = band.size();
-    pairwise_group_tiles(g.nb, c.jmax, group_row0[(size_t)q], group_row0[(size_t)q + 1], pairs, prod[(size_t)q], band);
-    group_tiles_max = std::max(group_tiles_max, band.size() - band_first[(size_t)q]);
-  }
-  band_first.back() = band.size();
+  XBuf d_scr, d_bt;
+  LdPairwiseOperand op;
+  if (op.stage(c, plink)) return 1;
+  const bool f4 = op.f4, dense = op.dense;
+  const int pairs = op.pairs;
+  int *d_sz = op.d_sz, *d_sa = op.d_sa;
+  LdGroups gr(c, cap, pairs);
+  const int ngroups = gr.n;
+  const std::vector<int> &group_row0 = gr.row0;
+  const std::vector<size_t> &band_first = gr.band_first;
   XTiles t;
-  if (upload_tiles(std::move(prod), s, t)) return 1;
-  if (d_bt.alloc(band.size() * sizeof(int4)) || d_scr.alloc(group_tiles_max * (size_t)pairs * slot_bytes)) return 1;
-  MXA_HIP(hipMemcpyAsync(d_bt.p, band.data(), band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
+  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * slot_bytes)) return 1;
+  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
   if (c.start()) return 1;
   const XPost none{};
   for (int q = 0; q < ngroups; q++) {
@@ -1804,6 +1890,254 @@ static int ld_pairwise_any(const char *who, const unsigned char *plink, long snp
   if (c.finish()) return 1;
   debug_info("%s: %d group(s) of up to %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, group_row0[1], pairs, dense ? "six counts" : "no missing code: per-SNP sums",
              f4 ? "FP4" : "int8");
+  return 0;
+}
+
+// ---- pairs above a cutoff as CSR (mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise): the candidates i < j <= last[i] whose q = fl(r r) >= min_r2, compacted
+// on the device.  Both routes run the window's tile products once into the count scratch (kPostCounts; the plain route one slot per window tile), in the
+// groups of LdGroups; per group k_ld_select counts (WRITE = false), the scan kernels turn the counts into positions, and k_ld_select runs again and writes
+// (WRITE = true), recomputing its masks from the scratch, which is still in place.  Every position is a sum of counts in a fixed order: no atomics.
+// The providers: r of one element from the counts of its sub-block (cnt[slot][register], the lane <-> element map of k_ld_pw_combine), bit for bit what the
+// rows entries store at kind 0 -- the plain map of xprod_store_window's fin, or pw_r as k_ld_pw_combine calls it.
+struct LdPairsPlain {
+  static constexpr int kSlots = 1;
+  const double *__restrict__ u, *__restrict__ w;
+  double a;
+  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long gi, long gj) const {
+    return ld_scale_map(ld_center_map((double)cnt[0][reg], u[gj], u[gi], a), w[gj], w[gi]);
+  }
+};
+struct LdPairsCounts {
+  static constexpr int kSlots = kPwPairs;
+  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long, long) const {
+    return pw_r((double)cnt[0][reg], (double)cnt[1][reg], (double)cnt[2][reg], (double)cnt[3][reg], (double)cnt[4][reg], (double)cnt[5][reg]);
+  }
+};
+struct LdPairsSums {
+  static constexpr int kSlots = 1;
+  const int *__restrict__ sz, *__restrict__ sa;
+  double indiv;
+  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long gi, long gj) const {
+    return pw_r(indiv, (double)cnt[0][reg], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj]);
+  }
+};
+// The one decision of both passes: q = fl(r r), kept iff q >= min_r2 (a NaN r: the comparison is false).  Nothing here can be contracted.
+__device__ __forceinline__ bool ld_pair_keep(double r, double min_r2, double &q) {
+  q = __dmul_rn(r, r);
+  return q >= min_r2;
+}
+
+// One workgroup per window tile.  Element (gi, gj) of the tile is held by the lane the crossproduct epilogue gives it: lane & 31 runs along gj, the two 32-lane
+// halves of a wave hold rows 4 apart, so a ballot is two 32-bit words of the table mask[row][word], word = the row's 32-column sub-block, ascending in gj.
+// Count pass: cnt[tile][row] = the row's popcount.  Write pass: cnt holds rel[tile][row], the row's kept pairs in the tiles to the left (k_ld_pairs_rowscan);
+// position = rowptr[gi] + rel + popcounts of the row's lower words + of its own word below the lane; a position >= capacity is dropped.
+template <bool WRITE, typename Prov, typename Win>
+__global__ void __launch_bounds__(256) k_ld_select(const int *__restrict__ scratch, const int4 *__restrict__ btiles, long n, Prov prov, Win win, double min_r2, int kind,
+                                                   int *__restrict__ cnt, const long *__restrict__ rowptr, int *__restrict__ col, double *__restrict__ val, long capacity) {
+  __shared__ unsigned mask[kXT][8];
+  __shared__ int below[WRITE ? kXT : 1][8];                  // kept pairs of the row in its lower words
+  __shared__ long base[WRITE ? kXT : 1];                     // rowptr[gi] + rel
+  const int4 t = btiles[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
+  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
+  const int4 *slot = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + tid;
+  constexpr size_t kSlotQuads = kPwSlotInts / 4;
+  const int c = lane & 31, hh = lane >> 5;
+  int counts[Prov::kSlots][16];                              // the counts of the current sub-block, in accumulator register order
+  auto load = [&](int a, int b) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int4 *p = slot + ((a * 4 + b) * 4 + q) * 256;
+#pragma unroll
+      for (int k = 0; k < Prov::kSlots; k++) {
+        const int4 w = p[(size_t)k * kSlotQuads];
+        counts[k][4 * q] = w.x; counts[k][4 * q + 1] = w.y; counts[k][4 * q + 2] = w.z; counts[k][4 * q + 3] = w.w;
+      }
+    }
+  };
+#pragma unroll
+  for (int k = 0; k < 8; k++) mask[tid][k] = 0u;             // sub-blocks skipped below keep no pair
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+      if (gj_base + 31 <= gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: no element above the diagonal, or none within the window
+      load(a, b);
+      const long gj = gj_base + c;
+#pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+        const long gi = gi_base + row;
+        bool keep = false;
+        if (gi < gj && gj < n && win.in(gi, gj)) {
+          double q;
+          keep = ld_pair_keep(prov.r(counts, reg, gi, gj), min_r2, q);
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (c == 0) mask[wi * 128 + a * 32 + row][wj * 4 + b] = (unsigned)(bal >> (32 * hh));
+      }
+    }
+  __syncthreads();
+  int *mine = cnt + (size_t)blockIdx.x * kXT + tid;
+  if constexpr (!WRITE) {
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) total += __popc(mask[tid][k]);
+    *mine = total;
+  } else {
+    int run = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { below[tid][k] = run; run += __popc(mask[tid][k]); }
+    base[tid] = i0 + tid < n ? rowptr[i0 + tid] + (long)*mine : 0L;
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+        if (gj_base + 31 <= gi_base || win.beyond(gi_base, gj_base, n)) continue;
+        load(a, b);
+        const long gj = gj_base + c;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+          const int row = wi * 128 + a * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh, word = wj * 4 + b;
+          const unsigned m = mask[row][word];
+          if ((m >> c) & 1u) {                               // kept by the decision above: gi < gj < n
+            const long pos = base[row] + (long)(below[row][word] + __popc(m & ((1u << c) - 1u)));
+            if (pos < capacity) {
+              double q;
+              const double r = prov.r(counts, reg, i0 + row, gj);
+              ld_pair_keep(r, min_r2, q);
+              col[pos] = (int)gj;
+              val[pos] = kind ? q : r;
+            }
+          }
+        }
+      }
+  }
+}
+
+// Between the two passes of a group: one workgroup per tile row I = i_lo + blockIdx.x of the group, thread = row.  cnt over the row's tiles (J ascending,
+// tfirst[I] = the window tiles in front of tile row I) becomes the exclusive offsets rel; the row totals are scanned within the tile row (rowptr[gi] = the
+// offset inside the tile row for now) and the tile row's total goes to rowsum[blockIdx.x].
+__global__ void __launch_bounds__(256) k_ld_pairs_rowscan(int *__restrict__ cnt, const long *__restrict__ tfirst, int i_lo, long n, long *__restrict__ rowptr,
+                                                          long *__restrict__ rowsum) {
+  __shared__ long sc[kXT];
+  const int tid = threadIdx.x, I = i_lo + (int)blockIdx.x;
+  const long t0 = tfirst[I] - tfirst[i_lo], t1 = tfirst[I + 1] - tfirst[i_lo];
+  int run = 0;                                               // < n: fits an int
+  for (long t = t0; t < t1; t++) {
+    int *p = cnt + (size_t)t * kXT + tid;
+    const int v = *p;
+    *p = run;
+    run += v;
+  }
+  sc[tid] = run;
+  __syncthreads();
+  for (int off = 1; off < kXT; off <<= 1) {
+    const long v = tid >= off ? sc[tid - off] : 0L;
+    __syncthreads();
+    sc[tid] += v;
+    __syncthreads();
+  }
+  const long gi = (long)I * kXT + tid;
+  if (gi < n) rowptr[gi] = sc[tid] - run;
+  if (tid == kXT - 1) rowsum[blockIdx.x] = sc[tid];
+}
+// One workgroup: rowsum[0 .. nrows) of the group's tile rows -> their exclusive prefix sums from the running base *base (the pairs of all earlier groups), and
+// *base moves on by the group's total.  Thread t sums a run of consecutive tile rows, the runs are scanned through the LDS.
+__global__ void __launch_bounds__(1024) k_ld_pairs_groupscan(long *__restrict__ rowsum, int nrows, long *__restrict__ base) {
+  __shared__ long sc[1024];
+  const int tid = threadIdx.x, per = (nrows + 1023) / 1024, r0 = min(nrows, tid * per), r1 = min(nrows, r0 + per);
+  const long start = *base;
+  long run = 0;
+  for (int r = r0; r < r1; r++) run += rowsum[r];
+  sc[tid] = run;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const long v = tid >= off ? sc[tid - off] : 0L;
+    __syncthreads();
+    sc[tid] += v;
+    __syncthreads();
+  }
+  long at = start + sc[tid] - run;
+  for (int r = r0; r < r1; r++) { const long v = rowsum[r]; rowsum[r] = at; at += v; }
+  if (tid == 1023) *base = start + sc[tid];
+}
+// rowptr[gi] of the group's rows: the offset inside the tile row plus the tile row's start; behind the last group rowptr[n] = the total
+__global__ void __launch_bounds__(256) k_ld_pairs_rowptr(long *__restrict__ rowptr, const long *__restrict__ rowstart, int i_lo, long n, const long *__restrict__ base, int is_last) {
+  const long gi = ((long)i_lo + blockIdx.x) * kXT + threadIdx.x;
+  if (gi < n) rowptr[gi] += rowstart[blockIdx.x];
+  if (is_last && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) rowptr[n] = *base;
+}
+
+// both routes of the CSR entries (pairwise: the pairwise-complete r; else the plain route with is_plink and freq)
+static int ld_pairs_any(const char *who, const unsigned char *plink, long snps, long indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
+                        long capacity, long *total, bool pairwise, bool is_plink, const double *freq) {
+  if (!last || !rowptr || !total) { set_error(1, "%s: bad arguments", who); return 1; }
+  if ((col == nullptr) != (val == nullptr)) { set_error(1, "%s: col and val must both be given (the filling call) or both be NULL (the count-only call)", who); return 1; }
+  if (col && capacity < 0) { set_error(1, "%s: capacity must not be negative (%ld)", who, capacity); return 1; }
+  if (!(min_r2 >= 0.0) || min_r2 > DBL_MAX) { set_error(1, "%s: min_r2 must be finite and not negative", who); return 1; }
+  const size_t cap = ld_scratch_cap();
+  LdWindow c(who, plink, snps, indiv, 0, last, reinterpret_cast<double *>(rowptr), 0, false, kind);
+  c.set_pairs(col, val, capacity);
+  const int pairs_max = pairwise ? kPwPairs : 1;
+  // the scratch as ld_pairwise_any counts it, the per-(tile, row) counters of a group (1 KiB per window tile), and per tile row tfirst and the row sums
+  auto extra = [&] {
+    const size_t scr = std::min(std::max(cap, c.row_tiles_max * pairs_max * kPwSlotBytes), c.ntiles * pairs_max * kPwSlotBytes);
+    return scr + std::min(c.ntiles, std::max(cap / kPwSlotBytes, c.row_tiles_max)) * kXT * sizeof(int) + sizeof(long) * (2 * (size_t)c.g.nb + 2);
+  };
+  if (c.begin(pairwise ? 3 : 1, extra, pairwise || freq ? nullptr : "%s: allele frequencies are required", pairwise ? kPwMaxIndiv : 0L, "%s",
+              pairwise ? "%s: at most %ld SNPs per call" : "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
+  const XGeom &g = c.g;
+  hipStream_t s = c.s;
+  LdPlainOperand plain;
+  LdPairwiseOperand pw;
+  if (pairwise ? pw.stage(c, plink) : plain.stage(c, plink, is_plink, freq)) return 1;
+  const bool f4 = pairwise ? pw.f4 : plain.f4;
+  const int pairs = pairwise ? pw.pairs : 1;
+  LdGroups gr(c, cap, pairs);
+  std::vector<long> tfirst((size_t)g.nb + 1, 0);
+  for (int I = 0; I < g.nb; I++) tfirst[(size_t)I + 1] = tfirst[(size_t)I] + (c.jmax[(size_t)I] - I + 1);
+  XTiles t;
+  XBuf d_scr, d_bt, d_cnt, d_rows;                           // d_rows: tfirst (nb + 1 longs), the groups' row sums (nb), the running base (1)
+  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
+  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * kPwSlotBytes) || d_cnt.alloc(gr.tiles_max * kXT * sizeof(int)) ||
+      d_rows.alloc(sizeof(long) * (2 * (size_t)g.nb + 2))) return 1;
+  long *d_tfirst = (long *)d_rows.p, *d_rowsum = d_tfirst + g.nb + 1, *d_base = d_rowsum + g.nb;
+  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  MXA_HIP(hipMemcpyAsync(d_tfirst, tfirst.data(), sizeof(long) * tfirst.size(), hipMemcpyHostToDevice, s));
+  MXA_HIP(hipMemsetAsync(d_base, 0, sizeof(long), s));
+  if (c.start()) return 1;
+  const XPost none{};
+  const LdVarWindow win{(const int *)c.d_last.p, nullptr, c.ndiag};
+  long *d_rowptr = c.d_pairs_rowptr();
+  for (int q = 0; q < gr.n; q++) {
+    // the group's products into the scratch; count; scan (the running base crosses the groups on the device: the host does not wait); write
+    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
+    const dim3 grid((unsigned)(gr.band_first[(size_t)q + 1] - gr.band_first[(size_t)q]));
+    const int4 *bt = (const int4 *)d_bt.p + gr.band_first[(size_t)q];
+    const int i_lo = gr.row0[(size_t)q], nrows = gr.row0[(size_t)q + 1] - i_lo;
+    auto select = [&](auto write, auto prov) {
+      hipLaunchKernelGGL((k_ld_select<decltype(write)::value, decltype(prov), LdVarWindow>), grid, dim3(256), 0, s, (const int *)d_scr.p, bt, snps, prov, win, min_r2, kind,
+                         (int *)d_cnt.p, (const long *)d_rowptr, c.d_pairs_col(), c.d_pairs_val(), c.capacity);
+    };
+    auto pass = [&](auto write) {
+      if (!pairwise) select(write, LdPairsPlain{plain.xp.u, plain.xp.w, plain.xp.a});
+      else if (pw.dense) select(write, LdPairsCounts{});
+      else select(write, LdPairsSums{pw.d_sz, pw.d_sa, (double)indiv});
+    };
+    pass(std::false_type());
+    hipLaunchKernelGGL(k_ld_pairs_rowscan, dim3((unsigned)nrows), dim3(256), 0, s, (int *)d_cnt.p, (const long *)d_tfirst, i_lo, snps, d_rowptr, d_rowsum);
+    hipLaunchKernelGGL(k_ld_pairs_groupscan, dim3(1), dim3(1024), 0, s, d_rowsum, nrows, d_base);
+    hipLaunchKernelGGL(k_ld_pairs_rowptr, dim3((unsigned)nrows), dim3(256), 0, s, d_rowptr, (const long *)d_rowsum, i_lo, snps, (const long *)d_base, q == gr.n - 1 ? 1 : 0);
+    if (c.fill) pass(std::true_type());
+    MXA_HIP(hipGetLastError());
+  }
+  if (c.finish_pairs(d_base, total)) return 1;
+  debug_info("%s: %d group(s), %d product(s) per window tile, %s engine, %ld pairs", who, gr.n, pairs, f4 ? "FP4" : "int8", *total);
   return 0;
 }
 
@@ -1855,6 +2189,19 @@ extern "C" int mxa_ld_window_scores_pairwise(const unsigned char *plink, int snp
   mxa::clear_error();
   if (!last) { mxa::set_error(1, "mxa_ld_window_scores_pairwise: bad arguments"); return 1; }
   return mxa::ld_pairwise_any("mxa_ld_window_scores_pairwise", plink, snps, indiv, 0, last, scores, 0, true, adjust);
+}
+
+// ---- the pairs of a window with r^2 >= min_r2 as CSR of the strict upper triangle
+extern "C" int mxa_ld_window_pairs(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
+                                   long capacity, long *total, int is_plink_format, const double *allele_freq) {
+  mxa::clear_error();
+  return mxa::ld_pairs_any("mxa_ld_window_pairs", plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, false, is_plink_format != 0, allele_freq);
+}
+
+extern "C" int mxa_ld_window_pairs_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
+                                            long capacity, long *total) {
+  mxa::clear_error();
+  return mxa::ld_pairs_any("mxa_ld_window_pairs_pairwise", plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, true, true, nullptr);
 }
 
 // The window ends of a distance window, on the host (no device is touched): last[i] = the largest j >= i on i's chromosome with pos[j] - pos[i] <= max_dist

@@ -16,6 +16,7 @@
 #   ld-band [snps indiv window]   windowed LD (mxa_ld_band / mxa_ld_scores): kernel time, tiles, bytes written, both engines; band vs full mxa_ld (A/B)
 #   ld-pairwise [snps indiv window]   pairwise-complete windowed LD (mxa_ld_band_pairwise / mxa_ld_scores_pairwise) against mxa_ld_band / mxa_ld_scores, one process, both engines
 #   ld-window-var [snps indiv window]   windowed LD over last[] (mxa_ld_window_rows / mxa_ld_window_scores) against mxa_ld_band / mxa_ld_scores, one process, both engines; a density profile
+#   ld-pairs [snps indiv window min_r2]   pairs with r^2 >= min_r2 as CSR (mxa_ld_window_pairs / _pairwise) against mxa_ld_window_rows(_pairwise), one process, both engines
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -114,6 +115,9 @@ ld-pairwise)
 ld-window-var)
   # the general entries with last[i] = min(i + window, snps - 1) against the fixed ones (same tiles), then a density profile with the same mean reach, alternating calls
   timeout -k 10 500 python3 tools/perf_ld_window_var.py ${1:-1000000} ${2:-50000} ${3:-1023} 5 2>&1 | tee -a "$O/ld_window_var.txt" || exit 1 ;;
+ld-pairs)
+  # count-only and filling calls of the pairs entries against the rows entries over the same last[], plain and pairwise (5 % missing; no missing code: one product), alternating calls
+  timeout -k 10 500 python3 tools/perf_ld_pairs.py ${1:-1000000} ${2:-50000} ${3:-1023} ${4:-0.2} 5 2>&1 | tee -a "$O/ld_pairs.txt" || exit 1 ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

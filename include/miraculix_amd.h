@@ -405,6 +405,34 @@ int mxa_ld_window_pairs(const unsigned char *plink, int snps, int indiv, const i
 int mxa_ld_window_pairs_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col,
                                  double *val, long capacity, long *total);
 
+/* LD pruning and clumping: the greedy selection on the pairs graph, on the device (what PLINK's --indep-pairwise / --clump and bigsnpr's snp_clumping ask for:
+ * a subset of SNPs in which no two within the window are in LD above a threshold, chosen in priority order).
+ * G is the graph on the SNPs 0 .. snps - 1 whose edges are exactly the pairs mxa_ld_window_pairs(_pairwise) keeps for the same plink, last, min_r2 and route:
+ * i < j <= last[i], q = fl(r^ * r^) >= min_r2, a NaN r^ is never an edge.  SNP a comes before SNP b iff priority[a] < priority[b], or the priorities are equal
+ * and a < b; priority == NULL: iff a < b.  Smaller goes first: p-values for clumping, -MAF for pruning.  Result: walk the SNPs in that order and keep a SNP iff
+ * none of its neighbours in G has been kept.  This is the lexicographically first maximal independent set of G under the order; it is unique, so keep, owner,
+ * *n_kept and *rounds do not depend on the engine, the pointer kinds, the scratch size or any schedule.
+ * keep: snps bytes of 0 / 1.  owner (optional, NULL skips its pass): snps ints, owner[v] = v for a kept v, else the first kept neighbour of v in the order -- the
+ * SNP that removes v in the walk, PLINK's index SNP of v's clump.  keep and owner: both host or both device pointers.  n_kept: a host pointer, required.
+ * rounds (optional, a host pointer): the number of rounds the device ran = the length of the longest dependency chain; small for priorities unrelated to
+ * position (p-values, MAF), about snps for priority == NULL on a long run of mutual LD (a path in index order takes snps rounds), each round two launches and
+ * one sweep over the rows.  *rounds <= snps always.
+ * mxa_ld_prune_csr: the graph step alone on any CSR of the strict upper triangle, e.g. the one mxa_ld_window_pairs returned (one pair list, several
+ * priorities, no second product).  rowptr (snps + 1 longs), col, priority: host or device pointers, each independently; col may be NULL when rowptr[snps] == 0.
+ * The CSR is checked where it lies (host loop, or a checking kernel whose flag the host reads): rowptr[0] == 0, rowptr non-decreasing, in every row
+ * i < col < snps strictly ascending.
+ * mxa_ld_window_prune(_pairwise): the pairs driver and the graph step; neither the pair list nor a val array leaves the device or is ever formed for the host.
+ * A count-only pass sizes col exactly, a filling pass writes col alone: the window's products run twice, as in the count-then-fill use of mxa_ld_window_pairs.
+ * snps == 1 is legal: keep = {1}, owner = {0}.
+ * Errors (return 1, mxa_last_error() == 1, outputs untouched): keep or n_kept NULL; keep / owner not both host or both device; a NaN in priority (+-inf is
+ * legal); mxa_ld_prune_csr: snps <= 0, rowptr NULL, a CSR that fails the check; the window entries: everything mxa_ld_window_pairs(_pairwise) rejects for these
+ * arguments.  12: not enough device memory (col, rowptr, the per-SNP state and owner arrays, and the scratch as the pairs entries count it). */
+int mxa_ld_prune_csr(int snps, const long *rowptr, const int *col, const double *priority, unsigned char *keep, int *owner, long *n_kept, int *rounds);
+int mxa_ld_window_prune(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, const double *priority, unsigned char *keep, int *owner,
+                        long *n_kept, int *rounds, int is_plink_format, const double *allele_freq);
+int mxa_ld_window_prune_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, const double *priority, unsigned char *keep,
+                                 int *owner, long *n_kept, int *rounds);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -18,6 +18,7 @@ module modmiraculix_amd
  public :: mxa_ld_band_pairwise, mxa_ld_scores_pairwise
  public :: mxa_ld_window_bounds, mxa_ld_window_rows, mxa_ld_window_scores, mxa_ld_window_rows_pairwise, mxa_ld_window_scores_pairwise
  public :: mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise
+ public :: mxa_ld_prune_csr, mxa_ld_window_prune, mxa_ld_window_prune_pairwise
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -218,6 +219,32 @@ module modmiraculix_amd
    integer(c_int), value, intent(in) :: snps, indiv, kind
    real(c_double), value, intent(in) :: min_r2
    integer(c_long), value, intent(in) :: capacity
+   integer(c_int) :: rc
+  end function
+
+  ! LD pruning / clumping: the greedy selection on the pairs graph (edges: the pairs above; order: smaller priority first, ties by index; priority =
+  ! c_null_ptr: index order).  keep: snps bytes of 0 / 1; owner (c_null_ptr skips it): snps C ints, 0-based, the index SNP of a dropped SNP's clump; keep
+  ! and owner both host or both device.  n_kept: c_loc of an integer(c_long), rounds (or c_null_ptr): c_loc of an integer(c_int), both on the host.
+  function mxa_ld_prune_csr(snps, rowptr, col, priority, keep, owner, n_kept, rounds) bind(C, name='mxa_ld_prune_csr') result(rc)
+   import c_int, c_ptr
+   integer(c_int), value, intent(in) :: snps
+   type(c_ptr), value, intent(in) :: rowptr, col, priority, keep, owner, n_kept, rounds
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_prune(plink, snps, indiv, last, min_r2, priority, keep, owner, n_kept, rounds, is_plink_format, allele_freq) &
+      bind(C, name='mxa_ld_window_prune') result(rc)
+   import c_int, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, priority, keep, owner, n_kept, rounds, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, is_plink_format
+   real(c_double), value, intent(in) :: min_r2
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_prune_pairwise(plink, snps, indiv, last, min_r2, priority, keep, owner, n_kept, rounds) &
+      bind(C, name='mxa_ld_window_prune_pairwise') result(rc)
+   import c_int, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, priority, keep, owner, n_kept, rounds
+   integer(c_int), value, intent(in) :: snps, indiv
+   real(c_double), value, intent(in) :: min_r2
    integer(c_int) :: rc
   end function
 

@@ -345,3 +345,89 @@ def ld_pairs(plink, snps, indiv, last=None, window=None, min_r2=0.2, kind="r2", 
     col, val = new(int(capacity), np.int32), new(int(capacity), np.float64)
     _check(call(col, val, int(capacity)), entry)               # error 25: the message names the total and the capacity
     return rowptr, col[: total.value], val[: total.value]
+
+
+# ---- LD pruning / clumping, the greedy selection on the pairs graph: C entries mxa_ld_window_prune / mxa_ld_window_prune_pairwise / mxa_ld_prune_csr
+def _prune_priority(priority, snps):
+    """priority as the C entries take it (None, float64 numpy, or a contiguous float64 tensor); NaN is refused here, the library checks again"""
+    if priority is None:
+        return None
+    if _lib.is_torch_tensor(priority):
+        import torch
+        if priority.dtype != torch.float64 or priority.numel() != snps:
+            raise ValueError(f"priority needs to be {snps} float64 values")
+        if bool(torch.isnan(priority).any()):
+            raise ValueError("priority must not hold a NaN")
+        return priority.contiguous()
+    priority = np.ascontiguousarray(priority, dtype=np.float64)
+    if priority.shape != (snps,):
+        raise ValueError(f"priority needs to be {snps} float64 values")
+    if np.isnan(priority).any():
+        raise ValueError("priority must not hold a NaN")
+    return priority
+
+
+def _prune_call(like, snps, return_owner, return_rounds, entry, call):
+    """keep / owner next to `like` (numpy, or torch on like's device), the call, and the results in the order (keep[, owner][, rounds])"""
+    import ctypes
+    if _lib.is_torch_tensor(like):
+        import torch
+        keep = torch.zeros(snps, dtype=torch.uint8, device=like.device)
+        owner = torch.zeros(snps, dtype=torch.int32, device=like.device) if return_owner else None
+    else:
+        keep = np.zeros(snps, dtype=np.uint8)
+        owner = np.zeros(snps, dtype=np.int32) if return_owner else None
+    n_kept, rounds = ctypes.c_long(0), ctypes.c_int(0)
+    _check(call(_lib.ptr(keep), _lib.ptr(owner), ctypes.byref(n_kept), ctypes.byref(rounds)), entry)
+    keep = keep.bool() if _lib.is_torch_tensor(keep) else keep.astype(bool)
+    out = (keep,) + ((owner,) if return_owner else ()) + ((rounds.value,) if return_rounds else ())
+    return out[0] if len(out) == 1 else out
+
+
+def ld_prune(plink, snps, indiv, last=None, window=None, min_r2=0.2, priority=None, pairwise=False, is_plink_format=False, allele_freq=None, return_owner=False,
+             return_rounds=False):
+    """Additive (C entries mxa_ld_window_prune, mxa_ld_window_prune_pairwise): LD pruning / clumping on the device.  The graph: the pairs ld_pairs() lists for
+    the same plink, last | window, min_r2 and route.  The order: smaller priority first, ties by index (priority=None: index order) -- p-values for clumping,
+    -MAF for pruning.  The result: walk the SNPs in that order, keep a SNP iff none of its neighbours has been kept (unique: the same on every engine).
+    Returns keep (bool, snps), or (keep, owner) with return_owner: owner[v] = v for a kept SNP, else the kept neighbour that removed it (int32; PLINK's index
+    SNP of the clump); return_rounds appends the number of rounds the device ran (the longest dependency chain).  numpy, or torch tensors on plink's device.
+    Exactly one of `last` and `window` is given, as for ld_pairs().  The pair list stays on the device; the window's products run twice (count, fill)."""
+    if (last is None) == (window is None):
+        raise ValueError("exactly one of last and window is needed")
+    if not pairwise and (allele_freq is None or len(allele_freq) != snps):
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    if window is not None:
+        if not 0 <= int(window) < snps:
+            raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+        last = np.minimum(np.arange(snps, dtype=np.int64) + int(window), snps - 1).astype(np.int32)
+    last, _ = _ld_last_args(plink, snps, indiv, last)
+    priority = _prune_priority(priority, snps)
+    L = _lib.check_library_handle()
+    entry = "mxa_ld_window_prune_pairwise" if pairwise else "mxa_ld_window_prune"
+    tail = []
+    if not pairwise:
+        f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+        tail = [int(bool(is_plink_format)), _lib.ptr(f)]
+    return _prune_call(plink, snps, return_owner, return_rounds, entry, lambda keep, owner, n_kept, rounds: getattr(L, entry)(
+        _lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), float(min_r2), _lib.ptr(priority), keep, owner, n_kept, rounds, *tail))
+
+
+def ld_prune_csr(rowptr, col, priority=None, return_owner=False, return_rounds=False):
+    """Additive (C entry mxa_ld_prune_csr): the graph step of ld_prune() alone, on a CSR of the strict upper triangle such as ld_pairs() returns (rowptr int64
+    of snps + 1, col int32, ascending in a row) -- one pair list pruned under several priorities without repeating the products.  Results as ld_prune(), next
+    to rowptr (numpy, or torch on rowptr's device)."""
+    def arr(a, np_dt, what):
+        if _lib.is_torch_tensor(a):
+            import torch
+            if a.dtype != {np.int64: torch.int64, np.int32: torch.int32}[np_dt]:
+                raise ValueError(f"{what} needs to be {np.dtype(np_dt).name}")
+            return a.contiguous()
+        return np.ascontiguousarray(a, dtype=np_dt)
+    rowptr, col = arr(rowptr, np.int64, "rowptr"), arr(col, np.int32, "col")
+    snps = int(np.prod(rowptr.shape)) - 1
+    if snps < 1:
+        raise ValueError("rowptr needs snps + 1 >= 2 entries")
+    priority = _prune_priority(priority, snps)
+    L = _lib.check_library_handle()
+    return _prune_call(rowptr, snps, return_owner, return_rounds, "mxa_ld_prune_csr", lambda keep, owner, n_kept, rounds: L.mxa_ld_prune_csr(
+        int(snps), _lib.ptr(rowptr), _lib.ptr(col) if int(np.prod(col.shape)) else None, _lib.ptr(priority), keep, owner, n_kept, rounds))

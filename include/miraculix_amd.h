@@ -433,6 +433,30 @@ int mxa_ld_window_prune(const unsigned char *plink, int snps, int indiv, const i
 int mxa_ld_window_prune_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, const double *priority, unsigned char *keep,
                                  int *owner, long *n_kept, int *rounds);
 
+/* The window applied to a matrix: Y = T_w(R) X without the rows.  Y[i, c] = sum over first[i] <= j <= last[i] of t(r_ij) X[j, c], first[i] = min{k: last[k] >= i}
+ * as in mxa_ld_window_scores; for j < i the value is that of the pair (j, i), the diagonal is one term, counted once.  mxa_ld_window_scores is this product
+ * with n = 1, X = 1.  Uses: partitioned (stratified) LD scores l(i, c) = sum_j r2_ij a_jc for an annotation matrix a (ldsc --l2 --annot), MAF-binned or
+ * weighted scores (indicator or weight columns), and R_w X with t = r for summary-statistics methods (one call per product of a conjugate-gradient solve).
+ * plink, snps, indiv, last, is_plink_format, allele_freq: exactly as for mxa_ld_window_rows / mxa_ld_window_rows_pairwise (staging, byte table, statistics,
+ * engines, bounds, the missing-free shortcut); a fixed window is last[i] = min(i + w, snps - 1).
+ * X: snps x n, column-major, ldx >= snps; Y: snps x n, column-major, ldy >= snps (dgemm_compressed's B / C).  X and Y are each a host or a device pointer,
+ * independently.  Rows snps .. ldy - 1 of a column of Y are never written, nor is anything beyond column n - 1.
+ * term: 0: t = r^; 1: t = fl(r^ r^); 2: the adjusted term of the scores entries -- plain route r2 - (1 - r2) (1 / (indiv - 2)), pairwise route
+ * r2 - ((1 - r2) / (N_ij - 2)) with the pair's own N_ij.  r^ is bit for bit the value mxa_ld_window_rows(_pairwise) stores for the pair at kind 0.
+ * NaN: a monomorphic SNP (plain route) or a pair with dx dy = 0 (pairwise route) makes its term NaN, and every Y[i, .] whose window holds it is then NaN, even
+ * where X[j, c] = 0: filter such SNPs before the call.  (An element outside the window is skipped, never multiplied: X may hold anything there.)
+ * Every Y[i, c] is a sum in a fixed order, no floating-point atomics: Y is identical from run to run, between the FP4 and the int8 engine
+ * (MXA_XPROD_ENGINE=i8), between host and device pointers, for every MXA_LD_PAIRWISE_SCRATCH_MB, and for every n: column c of an n-column call is bit for
+ * bit the one-column call on that column.  The window's tile products run once, into the int32 count tiles of the pairs entries; per window tile
+ * 4 KiB n of partial sums share the scratch cap with them.
+ * Errors (return 1, mxa_last_error() == 1, Y untouched): everything mxa_ld_window_rows(_pairwise) rejects; X or Y NULL; n < 1 (or n > 1 048 560); ldx < snps
+ * or ldy < snps; term not 0, 1 or 2; term == 2 with indiv < 3.  12: not enough device memory (the scratch, the partial sums and the device copies of a host
+ * X / Y are counted). */
+int mxa_ld_window_apply(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y, long ldy,
+                        int is_plink_format, const double *allele_freq);
+int mxa_ld_window_apply_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y,
+                                 long ldy);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -19,6 +19,7 @@ module modmiraculix_amd
  public :: mxa_ld_window_bounds, mxa_ld_window_rows, mxa_ld_window_scores, mxa_ld_window_rows_pairwise, mxa_ld_window_scores_pairwise
  public :: mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise
  public :: mxa_ld_prune_csr, mxa_ld_window_prune, mxa_ld_window_prune_pairwise
+ public :: mxa_ld_window_apply, mxa_ld_window_apply_pairwise
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -245,6 +246,23 @@ module modmiraculix_amd
    type(c_ptr), value, intent(in) :: plink, last, priority, keep, owner, n_kept, rounds
    integer(c_int), value, intent(in) :: snps, indiv
    real(c_double), value, intent(in) :: min_r2
+   integer(c_int) :: rc
+  end function
+
+  ! the window applied to a matrix: Y = T_w(R) X, X and Y snps x n column-major (Fortran arrays x(ldx, n), y(ldy, n)), host or device each; term 0: r,
+  ! 1: r * r, 2: the adjusted term of the scores.  Rows beyond snps of y are not written.  Every sum runs in a fixed order (the same bits for every n).
+  function mxa_ld_window_apply(plink, snps, indiv, last, term, X, ldx, n, Y, ldy, is_plink_format, allele_freq) bind(C, name='mxa_ld_window_apply') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, X, Y, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, term, n, is_plink_format
+   integer(c_long), value, intent(in) :: ldx, ldy
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_window_apply_pairwise(plink, snps, indiv, last, term, X, ldx, n, Y, ldy) bind(C, name='mxa_ld_window_apply_pairwise') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, X, Y
+   integer(c_int), value, intent(in) :: snps, indiv, term, n
+   integer(c_long), value, intent(in) :: ldx, ldy
    integer(c_int) :: rc
   end function
 

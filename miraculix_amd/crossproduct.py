@@ -347,6 +347,69 @@ def ld_pairs(plink, snps, indiv, last=None, window=None, min_r2=0.2, kind="r2", 
     return rowptr, col[: total.value], val[: total.value]
 
 
+# ---- the window applied to a matrix, Y = T_w(R) X: C entries mxa_ld_window_apply / mxa_ld_window_apply_pairwise
+LD_APPLY_TERMS = {"r": 0, "r2": 1, "r2_adj": 2}
+LD_APPLY_NC = 16                                              # columns of X per workgroup of the tile kernel (kLdApplyNC)
+
+
+def ld_window_apply(plink, snps, indiv, X, last=None, window=None, term="r2", pairwise=False, is_plink_format=False, allele_freq=None, out=None):
+    """Additive (C entries mxa_ld_window_apply, mxa_ld_window_apply_pairwise): Y = T_w(R) X, Y[i, c] = sum over the window of SNP i (first[i] <= j <= last[i],
+    both sides of i) of t(r_ij) X[j, c], without writing the window's rows.  X: (snps, n) or (snps,) float64, numpy or a torch tensor (host / device); the
+    result has X's shape and kind.  term "r" (t = r: R_w X), "r2" (partitioned LD scores) or "r2_adj" (the adjusted term of the scores entries).  Exactly one of
+    `last` and `window`, as for ld_pairs().  Every sum runs in a fixed order: the same bits for every engine, pointer kind, scratch size and n.  A monomorphic
+    SNP makes every row whose window holds it NaN: filter first.  out: a (snps, n) result to fill, Fortran-ordered numpy or a torch tensor whose transpose is
+    contiguous (n rows of snps values)."""
+    if term not in LD_APPLY_TERMS:
+        raise ValueError(f"term needs to be 'r', 'r2' or 'r2_adj': {term!r}")
+    if (last is None) == (window is None):
+        raise ValueError("exactly one of last and window is needed")
+    if not pairwise and (allele_freq is None or len(allele_freq) != snps):
+        raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+    if term == "r2_adj" and indiv < 3:
+        raise ValueError(f"The adjusted estimator needs at least 3 individuals: {indiv}")
+    shape = tuple(X.shape)
+    if len(shape) not in (1, 2) or shape[0] != snps or (len(shape) == 2 and shape[1] < 1):
+        raise ValueError(f"X needs to be ({snps},) or ({snps}, n >= 1): {shape}")
+    n = 1 if len(shape) == 1 else int(shape[1])
+    if window is not None:
+        if not 0 <= int(window) < snps:
+            raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+        last = np.minimum(np.arange(snps, dtype=np.int64) + int(window), snps - 1).astype(np.int32)
+    last, _ = _ld_last_args(plink, snps, indiv, last)
+    # column-major operands: n contiguous columns of snps values
+    if _lib.is_torch_tensor(X):
+        import torch
+        if X.dtype != torch.float64:
+            raise ValueError("X needs to be float64")
+        xc = X.reshape(snps, n).t().contiguous()              # (n, snps) row-major = (snps, n) column-major
+        yc = torch.zeros((n, snps), dtype=torch.float64, device=X.device) if out is None else out.t()
+        if out is not None and (tuple(out.shape) != (snps, n) or out.dtype != torch.float64 or not yc.is_contiguous()):
+            raise ValueError(f"out needs to be a float64 ({snps}, {n}) tensor with contiguous columns")
+    else:
+        xc = np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(snps, n).T)
+        yc = np.zeros((n, snps), dtype=np.float64) if out is None else out.T
+        if out is not None and (out.shape != (snps, n) or out.dtype != np.float64 or not yc.flags.c_contiguous):
+            raise ValueError(f"out needs to be a float64 ({snps}, {n}) array in Fortran order")
+    L = _lib.check_library_handle()
+    head = [_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), LD_APPLY_TERMS[term], _lib.ptr(xc), int(snps), n, _lib.ptr(yc), int(snps)]
+    if pairwise:
+        _check(L.mxa_ld_window_apply_pairwise(*head), "mxa_ld_window_apply_pairwise")
+    else:
+        f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+        _check(L.mxa_ld_window_apply(*head, int(bool(is_plink_format)), _lib.ptr(f)), "mxa_ld_window_apply")
+    if out is not None:
+        return out
+    Y = yc.t() if _lib.is_torch_tensor(yc) else yc.T
+    return Y.reshape(shape)
+
+
+def ld_scores_partitioned(plink, snps, indiv, annot, last=None, window=None, adjust=False, pairwise=False, is_plink_format=False, allele_freq=None):
+    """Partitioned (stratified) LD scores l(i, c) = sum over the window of SNP i of t(r_ij) annot[j, c] (ldsc --l2 --annot; the input of S-LDSC): annot is
+    (snps, n) -- a base column of ones gives ld_window_scores() up to the order of the sums.  adjust: the adjusted term.  A wrapper of ld_window_apply()."""
+    return ld_window_apply(plink, snps, indiv, annot, last=last, window=window, term="r2_adj" if adjust else "r2", pairwise=pairwise,
+                           is_plink_format=is_plink_format, allele_freq=allele_freq)
+
+
 # ---- LD pruning / clumping, the greedy selection on the pairs graph: C entries mxa_ld_window_prune / mxa_ld_window_prune_pairwise / mxa_ld_prune_csr
 def _prune_priority(priority, snps):
     """priority as the C entries take it (None, float64 numpy, or a contiguous float64 tensor); NaN is refused here, the library checks again"""

@@ -1476,6 +1476,8 @@ struct LdWindow {
   int *col = nullptr;
   double *val = nullptr;
   long capacity = 0;           // entries of col / val (0 on a count-only call)
+  bool apply = false;          // the window applied to a matrix (mxa_ld_window_apply*): out = Y, ldb = ldy, result = snps x ncols
+  int ncols = 0;
   XGeom g;
   long row_bytes = 0;
   int ndiag = 0;               // tile diagonals of the partial buffer: the kernels' (ld_band_diagonals(window)), or max(jmax[I] - I)
@@ -1498,6 +1500,7 @@ struct LdWindow {
   long post_c0() const { return general() ? (long)ndiag : window; }
   void set_post(XPost &xp) const { xp.do_scale = flag; xp.last = (const int *)d_last.p; xp.rowptr = (const long *)d_rowptr.p; }
   std::vector<int4> tiles() const { return window_tiles(jmax); }
+  void set_apply(int ncols_) { apply = true; ncols = ncols_; }
   void set_pairs(int *col_, double *val_, long capacity_) { pairs = true; fill = col_ != nullptr; col = col_; val = val_; capacity = fill ? capacity_ : 0; }
   // where the CSR result is formed on the device: the caller's arrays, or the pieces of d_out
   long *d_pairs_rowptr() const { return out_dev ? reinterpret_cast<long *>(out) : (long *)d_out.p; }
@@ -1567,6 +1570,7 @@ struct LdWindow {
     plane_bytes = (size_t)g.rows_pad() * g.pitch();
     obytes = sizeof(double) * (scores ? (size_t)snps : general() ? (size_t)h_rowptr.back() : (size_t)(window + 1) * (size_t)snps);
     if (pairs) obytes = sizeof(long) * ((size_t)snps + 1) + (sizeof(double) + sizeof(int)) * (size_t)capacity;
+    if (apply) obytes = sizeof(double) * (size_t)snps * (size_t)ncols;   // a host Y leaves from a compact device copy (leading dimension snps)
     const size_t pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
     const size_t wbytes = sizeof(int) * (size_t)g.nb + (general() ? sizeof(int) * (size_t)snps + sizeof(long) * ((size_t)snps + 1) : 0);   // jmax, last, rowptr
     size_t free_b = 0, total_b = 0;
@@ -1582,7 +1586,7 @@ struct LdWindow {
       MXA_HIP(hipMemcpy(d_jmax.p, jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice));
     }
     if (general()) {
-      const bool rows = !scores && !pairs;   // the ragged rows' starts
+      const bool rows = !scores && !pairs && !apply;   // the ragged rows' starts
       if (d_last.alloc(sizeof(int) * (size_t)snps) || (rows && d_rowptr.alloc(sizeof(long) * ((size_t)snps + 1)))) return 1;
       MXA_HIP(hipMemcpy(d_last.p, h_last.data(), sizeof(int) * (size_t)snps, hipMemcpyHostToDevice));
       if (rows) MXA_HIP(hipMemcpy(d_rowptr.p, h_rowptr.data(), sizeof(long) * ((size_t)snps + 1), hipMemcpyHostToDevice));
@@ -1601,6 +1605,14 @@ struct LdWindow {
     MXA_HIP(hipEventRecord(e1.e, s));
     if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores || general(), s)) return 1;
     MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
+    MXA_HIP(profile_launch(e0, e1));
+    return 0;
+  }
+  // the applied window: Y is complete on the device (d_res, leading dimension out_dev ? ldb : snps); a host Y takes its snps rows of every column
+  int finish_apply() {
+    MXA_HIP(hipEventRecord(e1.e, s));
+    if (!out_dev) MXA_HIP(hipMemcpy2DAsync(out, sizeof(double) * (size_t)ldb, d_res, sizeof(double) * (size_t)snps, sizeof(double) * (size_t)snps, (size_t)ncols, hipMemcpyDeviceToHost, s));
+    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics, scratch and partials
     MXA_HIP(profile_launch(e0, e1));
     return 0;
   }
@@ -1784,13 +1796,15 @@ struct LdGroups {
   std::vector<int4> band;
   std::vector<size_t> band_first;
   size_t tiles_max = 0;
-  LdGroups(const LdWindow &c, size_t cap, int pairs) : row0{0} {
+  // tile_extra: bytes a window tile holds next to its count slots under the same cap (the partials of the apply entries)
+  LdGroups(const LdWindow &c, size_t cap, int pairs, size_t tile_extra = 0) : row0{0} {
     const XGeom &g = c.g;
+    const size_t tile_bytes = (size_t)pairs * kPwSlotBytes + tile_extra;
     if (!c.general()) {
-      const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * (size_t)pairs * kPwSlotBytes)));
+      const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * tile_bytes)));
       for (int i = rows_per_group; i < g.nb; i += rows_per_group) row0.push_back(i);
     } else {
-      const size_t cap_tiles = cap / ((size_t)pairs * kPwSlotBytes);
+      const size_t cap_tiles = cap / tile_bytes;
       size_t held = 0;
       for (int i = 0; i < g.nb; i++) {
         const size_t t = (size_t)(c.jmax[(size_t)i] - i + 1);
@@ -2144,6 +2158,263 @@ static int ld_pairs_any(const char *who, const unsigned char *plink, long snps, 
   }
   if (c.finish_pairs(d_base, total)) return 1;
   debug_info("%s: %d group(s), %d product(s) per window tile, %s engine, %ld pairs", who, gr.n, pairs, f4 ? "FP4" : "int8", *total);
+  return 0;
+}
+
+// ---- the window applied to a matrix (mxa_ld_window_apply, mxa_ld_window_apply_pairwise): Y = T_w(R) X, Y[i, c] = sum over first[i] <= j <= last[i] of
+// t(r_ij) X[j, c], X and Y snps x n column-major.  Neither the rows nor the band are written: both routes run the window's tile products once into the count
+// scratch (kPostCounts, the groups of LdGroups, as the CSR entries do), k_ld_apply_tile turns every window tile into two partials per chunk of kLdApplyNC
+// columns -- the I side P_I[i][c] = sum_j t_ij X[j, c] over the tile's elements i <= j, the J side P_J[j][c] = sum_i t_ij X[i, c] over its elements i < j --
+// and k_ld_apply_finish adds the partials of a group to Y in the canonical order of a row block B: the J sides of the tiles (I, B), I ascending, then the I
+// sides of the tiles (B, J), J ascending.  Groups are consecutive tile rows and the running sum passes through Y between them, so the association of every
+// sum is the same for every group partition; inside a tile the order is fixed by the lane <-> element map alone and every column runs the same
+// instructions, so it does not depend on the engine, on where the pointers live, on the scratch size or on n.  No floating-point atomics.
+// t: term 0 = r, the providers' value (bit for bit what the rows entries store at kind 0); 1 = fl(r r); 2 = the adjusted term of the scores entries -- the
+// plain route r2 - (1 - r2) (1 / (indiv - 2)) as xprod_store_window forms it, the pairwise route with the pair's own N as pw_value<true> does.
+constexpr int kLdApplyNC = 16;                                          // columns of X per workgroup
+constexpr int kLdApplyXBytes = 2 * kXT * kLdApplyNC * 8;                // xs[side][row][NC]: the X rows of tile rows I and J; afterwards the two halves of a side's partial
+constexpr int kLdApplyLds = kLdApplyXBytes + kXScratchBytes + 4 * 32 * 4;   // + the four waves' 32 x 33 sub-block of t and their 32 row masks: 99 840 bytes
+constexpr long kLdApplyMaxCols = 65535L * kLdApplyNC;                   // grid.y
+
+template <typename Prov>
+__device__ __forceinline__ double ld_apply_term(const Prov &prov, const int (&cnt)[Prov::kSlots][16], int reg, long gi, long gj, int term, double inv_adj) {
+  // Every operation below is rounded on its own.  They are written as operators under this pragma and not as __dmul_rn / __dsub_rn: those are plain operators
+  // inside the toolchain's header, compiled there with contraction allowed, and once inlined the compiler fuses r r - p or r2 - q g into an fma all the same.
+#pragma clang fp contract(off)
+  const double r = prov.r(cnt, reg, gi, gj);
+  if (term == 0) return r;
+  const double r2 = r * r;
+  if (term == 1) return r2;
+  const double q = 1.0 - r2;
+  if constexpr (__is_same(Prov, LdPairsPlain)) {
+    const double p = q * inv_adj;
+    return r2 - p;
+  } else {
+    double N;
+    if constexpr (__is_same(Prov, LdPairsCounts)) N = (double)cnt[0][reg]; else N = prov.indiv;
+    const double p = q / (N - 2.0);
+    return r2 - p;
+  }
+}
+
+// Grid (window tiles of the group, column chunks).  The counts are read with the lane <-> element map of k_ld_select; a wave takes its 128 x 128 quadrant
+// sub-block by sub-block: t of the 32 x 32 sub-block goes to the wave's padded LDS scratch (0 outside the window) and the row masks of the ballot say which
+// elements count -- an element outside the window is skipped, not multiplied.  Then lane (c = lane & 31, hh = lane >> 5) owns the 8 columns 8 hh .. 8 hh + 7
+// of the chunk: for the J side it is column gj_base + c and walks the 32 rows of the sub-block (X[gi, .] an LDS broadcast), for the I side it is row
+// gi_base + c and walks the 32 columns (t read transposed, stride 33).  A lane's sum runs over rows / columns ascending within a sub-block and over the
+// sub-blocks a (b) ascending; the two waves that share rows (columns) are added as wj = 0 + wj = 1 (wi = 0 + wi = 1) through the LDS.
+template <typename Prov, typename Win>
+__global__ void __launch_bounds__(256) k_ld_apply_tile(const int *__restrict__ scratch, const int4 *__restrict__ btiles, long n, Prov prov, Win win, int term,
+                                                       const double *__restrict__ X, long ldx, int ncols, double *__restrict__ P) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NC = kLdApplyNC;
+  const int4 t = btiles[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
+  const int c = lane & 31, hh = lane >> 5, kh = 8 * hh;
+  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
+  const int c0 = (int)blockIdx.y * NC;
+  double *xs = reinterpret_cast<double *>(smem);
+  double *tsc = reinterpret_cast<double *>(smem + kLdApplyXBytes) + wave * (32 * 33);
+  unsigned *rmask = reinterpret_cast<unsigned *>(smem + kLdApplyXBytes + kXScratchBytes) + wave * 32;
+  double inv_adj = 0.0;
+  if constexpr (__is_same(Prov, LdPairsPlain)) inv_adj = term == 2 ? 1.0 / (prov.a * 0.25 - 2.0) : 0.0;   // prov.a = 4 indiv
+  for (int e = tid; e < 2 * kXT * NC; e += 256) {           // e = (side NC + k) 256 + row: the threads run along the rows of a column of X
+    const int row = e & (kXT - 1), k = (e >> 8) % NC, side = e / (kXT * NC);
+    const long g = (side ? j0 : i0) + row;
+    xs[(side * kXT + row) * NC + k] = g < n && c0 + k < ncols ? X[(size_t)g + (size_t)(c0 + k) * (size_t)ldx] : 0.0;
+  }
+  __syncthreads();
+  const int4 *slot = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + tid;
+  constexpr size_t kSlotQuads = kPwSlotInts / 4;
+  int counts[Prov::kSlots][16];                              // the counts of the current sub-block, in accumulator register order
+  double rowacc[4][8], colacc[4][8];
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) rowacc[q][k] = colacc[q][k] = 0.0;
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
+      if (gj_base + 31 < gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: wholly below the diagonal, or no element within the window
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int4 *p = slot + ((a * 4 + b) * 4 + q) * 256;
+#pragma unroll
+        for (int k = 0; k < Prov::kSlots; k++) {
+          const int4 w = p[(size_t)k * kSlotQuads];
+          counts[k][4 * q] = w.x; counts[k][4 * q + 1] = w.y; counts[k][4 * q + 2] = w.z; counts[k][4 * q + 3] = w.w;
+        }
+      }
+      const long gj = gj_base + c;
+#pragma unroll
+      for (int reg = 0; reg < 16; reg++) {
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+        const long gi = gi_base + row;
+        const bool ok = gi <= gj && gj < n && win.in(gi, gj);
+        double tv = 0.0;
+        if (ok) tv = ld_apply_term(prov, counts, reg, gi, gj, term, inv_adj);
+        tsc[row * 33 + c] = tv;
+        const unsigned long long bal = __ballot(ok);
+        if (c == 0) rmask[row] = (unsigned)(bal >> (32 * hh));
+      }
+      __builtin_amdgcn_wave_barrier();                       // the wave reads what it wrote: LDS operations of one wave complete in order
+      // J side: column gj, the rows gi < gj of the sub-block
+      const double *xi = xs + ((wi * 128 + a * 32) * NC + kh);
+#pragma unroll 2
+      for (int row = 0; row < 32; row++) {
+        if (((rmask[row] >> c) & 1u) && gi_base + row != gj) {
+          const double tv = tsc[row * 33 + c];
+#pragma unroll
+          for (int k = 0; k < 8; k++) colacc[b][k] = fma(tv, xi[row * NC + k], colacc[b][k]);
+        }
+      }
+      // I side: row gi_base + c, the columns of the sub-block
+      const unsigned mine = rmask[c];
+      const double *xj = xs + ((kXT + wj * 128 + b * 32) * NC + kh);
+#pragma unroll 2
+      for (int cc = 0; cc < 32; cc++) {
+        if ((mine >> cc) & 1u) {
+          const double tv = tsc[c * 33 + cc];
+#pragma unroll
+          for (int k = 0; k < 8; k++) rowacc[a][k] = fma(tv, xj[cc * NC + k], rowacc[a][k]);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  // the partials of the tile: P[tile][side][row][ncols]; a side is the sum of its two halves, formed through the LDS where X was
+  double *Pt = P + (size_t)blockIdx.x * 2 * kXT * (size_t)ncols;
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 4; a++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) xs[(wj * kXT + wi * 128 + a * 32 + c) * NC + kh + k] = rowacc[a][k];
+  __syncthreads();
+  for (int e = tid; e < kXT * NC; e += 256) {
+    const int row = e / NC, k = e % NC;
+    if (c0 + k < ncols) Pt[(size_t)row * (size_t)ncols + (size_t)(c0 + k)] = xs[row * NC + k] + xs[(kXT + row) * NC + k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) xs[(wi * kXT + wj * 128 + b * 32 + c) * NC + kh + k] = colacc[b][k];
+  __syncthreads();
+  for (int e = tid; e < kXT * NC; e += 256) {
+    const int row = e / NC, k = e % NC;
+    if (c0 + k < ncols) Pt[(size_t)(kXT + row) * (size_t)ncols + (size_t)(c0 + k)] = xs[row * NC + k] + xs[(kXT + row) * NC + k];
+  }
+}
+
+// Per group of tile rows [i_lo, i_hi): one thread per (row i, column c) of the row blocks B = i_lo .. jmax[i_hi - 1] the group touches.  Y[i, c] takes, in this
+// order, the J sides of the group's tiles (I, B), I ascending from max(i_lo, imin[B]) (imin[B] = the first tile row that reaches B; jmax is non-decreasing),
+// and, where B is one of the group's tile rows, the I sides of its tiles (B, J), J ascending.  tfirst[I] = the window tiles in front of tile row I.
+__global__ void __launch_bounds__(256) k_ld_apply_finish(const double *__restrict__ P, int ncols, const long *__restrict__ tfirst, const int *__restrict__ jmax,
+                                                         const int *__restrict__ imin, int i_lo, int i_hi, long n, long nrows, double *__restrict__ Y, long ldy) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nrows * (long)ncols) return;
+  const long i = (long)i_lo * kXT + idx / ncols;
+  const int col = (int)(idx % ncols);
+  if (i >= n) return;
+  const int B = (int)(i / kXT), rr = (int)(i % kXT);
+  double *y = Y + (size_t)i + (size_t)col * (size_t)ldy;
+  double sum = *y;
+  auto part = [&](long tile, int side) { return P[((size_t)(tile * 2 + side) * kXT + (size_t)rr) * (size_t)ncols + (size_t)col]; };
+  const int i_end = min(i_hi - 1, B);
+  for (int I = max(i_lo, imin[B]); I <= i_end; I++) sum += part(tfirst[I] - tfirst[i_lo] + (B - I), 1);
+  if (B < i_hi) {
+    const int J1 = jmax[B];
+    for (int J = B; J <= J1; J++) sum += part(tfirst[B] - tfirst[i_lo] + (J - B), 0);
+  }
+  *y = sum;
+}
+
+// both routes of the apply entries (pairwise: the pairwise-complete r; else the plain route with is_plink and freq)
+static int ld_apply_any(const char *who, const unsigned char *plink, long snps, long indiv, const int *last, int term, const double *X, long ldx, long n, double *Y,
+                        long ldy, bool pairwise, bool is_plink, const double *freq) {
+  if (!last || !X || !Y) { set_error(1, "%s: bad arguments", who); return 1; }
+  if (n < 1 || n > kLdApplyMaxCols) { set_error(1, "%s: need 1 <= n <= %ld (n %ld)", who, kLdApplyMaxCols, n); return 1; }
+  if (term < 0 || term > 2) { set_error(1, "%s: term must be 0, 1 or 2", who); return 1; }
+  if (term == 2 && indiv < 3) { set_error(1, "%s: the adjusted term needs indiv >= 3", who); return 1; }
+  if (snps > 0 && (ldx < snps || ldy < snps)) { set_error(1, "%s: need ldx >= snps and ldy >= snps (ldx %ld, ldy %ld, snps %ld)", who, ldx, ldy, snps); return 1; }
+  const size_t cap = ld_scratch_cap();
+  LdWindow c(who, plink, snps, indiv, 0, last, Y, ldy, false, 0);
+  c.set_apply((int)n);
+  const int pairs_max = pairwise ? kPwPairs : 1;
+  const size_t part_bytes = sizeof(double) * 2 * kXT * (size_t)n;   // the partials of a window tile: they share the cap with its count slots
+  bool x_dev = false;
+  // the scratch and the partials as ld_pairwise_any counts the scratch, the device copy of a host X, the window tiles' list and the plan's arrays
+  auto extra = [&] {
+    x_dev = ptr_location(X, nullptr) == 1;
+    const size_t tile_bytes = pairs_max * kPwSlotBytes + part_bytes;
+    return std::min(std::max(cap, c.row_tiles_max * tile_bytes), c.ntiles * tile_bytes) + (x_dev ? 0 : sizeof(double) * (size_t)snps * (size_t)n) +
+           c.ntiles * sizeof(int4) + sizeof(long) * ((size_t)c.g.nb + 1) + 2 * sizeof(int) * (size_t)c.g.nb;
+  };
+  if (c.begin(pairwise ? 3 : 1, extra, pairwise || freq ? nullptr : "%s: allele frequencies are required", pairwise ? kPwMaxIndiv : 0L, "%s",
+              pairwise ? "%s: at most %ld SNPs per call" : "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
+  const XGeom &g = c.g;
+  hipStream_t s = c.s;
+  LdPlainOperand plain;
+  LdPairwiseOperand pw;
+  if (pairwise ? pw.stage(c, plink) : plain.stage(c, plink, is_plink, freq)) return 1;
+  const bool f4 = pairwise ? pw.f4 : plain.f4;
+  const int pairs = pairwise ? pw.pairs : 1;
+  LdGroups gr(c, cap, pairs, part_bytes);
+  // the plan's arrays on the device: tfirst (nb + 1 longs), then jmax and imin (nb ints each)
+  std::vector<long> tfirst((size_t)g.nb + 1, 0);
+  std::vector<int> imin((size_t)g.nb, 0);
+  for (int I = 0; I < g.nb; I++) tfirst[(size_t)I + 1] = tfirst[(size_t)I] + (c.jmax[(size_t)I] - I + 1);
+  for (int B = 0, I = 0; B < g.nb; B++) { while (c.jmax[(size_t)I] < B) I++; imin[(size_t)B] = I; }   // jmax[B] >= B ends the search
+  XTiles t;
+  XBuf d_scr, d_bt, d_part, d_plan, d_xm;
+  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
+  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * kPwSlotBytes) || d_part.alloc(gr.tiles_max * part_bytes) ||
+      d_plan.alloc(sizeof(long) * ((size_t)g.nb + 1) + 2 * sizeof(int) * (size_t)g.nb) || (!x_dev && d_xm.alloc(sizeof(double) * (size_t)snps * (size_t)n))) return 1;
+  long *d_tfirst = (long *)d_plan.p;
+  int *d_jmax = (int *)(d_tfirst + g.nb + 1), *d_imin = d_jmax + g.nb;
+  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  MXA_HIP(hipMemcpyAsync(d_tfirst, tfirst.data(), sizeof(long) * tfirst.size(), hipMemcpyHostToDevice, s));
+  MXA_HIP(hipMemcpyAsync(d_jmax, c.jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice, s));
+  MXA_HIP(hipMemcpyAsync(d_imin, imin.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice, s));
+  // X once to the device (compact), Y cleared once: its snps rows of every column, nothing else
+  const double *d_x = X;
+  long ld_x = ldx;
+  if (!x_dev) {
+    MXA_HIP(hipMemcpy2DAsync(d_xm.p, sizeof(double) * (size_t)snps, X, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)snps, (size_t)n, hipMemcpyHostToDevice, s));
+    d_x = (const double *)d_xm.p;
+    ld_x = snps;
+  }
+  double *d_y = c.d_res;
+  const long ld_y = c.out_dev ? ldy : snps;
+  MXA_HIP(hipMemset2DAsync(d_y, sizeof(double) * (size_t)ld_y, 0, sizeof(double) * (size_t)snps, (size_t)n, s));
+  if (c.start()) return 1;
+  const XPost none{};
+  const LdVarWindow win{(const int *)c.d_last.p, nullptr, c.ndiag};
+  const unsigned chunks = (unsigned)((n + kLdApplyNC - 1) / kLdApplyNC);
+  static unsigned long long lds_mask[3] = {0, 0, 0};
+  for (int q = 0; q < gr.n; q++) {
+    // the group's products into the scratch, its tiles' partials, and the partials into Y (the next group reuses the scratch and the partials)
+    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
+    const dim3 grid((unsigned)(gr.band_first[(size_t)q + 1] - gr.band_first[(size_t)q]), chunks);
+    const int4 *bt = (const int4 *)d_bt.p + gr.band_first[(size_t)q];
+    auto tile = [&](auto prov, int which) {
+      constexpr auto K = &k_ld_apply_tile<decltype(prov), LdVarWindow>;
+      if (ensure_dyn_lds(reinterpret_cast<const void *>(K), kLdApplyLds, &lds_mask[which])) return 1;
+      hipLaunchKernelGGL(K, grid, dim3(256), kLdApplyLds, s, (const int *)d_scr.p, bt, snps, prov, win, term, d_x, ld_x, (int)n, (double *)d_part.p);
+      return 0;
+    };
+    if (!pairwise ? tile(LdPairsPlain{plain.xp.u, plain.xp.w, plain.xp.a}, 0) : pw.dense ? tile(LdPairsCounts{}, 1) : tile(LdPairsSums{pw.d_sz, pw.d_sa, (double)indiv}, 2)) return 1;
+    const int i_lo = gr.row0[(size_t)q], i_hi = gr.row0[(size_t)q + 1];
+    const long nrows = std::min(snps, ((long)c.jmax[(size_t)i_hi - 1] + 1) * kXT) - (long)i_lo * kXT;
+    const long blocks = (nrows * n + 255) / 256;
+    if (blocks > 0x7fffffffL) { set_error(3, "%s: launch too large", who); return 1; }
+    hipLaunchKernelGGL(k_ld_apply_finish, dim3((unsigned)blocks), dim3(256), 0, s, (const double *)d_part.p, (int)n, (const long *)d_tfirst, (const int *)d_jmax,
+                       (const int *)d_imin, i_lo, i_hi, snps, nrows, d_y, ld_y);
+    MXA_HIP(hipGetLastError());
+  }
+  if (c.finish_apply()) return 1;
+  debug_info("%s: %d group(s), %d product(s) per window tile, %s engine, %ld column(s) in %u chunk(s)", who, gr.n, pairs, f4 ? "FP4" : "int8", n, chunks);
   return 0;
 }
 
@@ -2540,6 +2811,19 @@ extern "C" int mxa_ld_window_pairs_pairwise(const unsigned char *plink, int snps
                                             long capacity, long *total) {
   mxa::clear_error();
   return mxa::ld_pairs_any("mxa_ld_window_pairs_pairwise", plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, true, true, nullptr);
+}
+
+// ---- the window applied to a matrix: Y = T_w(R) X without the rows
+extern "C" int mxa_ld_window_apply(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y, long ldy,
+                                   int is_plink_format, const double *allele_freq) {
+  mxa::clear_error();
+  return mxa::ld_apply_any("mxa_ld_window_apply", plink, snps, indiv, last, term, X, ldx, n, Y, ldy, false, is_plink_format != 0, allele_freq);
+}
+
+extern "C" int mxa_ld_window_apply_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y,
+                                            long ldy) {
+  mxa::clear_error();
+  return mxa::ld_apply_any("mxa_ld_window_apply_pairwise", plink, snps, indiv, last, term, X, ldx, n, Y, ldy, true, true, nullptr);
 }
 
 // ---- the greedy selection on the pairs graph: the graph step alone, and the window entries (pairs driver + graph step, all on the device)

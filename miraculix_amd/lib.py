@@ -119,6 +119,12 @@ def load_shared_library():
     L.mxa_ld_window_prune_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]
     L.mxa_ld_window_prune_pairwise.restype = ctypes.c_int
+    L.mxa_ld_window_apply.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p]
+    L.mxa_ld_window_apply.restype = ctypes.c_int
+    L.mxa_ld_window_apply_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_long]
+    L.mxa_ld_window_apply_pairwise.restype = ctypes.c_int
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

@@ -457,6 +457,48 @@ int mxa_ld_window_apply(const unsigned char *plink, int snps, int indiv, const i
 int mxa_ld_window_apply_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y,
                                  long ldy);
 
+/* The LD operator object: the window's values staged ONCE in device memory, then applied and ridge-solved there.  mxa_ld_window_apply forms every r^ anew on
+ * each call; LDpred-inf, SBLUP and ridge regression on summary statistics apply the same T_w(R) tens to hundreds of times.  The object holds
+ * T[i, j] for first[i] <= j <= last[i] (first[i] = min{k : last[k] >= i}), symmetric; kind 0: T = r^, kind 1: T = fl(r^ r^) -- bit for bit what
+ * mxa_ld_window_rows / mxa_ld_window_rows_pairwise store for the same arguments: creation runs that driver into a device buffer.  The adjusted term (term 2 of
+ * mxa_ld_window_apply) is not offered.  The object lives in the memory of the selected device (no MIRACULIX_NUM_GPUS sharding); one call is in flight per
+ * object, as for the compressed objects.
+ * Storage: the MIRRORED ragged rows in one array, row j = T[j, first[j] .. last[j]] at ptr[j] (ptr = exclusive prefix sum of last[j] - first[j] + 1), i.e.
+ * 2 entries - snps doubles with entries = rowptr[snps], the number of upper entries; first, last, ptr, rowptr, ptr - first and a packing buffer of 16 doubles
+ * per SNP (the column chunk of an apply) sit beside it.  Peak during creation: the upper rows (8 entries bytes, released at the end) plus the larger of the
+ * object (`bytes`) and the rows driver's own staging.
+ * mxa_ld_op_bytes (host only, no device needed; last: a host pointer): *entries and *bytes (what an object holds after creation) from `last` alone.
+ * mxa_ld_op_create / _create_pairwise: arguments as mxa_ld_window_rows / mxa_ld_window_rows_pairwise; *op receives the handle.
+ * mxa_ld_op_from_rows: the same object from caller-supplied upper ragged rows (mxa_ld_window_rows' layout, `entries` doubles, host or device; copied): LD from
+ *   another source.  The values are taken as they are (no unit diagonal is required).
+ * mxa_ld_op_rows: the upper ragged rows back out, `entries` doubles, host or device.
+ * mxa_ld_op_apply: Y[i, c] = shift X[i, c] + sum over first[i] <= j <= last[i] of T[i, j] X[j, c].  X, Y: snps x n column-major, ldx, ldy >= snps, each a host
+ *   or a device pointer independently; rows snps .. ldy - 1 of Y and anything beyond column n - 1 are never written; X and Y must not overlap.  The sum is the
+ *   chain acc = fma(T[i, j], X[j, c], acc) over ascending j from 0.0, then fma(shift, X[i, c], acc): an order fixed by i and the window alone, no atomics.  Y
+ *   is identical from run to run, between host and device pointers and for every n (column c of an n-column call is bit for bit the one-column call).  An
+ *   element outside the window is skipped, never multiplied; a NaN in T makes exactly the rows whose window holds it NaN.
+ * mxa_ld_op_solve: (T + shift I) X = B by conjugate gradients from X = 0, the n columns in lockstep, each with its own alpha, beta, iteration count and
+ *   stopping decision, all kept on the device (the host reads one word per iteration: the number of columns still running).  A column stops when the
+ *   recurrence residual satisfies sqrt(r.r) / sqrt(b.b) <= tol, tested before the first iteration too (b = 0: X = 0, iters 0).  status[c]: 0 converged, 1
+ *   max_iter reached, 2 breakdown (p.Ap not > 0: the matrix is not positive definite along p, or a NaN); after 1 or 2, X holds the last iterate.  relres[c]:
+ *   the final recurrence residual over the norm of b (0 for b = 0); iters, relres, status: optional host arrays of n.  Dot products are per-block partials
+ *   (1024 rows each) summed by one block in index order: column c of an n-column solve, its iters included, is bit for bit the one-column solve.  The return
+ *   value is 0 whenever the call ran; the verdict is per column.  B, X: host or device independently, must not overlap.
+ * mxa_ld_op_free: releases the object and sets *op = NULL; NULL or an already freed handle: no-op.
+ * Errors (return 1, mxa_last_error() == 1, outputs untouched, *op left NULL on creation): everything mxa_ld_window_rows(_pairwise) rejects; NULL op or pointers;
+ * n < 1 (solve: n > 65535); ldx / ldy / ldb < snps; overlap of X and Y (B and X) between pointers of the same kind; shift NaN or infinite; tol not in (0, 1); max_iter < 0; a
+ * handle that is not live.  12: not enough device memory (creation: upper rows plus object; apply: the device copies of host X / Y; solve: r, p, Ap, the
+ * partial sums and the device copies of host B / X). */
+int mxa_ld_op_bytes(int snps, const int *last, long *entries, long *bytes);
+int mxa_ld_op_create(const unsigned char *plink, int snps, int indiv, const int *last, int kind, int is_plink_format, const double *allele_freq, void **op);
+int mxa_ld_op_create_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, int kind, void **op);
+int mxa_ld_op_from_rows(int snps, const int *last, const double *rows, void **op);
+int mxa_ld_op_rows(void *op, double *rows);
+int mxa_ld_op_apply(void *op, double shift, const double *X, long ldx, int n, double *Y, long ldy);
+int mxa_ld_op_solve(void *op, double shift, const double *B, long ldb, int n, double *X, long ldx, double tol, int max_iter, int *iters, double *relres,
+                    int *status);
+void mxa_ld_op_free(void **op);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

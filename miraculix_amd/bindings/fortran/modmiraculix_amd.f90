@@ -20,6 +20,7 @@ module modmiraculix_amd
  public :: mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise
  public :: mxa_ld_prune_csr, mxa_ld_window_prune, mxa_ld_window_prune_pairwise
  public :: mxa_ld_window_apply, mxa_ld_window_apply_pairwise
+ public :: mxa_ld_op_bytes, mxa_ld_op_create, mxa_ld_op_create_pairwise, mxa_ld_op_from_rows, mxa_ld_op_rows, mxa_ld_op_apply, mxa_ld_op_solve, mxa_ld_op_free
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -265,6 +266,62 @@ module modmiraculix_amd
    integer(c_long), value, intent(in) :: ldx, ldy
    integer(c_int) :: rc
   end function
+
+  ! the LD operator object: the window's values staged once on the device (op: a handle, type(c_ptr)), then Y = shift X + T X and the conjugate-gradient solve
+  ! of (T + shift I) X = B there; iters, relres, status of the solve: host arrays of n, or c_null_ptr
+  function mxa_ld_op_bytes(snps, last, entries, bytes) bind(C, name='mxa_ld_op_bytes') result(rc)
+   import c_int, c_long, c_ptr
+   integer(c_int), value, intent(in) :: snps
+   type(c_ptr), value, intent(in) :: last
+   integer(c_long), intent(out) :: entries, bytes
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_create(plink, snps, indiv, last, kind, is_plink_format, allele_freq, op) bind(C, name='mxa_ld_op_create') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last, allele_freq
+   integer(c_int), value, intent(in) :: snps, indiv, kind, is_plink_format
+   type(c_ptr), intent(out) :: op
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_create_pairwise(plink, snps, indiv, last, kind, op) bind(C, name='mxa_ld_op_create_pairwise') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: plink, last
+   integer(c_int), value, intent(in) :: snps, indiv, kind
+   type(c_ptr), intent(out) :: op
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_from_rows(snps, last, rows, op) bind(C, name='mxa_ld_op_from_rows') result(rc)
+   import c_int, c_ptr
+   integer(c_int), value, intent(in) :: snps
+   type(c_ptr), value, intent(in) :: last, rows
+   type(c_ptr), intent(out) :: op
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_rows(op, rows) bind(C, name='mxa_ld_op_rows') result(rc)
+   import c_int, c_ptr
+   type(c_ptr), value, intent(in) :: op, rows
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_apply(op, shift, X, ldx, n, Y, ldy) bind(C, name='mxa_ld_op_apply') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: op, X, Y
+   real(c_double), value, intent(in) :: shift
+   integer(c_long), value, intent(in) :: ldx, ldy
+   integer(c_int), value, intent(in) :: n
+   integer(c_int) :: rc
+  end function
+  function mxa_ld_op_solve(op, shift, B, ldb, n, X, ldx, tol, max_iter, iters, relres, status) bind(C, name='mxa_ld_op_solve') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: op, B, X, iters, relres, status
+   real(c_double), value, intent(in) :: shift, tol
+   integer(c_long), value, intent(in) :: ldb, ldx
+   integer(c_int), value, intent(in) :: n, max_iter
+   integer(c_int) :: rc
+  end function
+  subroutine mxa_ld_op_free(op) bind(C, name='mxa_ld_op_free')
+   import c_ptr
+   type(c_ptr), intent(inout) :: op
+  end subroutine
 
   ! incremental staging: the object is filled by blocks of SNP rows (objects larger than any buffer the caller could hold)
   function mxa_plink2compressed_begin(snps, indiv, max_n, compressed) bind(C, name='mxa_plink2compressed_begin') result(rc)

@@ -494,3 +494,188 @@ def ld_prune_csr(rowptr, col, priority=None, return_owner=False, return_rounds=F
     L = _lib.check_library_handle()
     return _prune_call(rowptr, snps, return_owner, return_rounds, "mxa_ld_prune_csr", lambda keep, owner, n_kept, rounds: L.mxa_ld_prune_csr(
         int(snps), _lib.ptr(rowptr), _lib.ptr(col) if int(np.prod(col.shape)) else None, _lib.ptr(priority), keep, owner, n_kept, rounds))
+
+
+# ---- the LD operator object: the window's values staged once on the device, then applied and ridge-solved there (C entries mxa_ld_op_*)
+LD_OP_KINDS = {"r": 0, "r2": 1}
+LD_OP_STATUS = ("converged", "max_iter reached", "breakdown")
+
+
+def _host_last(last, snps):
+    """`last` as a checked int32 numpy array of snps values"""
+    if _lib.is_torch_tensor(last):
+        last = last.cpu().numpy()
+    last = np.ascontiguousarray(last, dtype=np.int32)
+    if last.shape != (snps,):
+        raise ValueError(f"last needs to be {snps} int32 values")
+    i = np.arange(snps)
+    if np.any(last < i) or np.any(last >= snps) or np.any(np.diff(last) < 0):
+        raise ValueError("last needs i <= last[i] < snps, non-decreasing")
+    return last
+
+
+def ld_op_bytes(last):
+    """Additive (C entry mxa_ld_op_bytes; no device needed): (entries, bytes) of the LdOperator of the window `last` -- the number of upper ragged entries
+    rowptr[snps], and the device bytes the object holds after creation (the mirrored rows, 2 entries - snps doubles, and its index arrays).  During
+    creation the upper rows (8 entries bytes) stand next to it."""
+    import ctypes
+    snps = int(np.prod(np.shape(last)))
+    if snps < 1:
+        raise ValueError("last needs at least one value")
+    last = _host_last(last, snps)
+    entries, nbytes = ctypes.c_long(0), ctypes.c_long(0)
+    _check(_lib.check_library_handle().mxa_ld_op_bytes(snps, _lib.ptr(last), ctypes.byref(entries), ctypes.byref(nbytes)), "mxa_ld_op_bytes")
+    return entries.value, nbytes.value
+
+
+def _window_or_last(snps, last, window):
+    if (last is None) == (window is None):
+        raise ValueError("exactly one of last and window is needed")
+    if window is not None:
+        if not 0 <= int(window) < snps:
+            raise ValueError(f"Window needs to be in [0, {snps}): {window}")
+        last = np.minimum(np.arange(snps, dtype=np.int64) + int(window), snps - 1).astype(np.int32)
+    return last
+
+
+class LdOperator:
+    """The windowed LD matrix T_w(R) (kind "r") or its element-wise square (kind "r2") resident on the device: created once, then applied
+    (Y = shift X + T X) and ridge-solved ((T + shift I) X = B, conjugate gradients) any number of times without repeating the genotype products.
+    T is bit for bit what ld_window_rows / ld_window_rows_pairwise return.  Use as a context manager, or call free()."""
+
+    def __init__(self, handle, snps, last):
+        self._h = handle
+        self.snps = snps
+        self.last = last
+        self.entries, self.nbytes = ld_op_bytes(last)
+
+    @classmethod
+    def create(cls, plink, snps, indiv, last=None, window=None, kind="r", pairwise=False, is_plink_format=False, allele_freq=None):
+        """from the packed genotypes: arguments as ld_window_rows / ld_window_rows_pairwise; exactly one of `last` and `window`"""
+        import ctypes
+        if kind not in LD_OP_KINDS:
+            raise ValueError(f"kind needs to be 'r' or 'r2': {kind!r}")
+        if not pairwise and (allele_freq is None or len(allele_freq) != snps):
+            raise ValueError(f"Allele frequencies need to be equal to length of SNPs {snps}.")
+        last = _window_or_last(snps, last, window)
+        host = _host_last(last, snps)
+        last, _ = _ld_last_args(plink, snps, indiv, last)
+        L = _lib.check_library_handle()
+        h = ctypes.c_void_p(None)
+        if pairwise:
+            _check(L.mxa_ld_op_create_pairwise(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), LD_OP_KINDS[kind], ctypes.byref(h)), "mxa_ld_op_create_pairwise")
+        else:
+            f = allele_freq if _lib.is_torch_tensor(allele_freq) else np.ascontiguousarray(allele_freq, dtype=np.float64)
+            _check(L.mxa_ld_op_create(_lib.ptr(plink), int(snps), int(indiv), _lib.ptr(last), LD_OP_KINDS[kind], int(bool(is_plink_format)), _lib.ptr(f),
+                                      ctypes.byref(h)), "mxa_ld_op_create")
+        return cls(h, int(snps), host)
+
+    @classmethod
+    def from_rows(cls, last, rows):
+        """from upper ragged rows (ld_window_rows' layout: rows[rowptr[i] + d] = T(i, i + d)), numpy or a torch tensor (host / device); copied"""
+        import ctypes
+        snps = int(np.prod(np.shape(last)))
+        if snps < 1:
+            raise ValueError("last needs at least one value")
+        host = _host_last(last, snps)
+        total = int((host.astype(np.int64) - np.arange(snps) + 1).sum())
+        if _lib.is_torch_tensor(rows):
+            import torch
+            if rows.dtype != torch.float64 or rows.numel() != total:
+                raise ValueError(f"rows needs to be {total} float64 values")
+            rows = rows.contiguous()
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.shape != (total,):
+                raise ValueError(f"rows needs to be {total} float64 values")
+        h = ctypes.c_void_p(None)
+        _check(_lib.check_library_handle().mxa_ld_op_from_rows(snps, _lib.ptr(host), _lib.ptr(rows), ctypes.byref(h)), "mxa_ld_op_from_rows")
+        return cls(h, snps, host)
+
+    def _live(self):
+        if self._h is None or not self._h.value:
+            raise RuntimeError("the LdOperator has been freed")
+        return _lib.check_library_handle()
+
+    def _columns(self, X, what):
+        """(column-major copy of X as n rows of snps values, n, X's shape)"""
+        shape = tuple(X.shape)
+        if len(shape) not in (1, 2) or shape[0] != self.snps or (len(shape) == 2 and shape[1] < 1):
+            raise ValueError(f"{what} needs to be ({self.snps},) or ({self.snps}, n >= 1): {shape}")
+        n = 1 if len(shape) == 1 else int(shape[1])
+        if _lib.is_torch_tensor(X):
+            import torch
+            if X.dtype != torch.float64:
+                raise ValueError(f"{what} needs to be float64")
+            return X.reshape(self.snps, n).t().contiguous(), n, shape
+        return np.ascontiguousarray(np.asarray(X, dtype=np.float64).reshape(self.snps, n).T), n, shape
+
+    def _result(self, like, n, out):
+        snps = self.snps
+        if _lib.is_torch_tensor(like):
+            import torch
+            yc = torch.zeros((n, snps), dtype=torch.float64, device=like.device) if out is None else out.t()
+            if out is not None and (tuple(out.shape) != (snps, n) or out.dtype != torch.float64 or not yc.is_contiguous()):
+                raise ValueError(f"out needs to be a float64 ({snps}, {n}) tensor with contiguous columns")
+        else:
+            yc = np.zeros((n, snps), dtype=np.float64) if out is None else out.T
+            if out is not None and (out.shape != (snps, n) or out.dtype != np.float64 or not yc.flags.c_contiguous):
+                raise ValueError(f"out needs to be a float64 ({snps}, {n}) array in Fortran order")
+        return yc
+
+    def apply(self, X, shift=0.0, out=None):
+        """Y = shift X + T X.  X: (snps, n) or (snps,) float64, numpy or torch (host / device); the result has X's shape and kind.  The same bits from run
+        to run, for host and device operands and for every n.  out: as for ld_window_apply()."""
+        L = self._live()
+        if not np.isfinite(shift):
+            raise ValueError(f"shift needs to be finite: {shift}")
+        xc, n, shape = self._columns(X, "X")
+        yc = self._result(xc, n, out)
+        _check(L.mxa_ld_op_apply(self._h, float(shift), _lib.ptr(xc), self.snps, n, _lib.ptr(yc), self.snps), "mxa_ld_op_apply")
+        if out is not None:
+            return out
+        return (yc.t() if _lib.is_torch_tensor(yc) else yc.T).reshape(shape)
+
+    def solve(self, B, shift, tol=1e-8, max_iter=1000):
+        """(T + shift I) X = B by conjugate gradients from X = 0, every column on its own.  Returns (X, iters, relres, status): X of B's shape and kind; iters
+        (int32), relres (the final recurrence residual over |b|) and status (0 converged, 1 max_iter reached, 2 breakdown: not positive definite, or a NaN) as
+        numpy arrays of n."""
+        L = self._live()
+        if not np.isfinite(shift):
+            raise ValueError(f"shift needs to be finite: {shift}")
+        if not 0.0 < tol < 1.0:
+            raise ValueError(f"tol needs to be in (0, 1): {tol}")
+        if int(max_iter) < 0:
+            raise ValueError(f"max_iter must not be negative: {max_iter}")
+        bc, n, shape = self._columns(B, "B")
+        xc = self._result(bc, n, None)
+        iters, relres, status = np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
+        _check(L.mxa_ld_op_solve(self._h, float(shift), _lib.ptr(bc), self.snps, n, _lib.ptr(xc), self.snps, float(tol), int(max_iter), _lib.ptr(iters),
+                                 _lib.ptr(relres), _lib.ptr(status)), "mxa_ld_op_solve")
+        return (xc.t() if _lib.is_torch_tensor(xc) else xc.T).reshape(shape), iters, relres, status
+
+    def rows(self, like=None):
+        """the upper ragged rows (ld_window_rows' layout) as a numpy array, or as a torch tensor next to `like`"""
+        L = self._live()
+        out = _zeros_like(like if like is not None else self.last, self.entries)
+        _check(L.mxa_ld_op_rows(self._h, _lib.ptr(out)), "mxa_ld_op_rows")
+        return out
+
+    def free(self):
+        if self._h is not None and self._h.value:
+            import ctypes
+            _lib.check_library_handle().mxa_ld_op_free(ctypes.byref(self._h))
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -1660,7 +1660,7 @@ struct LdPlainOperand {
 }  // namespace
 
 // the plain route: the operand staged as it is, the LD map's statistics, and one launch of the window's tiles with the window epilogue
-static int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
+int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
                          bool is_plink, const double *freq) {
   LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
   if (c.begin(1, [] { return (size_t)0; }, freq ? nullptr : "%s: allele frequencies are required", 0, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3",
@@ -1859,7 +1859,7 @@ struct LdPairwiseOperand {
 }  // namespace
 
 // the pairwise route: the three planes staged, per group of tile rows the count products and their combine
-static int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag) {
+int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag) {
   // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
   const size_t cap = ld_scratch_cap();
   const size_t slot_bytes = kPwSlotBytes;

@@ -276,6 +276,12 @@ int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_t
 // G_tn: the OTHER stored orientation (rows = the K index); the main kernel then runs in the transposed-operand form k_gemm_i8_tn, one launch per tile of 32
 // expanded columns.  Returns 2 (nothing enqueued) when that would take more passes than the fp64 MFMA tile costs or the plan has several column chunks.
 
+// mxa_crossprod.hip: the two windowed-LD host drivers, also run by the LD operator object (mxa_ldop.hip) into a device buffer of ragged rows.
+// window / ldb: the fixed entries' band (last == nullptr); last: the general window (rows: out = rowptr[snps] doubles; scores: snps).  out: host or device.
+int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
+                  bool is_plink, const double *freq);
+int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag);
+
 // mxa_dense.hip: dense fp64 MFMA building blocks of the solver twin
 int launch_dgemm(bool ta, bool tb, long M, long N, long K, double alpha, const double *A, long lda, const double *B, long ldb, double beta, double *C, long ldc,
                  bool lower_only, hipStream_t s);

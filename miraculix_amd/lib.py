@@ -125,6 +125,24 @@ def load_shared_library():
     L.mxa_ld_window_apply_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_long]
     L.mxa_ld_window_apply_pairwise.restype = ctypes.c_int
+    L.mxa_ld_op_bytes.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long)]
+    L.mxa_ld_op_bytes.restype = ctypes.c_int
+    L.mxa_ld_op_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                   ctypes.POINTER(ctypes.c_void_p)]
+    L.mxa_ld_op_create.restype = ctypes.c_int
+    L.mxa_ld_op_create_pairwise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    L.mxa_ld_op_create_pairwise.restype = ctypes.c_int
+    L.mxa_ld_op_from_rows.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    L.mxa_ld_op_from_rows.restype = ctypes.c_int
+    L.mxa_ld_op_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.mxa_ld_op_rows.restype = ctypes.c_int
+    L.mxa_ld_op_apply.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.mxa_ld_op_apply.restype = ctypes.c_int
+    L.mxa_ld_op_solve.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_double,
+                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mxa_ld_op_solve.restype = ctypes.c_int
+    L.mxa_ld_op_free.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
+    L.mxa_ld_op_free.restype = None
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

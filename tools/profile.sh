@@ -19,6 +19,7 @@
 #   ld-pairs [snps indiv window min_r2]   pairs with r^2 >= min_r2 as CSR (mxa_ld_window_pairs / _pairwise) against mxa_ld_window_rows(_pairwise), one process, both engines
 #   ld-prune [snps indiv window min_r2 reps]   LD pruning / clumping on the device (mxa_ld_window_prune, mxa_ld_prune_csr): products, select passes, rounds, owner pass; three priorities; against ld_pairs + the walk on the host
 #   ld-apply [snps indiv window reps]   the window applied to a matrix (mxa_ld_window_apply), n in {1, 16, 64}, against mxa_ld_window_scores and against mxa_ld_window_rows + a device band product in torch, one process, both engines
+#   ld-op [snps indiv window reps]   the LD operator object (mxa_ld_op_*): creation against mxa_ld_window_rows, apply at n in {1, 16, 64} against mxa_ld_window_apply with the byte model, a 50-iteration solve, one process
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -127,6 +128,10 @@ ld-apply)
   # kernel and whole-call time of the apply entry per n and the two comparison legs, alternating calls; the text is what profiles/r13_ld_apply.txt holds
   timeout -k 10 900 python3 tools/perf_ld_apply.py ${1:-1000000} ${2:-50000} ${3:-1023} ${4:-5} 2>&1 | tee "$O/ld_apply.txt" || exit 1
   cp -f "$O/ld_apply.txt" "$R/profiles/r13_ld_apply.txt" ;;
+ld-op)
+  # whole-call times of creation, apply and solve against the entries that redo the products, alternating calls; the text is what profiles/r14_ld_op.txt holds
+  timeout -k 10 900 python3 tools/perf_ld_op.py ${1:-1000000} ${2:-50000} ${3:-1023} ${4:-5} 2>&1 | tee "$O/ld_op.txt" || exit 1
+  cp -f "$O/ld_op.txt" "$R/profiles/r14_ld_op.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

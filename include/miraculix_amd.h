@@ -7,6 +7,19 @@
  * use, on-device .bed staging helpers and measurement; the reference has no counterpart for them.
  *
  * All matrices are column-major fp64.  Plain pointers and sizes only.
+ *
+ * ALIGNMENT.  Every pointer argument is valid at the natural alignment of its element type -- 1 byte for packed genotypes and keep[], 4 for int, 8 for double
+ * and long -- in host or in device memory, and no result depends on it: base + 3 of a memory-mapped .bed, a slice of a device tensor, a column of a bigger
+ * buffer and a Fortran array section give bit for bit what a fresh allocation gives.  Nothing in front of or behind an output is written.
+ *
+ * PADDING BITS.  A packed row of k 2-bit fields takes ceil(k / 4) bytes; when k is no multiple of 4 the last byte has fields at and beyond k.  A well-formed
+ * .bed has 00 there; a buffer that is reused or sliced may not.  What they mean, by entry group (each group's comment repeats its rule):
+ *   ignored    -- plink2compressed, mxa_plink2compressed_shard / _begin / _rows / _end, mxa_bed2compressed(_range) and everything computed from their objects
+ *                 (dgemm_compressed, mxa_dgemm_compressed_device / _multi, mxa_gram_matvec(_device), get_compressed_freq); dgemm_plink; sparse_times_plink;
+ *                 mxa_transpose_2bit (its output has 00 in its own padding); mxa_allele_freq; mxa_grm, mxa_ld and every mxa_ld_* entry, plain and _pairwise.
+ *                 These entries know how many genotypes a row holds; the result is bit for bit that of the same call on 00 padding.
+ *   as stored  -- snp_multiply_gpu and mxa_snp_multiply_panel, as in the reference: whole bytes are multiplied, so the padding fields enter the sums with
+ *                 the values they hold (under is_plink_format a padding 01 turns its byte into four 3s).  Clear them before the call.
  */
 #ifndef MIRACULIX_AMD_H
 #define MIRACULIX_AMD_H
@@ -46,7 +59,10 @@ void setOptions_compressed(int use_gpu, int cores, int floatLoop, int meanSubstr
  * plink_transposed may be NULL or the same pointer as plink -- the call shape of the reference's CPU path, which never reads it
  * (5codesChar.cc:368-393; utils/benchmark/benchmark.f90:185 passes the same pointer twice): then only the SNP-major matrix is uploaded
  * and the individual-major copy is produced on the device (2-bit transpose of the raw PLINK codes), bit-identical to the object built
- * from two pointers.  On failure *compressed is left NULL and a message is printed (reference: print + handle unset). */
+ * from two pointers.  On failure *compressed is left NULL and a message is printed (reference: print + handle unset).
+ * Padding bits: IGNORED in both matrices (fields at and beyond indiv of a SNP-major row, at and beyond snps of an individual-major row), for every call
+ * shape and for the other staging entries (mxa_plink2compressed_shard, _begin / _rows / _end, mxa_bed2compressed(_range)); so are they by every product of the
+ * object and by get_compressed_freq. */
 void plink2compressed(char *plink, char *plink_transposed, int snps, int indiv, double *f, int max_n,
                       void **compressed);
 
@@ -73,7 +89,7 @@ void get_compressed_freq(void *compressed, double *f);
  *   transcompressed in {T,t,Y,y}: C (nIdx x snps, ld Ldc) = S (nIdx x indiv) * Z, packed matrix = plink_transposed.
  * rowIdxB (nIdx + 1 entries) / colIdxB / B are ZERO-based CSR; C is zero-filled over Ldc x columns.  transsparse must be N
  * (the reference aborts otherwise; so does this).  Only the packed matrix that is used needs to be non-NULL.  Pointers may be
- * host or device.  Errors: message on stderr, C unwritten, mxa_last_error() != 0. */
+ * host or device.  Padding bits of the packed rows: IGNORED.  Errors: message on stderr, C unwritten, mxa_last_error() != 0. */
 void sparse_times_plink(char *transsparse, char *transcompressed, char *plink, char *plink_transposed, int snps, int indiv,
                         int nIdx, int *rowIdxB, int *colIdxB, double *B, double *C, int Ldc);
 
@@ -85,7 +101,7 @@ void sparse_times_plink(char *transsparse, char *transcompressed, char *plink, c
  * plink256.cc:332) and nothing binds it, so there is no reference output to compare with; results are checked against the dense oracle.  The reference's
  * "indiv must be a multiple of 32" (5codesChar.cc:510) is not required.  Only the matrix the reference would read needs to be non-NULL ('N':
  * plink_transposed, 'T': plink); when only plink_transposed is given it is transposed on the device first.  Host or device pointers.
- * Errors: message on stderr, C unwritten, mxa_last_error() != 0. */
+ * Padding bits: IGNORED, as by plink2compressed.  Errors: message on stderr, C unwritten, mxa_last_error() != 0. */
 void dgemm_plink(char *trans, char *plink, char *plink_transposed, int snps, int indiv, double *f, int n, double *B, int Ldb, double *C, int Ldc);
 
 /* replaces src/cuda/snp_multiply_cuda.cu:375-382 (prototype src/cuda/snp_multiply_cuda.h:113-114; Julia binding
@@ -94,6 +110,8 @@ void dgemm_plink(char *trans, char *plink, char *plink_transposed, int snps, int
  * of 2-bit values; positional meaning as in the reference: `snps` = packed (inner) dimension, `indiv` = output
  * dimension.  is_plink_format applies the reference's byte table first (00->0, 10->1, 11->2, any byte holding a
  * missing 01 pair -> 0xFF).  Exact int32 accumulation.  snp_matrix and ans may be host or device pointers.
+ * Padding bits: AS STORED.  The reference multiplies whole bytes (snp_multiply_cuda.h:121-210), and so does this: when snps is no multiple of 4, the fields
+ * at and beyond snps of a row's last byte are multiplied like genotypes (and a 01 among them makes the byte 0xFF under the table).
  * Returns 0 on success, 1 on failure. */
 int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, double *ans, bool is_plink_format);
 
@@ -170,7 +188,8 @@ int mxa_gram_matvec_device(void *compressed, int n, const double *dV, long ldv, 
 
 /* on-device .bed staging helpers (reference counterparts live in the bindings:
  * transpose_genotype_matrix src/bindings/Julia/compressed_operations.jl:45-66, popcount frequencies
- * src/bindings/Julia/read_plink.jl:199-203).  Pointers may be host or device. */
+ * src/bindings/Julia/read_plink.jl:199-203).  Pointers may be host or device.
+ * Padding bits: IGNORED by both; the rows mxa_transpose_2bit writes have 00 in their own padding fields, whatever the input's held. */
 int mxa_transpose_2bit(const unsigned char *in, long rows, long cols, unsigned char *out);
 /* f_s = (sum of the allele counts of SNP s) / (2 indiv) with the decode the multiply uses: 00 -> 0, 10 -> 1, 11 -> 2 and the
  * missing code 01 -> 0, so that f is exactly the column mean / 2 of the matrix dgemm_compressed multiplies with.
@@ -283,7 +302,7 @@ int mxa_multi_reset_profile(void *compressed);
  * dimension ld).  col_begin must be a multiple of 256, col_end a multiple of 256 or == indiv.  upper_only != 0 computes only
  * rows [0, col_end) of the panel, i.e. everything above its diagonal block and the block itself (a host panel gets zeros in the
  * rows below, a device panel is left untouched there) -- half the total work for callers that exchange the transposed blocks
- * (miraculix_amd/distributed.py: crossprod_sharded).  Same argument meaning otherwise as snp_multiply_gpu.  Returns 0 / 1. */
+ * (miraculix_amd/distributed.py: crossprod_sharded).  Same argument meaning otherwise as snp_multiply_gpu, padding bits included (AS STORED).  Returns 0 / 1. */
 int mxa_snp_multiply_panel(const unsigned char *snp_matrix, int snps, int indiv, int col_begin, int col_end, int upper_only,
                            double *panel, long ld, int is_plink_format);
 
@@ -295,7 +314,10 @@ int mxa_snp_multiply_panel(const unsigned char *snp_matrix, int snps, int indiv,
  * The element-wise map runs INSIDE the crossproduct epilogue (round 3): the column sums and the diagonal of the crossproduct are formed from
  * the packed matrix before the product (exact integers), so the result is written once and a host result leaves through the same slab
  * pipeline as snp_multiply_gpu's.  The reference's divisions (by 2 sum f(1-f); by sigma_i, sigma_j) are multiplications by reciprocals
- * (<= 1 ulp from the quotients).  MXA_XPROD_FUSED_POST=0 runs the three separate passes over the result instead (bit-identical). */
+ * (<= 1 ulp from the quotients).  MXA_XPROD_FUSED_POST=0 runs the three separate passes over the result instead (bit-identical).
+ * Padding bits: IGNORED by mxa_grm, mxa_ld and every plain windowed entry below (mxa_ld_band, mxa_ld_scores, mxa_ld_window_rows / _scores / _pairs / _prune /
+ * _apply, mxa_ld_op_create), unlike snp_multiply_gpu: the fields at and beyond the row's length are staged as 00 BEFORE the byte table, so they are no
+ * individuals (mxa_ld; `indiv` and f in its formula do not count them either) and no SNPs (mxa_grm), and a padding 01 does not turn its byte into 3s. */
 int mxa_grm(const unsigned char *plink_transposed, int snps, int indiv, double *G, int is_plink_format, int do_scale,
             const double *allele_freq);
 int mxa_ld(const unsigned char *plink, int snps, int indiv, double *R, int is_plink_format, const double *allele_freq);

@@ -68,13 +68,19 @@ __device__ __forceinline__ uint32_t xstage_load(const uint8_t *p, long b, long r
 __device__ __forceinline__ uint32_t *xstage_dst(uint8_t *dst, long nslabs, long R, long b) {
   return reinterpret_cast<uint32_t *>(dst + ((size_t)(R / kTileRows) * nslabs + (size_t)(b / kSlabBytes)) * kTileBytes + (size_t)(R % kTileRows) * kSlabBytes + b % kSlabBytes);
 }
+// fields > 0 (the GRM / LD entries): the row holds `fields` 2-bit fields; those at and beyond it -- the padding bits of the row's last byte -- are set to 00
+// BEFORE the table, so that a padding 01 cannot turn its byte into 0xFF.  fields == 0 (the plain crossproduct): the bytes as stored, as the reference multiplies them.
 __global__ void __launch_bounds__(256) k_xstage(const uint8_t *__restrict__ src, size_t src_pitch, long row_bytes, long nrows,
-                                                uint8_t *__restrict__ dst, long nslabs, long dst_row0, int apply_lut, int *__restrict__ has3) {
+                                                uint8_t *__restrict__ dst, long nslabs, long dst_row0, int apply_lut, int *__restrict__ has3, long fields) {
   const long dpr = (row_bytes + 3) / 4;
   const long total = nrows * dpr;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const long r = idx / dpr, d = idx - r * dpr, b = d * 4;
     uint32_t keep, w = xstage_load(src + (size_t)r * src_pitch + b, b, row_bytes, keep);
+    if (fields > 0) {
+      const long left = fields - 4 * b;                                         // fields from this dword's first one on
+      if (left < 16) w &= left > 0 ? (1u << (2 * left)) - 1u : 0u;
+    }
     if (apply_lut) w = plink_lut4(w) & keep;
     if (w & (w >> 1) & 0x55555555u) atomicOr(has3, 1);
     *xstage_dst(dst, nslabs, dst_row0 + r, b) = w;
@@ -1222,8 +1228,9 @@ static int postprocess_device(double *d_M, long rows, long k, int post, int do_s
 // X (rows of row_bytes packed bytes, in device or host memory) -> d_X, zeroed first, in the tiled layout (k_xstage; is_plink: the reference's table);
 // *d_has3 = 1 when a staged field holds the value 3.  Host rows go through `bounce` (<= 256 MiB: kept by the caller, the pre-flight counts it).
 // planes_indiv > 0: the three planes Z, M, A of the pairwise-complete LD instead (k_xstage_planes; d_X holds 3 * rows_pad rows, *d_has3 = a missing code occurs).
+// mask_fields > 0: a row holds that many fields, its padding bits are staged as 00 (the GRM / LD entries); 0: the bytes as stored (the plain crossproduct).
 static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, bool is_plink, const XGeom &g, uint8_t *d_X, int *d_has3, XBuf &bounce,
-                         hipStream_t s, long planes_indiv = 0) {
+                         hipStream_t s, long planes_indiv = 0, long mask_fields = 0) {
   const long rows = g.rows;
   const size_t plane_bytes = (size_t)g.rows_pad() * g.pitch();
   MXA_HIP(hipMemsetAsync(d_X, 0, plane_bytes * (planes_indiv > 0 ? 3 : 1), s));
@@ -1232,7 +1239,7 @@ static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_
   auto stage = [&](const uint8_t *src, long r0, long nr) {
     const dim3 grid((unsigned)std::min<long>((nr * ((row_bytes + 3) / 4) + 255) / 256, 8192));
     if (planes_indiv > 0) hipLaunchKernelGGL(k_xstage_planes, grid, dim3(256), 0, s, src, (size_t)row_bytes, row_bytes, nr, planes_indiv, d_X, g.nslabs, plane_bytes, r0, d_has3);
-    else hipLaunchKernelGGL(k_xstage, grid, dim3(256), 0, s, src, (size_t)row_bytes, row_bytes, nr, d_X, g.nslabs, r0, is_plink ? 1 : 0, d_has3);
+    else hipLaunchKernelGGL(k_xstage, grid, dim3(256), 0, s, src, (size_t)row_bytes, row_bytes, nr, d_X, g.nslabs, r0, is_plink ? 1 : 0, d_has3, mask_fields);
   };
   if (in_dev) {
     stage(snp_matrix, 0L, rows);
@@ -1357,7 +1364,7 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   XBuf d_X, bounce, d_out, d_flag, f_tmp;
   if (d_X.alloc(xbytes) || d_flag.alloc(sizeof(int))) return 1;
   clk.mark("operand buffer allocated");
-  if (stage_operand(snp_matrix, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s)) return 1;
+  if (stage_operand(snp_matrix, in_dev, row_bytes, is_plink, g, (uint8_t *)d_X.p, (int *)d_flag.p, bounce, s, 0, post ? k : 0)) return 1;   // GRM / LD: padding bits are no data
   clk.mark("operand staged (upload + k_xstage)");
   bool f4 = false;
   if (pick_engine((const int *)d_flag.p, k, s, f4)) return 1;
@@ -1646,7 +1653,7 @@ struct LdPlainOperand {
   XPost xp;
   int stage(LdWindow &c, const unsigned char *plink, bool is_plink, const double *freq) {
     hipStream_t s = c.s;
-    if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, c.g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s)) return 1;
+    if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, c.g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, 0, c.indiv)) return 1;   // padding bits are no individuals
     if (pick_engine((const int *)c.d_flag.p, c.indiv, s, f4)) return 1;
     const double *d_f = freq;
     if (ptr_location(freq, nullptr) != 1) {

@@ -2318,8 +2318,9 @@ __global__ void __launch_bounds__(256) k_ld_apply_tile(const int *__restrict__ s
 // order, the J sides of the group's tiles (I, B), I ascending from max(i_lo, imin[B]) (imin[B] = the first tile row that reaches B; jmax is non-decreasing),
 // and, where B is one of the group's tile rows, the I sides of its tiles (B, J), J ascending.  tfirst[I] = the window tiles in front of tile row I.
 __global__ void __launch_bounds__(256) k_ld_apply_finish(const double *__restrict__ P, int ncols, const long *__restrict__ tfirst, const int *__restrict__ jmax,
-                                                         const int *__restrict__ imin, int i_lo, int i_hi, long n, long nrows, double *__restrict__ Y, long ldy) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+                                                         const int *__restrict__ imin, int i_lo, int i_hi, long n, long nrows, double *__restrict__ Y, long ldy,
+                                                         long blk0) {
+  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
   if (idx >= nrows * (long)ncols) return;
   const long i = (long)i_lo * kXT + idx / ncols;
   const int col = (int)(idx % ncols);
@@ -2414,10 +2415,13 @@ static int ld_apply_any(const char *who, const unsigned char *plink, long snps, 
     if (!pairwise ? tile(LdPairsPlain{plain.xp.u, plain.xp.w, plain.xp.a}, 0) : pw.dense ? tile(LdPairsCounts{}, 1) : tile(LdPairsSums{pw.d_sz, pw.d_sa, (double)indiv}, 2)) return 1;
     const int i_lo = gr.row0[(size_t)q], i_hi = gr.row0[(size_t)q + 1];
     const long nrows = std::min(snps, ((long)c.jmax[(size_t)i_hi - 1] + 1) * kXT) - (long)i_lo * kXT;
-    const long blocks = (nrows * n + 255) / 256;
-    if (blocks > 0x7fffffffL) { set_error(3, "%s: launch too large", who); return 1; }
-    hipLaunchKernelGGL(k_ld_apply_finish, dim3((unsigned)blocks), dim3(256), 0, s, (const double *)d_part.p, (int)n, (const long *)d_tfirst, (const int *)d_jmax,
-                       (const int *)d_imin, i_lo, i_hi, snps, nrows, d_y, ld_y);
+    // One thread per (row, column) of the group: the limit of a launch is 2^32 threads, not 2^31 workgroups, so this goes in pieces as well (every thread
+    // owns its Y[i, c]: no order between the pieces).  No test reaches the second piece: under the default 2 GiB scratch cap a group holds nrows n <= 2^26,
+    // and 2^32 (row, column) pairs in one group need more than 100 GB of partial sums.
+    launch_in_block_chunks((nrows * n + 255) / 256, [&](unsigned nb, long blk0) {
+      hipLaunchKernelGGL(k_ld_apply_finish, dim3(nb), dim3(256), 0, s, (const double *)d_part.p, (int)n, (const long *)d_tfirst, (const int *)d_jmax,
+                         (const int *)d_imin, i_lo, i_hi, snps, nrows, d_y, ld_y, blk0);
+    });
     MXA_HIP(hipGetLastError());
   }
   if (c.finish_apply()) return 1;
@@ -2452,9 +2456,10 @@ __device__ __forceinline__ unsigned long long prune_key(double p) {
 }
 
 __global__ void __launch_bounds__(256) k_ld_prune_edges(const long *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ prio, long n, int round,
-                                                        const int *__restrict__ state, int *__restrict__ rm, int *__restrict__ bl, const int *__restrict__ und_prev) {
+                                                        const int *__restrict__ state, int *__restrict__ rm, int *__restrict__ bl, const int *__restrict__ und_prev,
+                                                        long blk0) {
   if (und_prev && *und_prev == 0) return;                    // converged in an earlier round of this batch
-  const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
   const int lane = threadIdx.x & 63, si = state[i];
   if (si != 0 && (si != round - 1 || round == 1)) return;   // neither undecided nor kept in the previous round (kPruneRemoved is never round - 1)
@@ -2508,8 +2513,8 @@ __global__ void __launch_bounds__(256) k_ld_prune_result(long n, const int *__re
 // that minimum (prio == nullptr: every neighbour).  The row's own minimum is reduced over the wave first: one atomic per row for it.
 template <bool KEY>
 __global__ void __launch_bounds__(256) k_ld_prune_owner(const long *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ prio, long n,
-                                                        const int *__restrict__ state, unsigned long long *__restrict__ key, int *__restrict__ owner) {
-  const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+                                                        const int *__restrict__ state, unsigned long long *__restrict__ key, int *__restrict__ owner, long blk0) {
+  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
   const int lane = threadIdx.x & 63;
   const bool ki = state[i] > 0;
@@ -2547,9 +2552,9 @@ __global__ void __launch_bounds__(256) k_ld_prune_check_rowptr(const long *__res
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n && ((i == 0 && rowptr[0] != 0) || rowptr[i + 1] < rowptr[i])) atomicOr(bad, 1);
 }
-__global__ void __launch_bounds__(256) k_ld_prune_check_col(const long *__restrict__ rowptr, const int *__restrict__ col, long n, int *__restrict__ bad) {
+__global__ void __launch_bounds__(256) k_ld_prune_check_col(const long *__restrict__ rowptr, const int *__restrict__ col, long n, int *__restrict__ bad, long blk0) {
   if (*bad) return;
-  const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
   const long k0 = rowptr[i], k1 = rowptr[i + 1];
   for (long k = k0 + (threadIdx.x & 63); k < k1; k += 64) {
@@ -2620,7 +2625,11 @@ static int ld_prune_graph(const char *who, long snps, const long *d_rowptr, cons
   int *r_owner = !owner ? nullptr : out_dev ? owner : (int *)d_owner.p;
   MXA_HIP(hipMemsetAsync(state, 0, 3 * sizeof(int) * n, s));
   MXA_HIP(hipMemsetAsync(d_kept, 0, sizeof(unsigned long long), s));
-  const dim3 rows_grid((unsigned)((snps + 3) / 4)), vert_grid((unsigned)((snps + 255) / 256));   // one wave per row (edge and owner passes); one thread per SNP
+  // One wave per row (edge and owner passes): 64 snps threads, 2^32 of them from 2^26 SNPs on, so these sweeps run in pieces (launch_in_block_chunks; the
+  // pieces of a round read the states the round before left and write round stamps and atomic minima only, so their order does not matter).  One thread per
+  // SNP in the vertex passes: snps is an int, a single launch.
+  const long rows_blocks = (snps + 3) / 4;
+  const dim3 vert_grid((unsigned)((snps + 255) / 256));
   int h_und[kPruneBatchMax];
   int round = 0, done = 0;
   for (int batch = kPruneBatch0; !done; batch = std::min(2 * batch, kPruneBatchMax)) {
@@ -2628,7 +2637,9 @@ static int ld_prune_graph(const char *who, long snps, const long *d_rowptr, cons
     for (int b = 0; b < batch; b++) {
       round++;
       const int *prev = b ? d_und + b - 1 : nullptr;
-      hipLaunchKernelGGL(k_ld_prune_edges, rows_grid, dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, round, (const int *)state, rm, bl, prev);
+      launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
+        hipLaunchKernelGGL(k_ld_prune_edges, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, round, (const int *)state, rm, bl, prev, blk0);
+      });
       hipLaunchKernelGGL(k_ld_prune_vertices, vert_grid, dim3(256), 0, s, snps, round, state, (const int *)rm, (const int *)bl, d_und + b, d_kept, prev);
     }
     MXA_HIP(hipGetLastError());
@@ -2639,8 +2650,12 @@ static int ld_prune_graph(const char *who, long snps, const long *d_rowptr, cons
   }
   hipLaunchKernelGGL(k_ld_prune_result, vert_grid, dim3(256), 0, s, snps, (const int *)state, r_keep, r_owner, (unsigned long long *)d_key.p);
   if (owner) {
-    if (d_prio) hipLaunchKernelGGL(k_ld_prune_owner<true>, rows_grid, dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner);
-    hipLaunchKernelGGL(k_ld_prune_owner<false>, rows_grid, dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner);
+    if (d_prio) launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
+      hipLaunchKernelGGL(k_ld_prune_owner<true>, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner, blk0);
+    });
+    launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
+      hipLaunchKernelGGL(k_ld_prune_owner<false>, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner, blk0);
+    });
   }
   MXA_HIP(hipGetLastError());
   unsigned long long h_kept = 0;
@@ -2703,7 +2718,9 @@ static int ld_prune_csr(const char *who, long snps, const long *rowptr, const in
   if (cl_dev && nnz) {
     if (!d_bad.p && d_bad.alloc(sizeof(int))) return 1;
     MXA_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_ld_prune_check_col, dim3((unsigned)((snps + 3) / 4)), dim3(256), 0, s, d_rowptr, col, snps, (int *)d_bad.p);
+    launch_in_block_chunks((snps + 3) / 4, [&](unsigned nb, long blk0) {
+      hipLaunchKernelGGL(k_ld_prune_check_col, dim3(nb), dim3(256), 0, s, d_rowptr, col, snps, (int *)d_bad.p, blk0);
+    });
     MXA_HIP(hipGetLastError());
     int bad = 0;
     MXA_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -20,6 +20,16 @@ constexpr int kRowAlign = 512;     // packed matrices are padded to a multiple o
 constexpr int kTileRows = 256;     // rows per HBM tile
 constexpr int kTileBytes = kTileRows * kSlabBytes;   // 8 KiB
 
+// A launch may not exceed 2^32 - 1 threads (grid x block): the runtime truncates a larger 1-D grid of 256-thread workgroups to its value modulo 2^24 without
+// an error.  A 1-D launch whose workgroup count can reach 2^24 goes through launch_in_block_chunks (DESIGN.md 2 lists them): `launch(nb, blk0)` is called for consecutive
+// pieces of at most kMaxBlocksPerLaunch workgroups (x 256 threads = 2^31 threads), the kernel takes blk0 and works on workgroup blk0 + blockIdx.x.  The pieces
+// are enqueued on one stream in ascending order; a grid that fits is one launch with blk0 = 0, the same workgroups doing the same work as before.
+constexpr long kMaxBlocksPerLaunch = 1L << 23;
+template <typename Launch>
+inline void launch_in_block_chunks(long blocks, Launch &&launch) {
+  for (long b0 = 0; b0 < blocks; b0 += kMaxBlocksPerLaunch) launch((unsigned)(blocks - b0 < kMaxBlocksPerLaunch ? blocks - b0 : kMaxBlocksPerLaunch), b0);
+}
+
 struct Options {
   bool gpu = true;
   bool centered = true;      // genetics.centered = !do_not_center (5codesAPI.c:59-68)

@@ -25,7 +25,6 @@ namespace mxa {
 // staging: recode
 // =====================================================================================================
 // PLINK code c -> allele count z = max(c-1,0): 00->00, 01->00 (missing), 10->01, 11->10, SWAR on 16 fields.
-constexpr long kMaxBlocksPerLaunch = 1L << 23;   // x 256 threads = 2^31 threads per launch (the runtime's limit is 2^32 - 1)
 
 __device__ __forceinline__ uint32_t recode16(uint32_t w) {
   const uint32_t H = (w >> 1) & 0x55555555u, L = w & 0x55555555u;

@@ -72,11 +72,12 @@ int need_device_bytes(const char *who, size_t need) {
 }  // namespace
 
 // ---- kernels
-// Mirror: one workgroup per row j of the mirrored layout.  k >= j comes from row j of the upper rows (coalesced), k < j from row k (a gather: one uncoalesced
-// pass, run once per object; neighbouring rows j touch neighbouring addresses, so most of it is served by the L2).
+// Mirror: one workgroup per row j = blk0 + blockIdx.x of the mirrored layout (launch_in_block_chunks: snps workgroups of 256 threads pass 2^32 threads at 2^24
+// SNPs).  k >= j comes from row j of the upper rows (coalesced), k < j from row k (a gather: one uncoalesced pass, run once per object; neighbouring rows j
+// touch neighbouring addresses, so most of it is served by the L2).
 __global__ void __launch_bounds__(256) k_ld_op_mirror(const double *__restrict__ upper, const long *__restrict__ rowptr, const long *__restrict__ ptr,
-                                                       const int *__restrict__ first, const int *__restrict__ last, double *__restrict__ full) {
-  const int j = (int)blockIdx.x;
+                                                       const int *__restrict__ first, const int *__restrict__ last, double *__restrict__ full, long blk0) {
+  const int j = (int)(blk0 + blockIdx.x);
   const int f = first[j], l = last[j];
   const long dst = ptr[j] - f, up = rowptr[j] - j;
   for (int k = f + (int)threadIdx.x; k <= l; k += 256) full[dst + k] = k >= j ? upper[up + k] : upper[rowptr[k] + (j - k)];
@@ -84,8 +85,8 @@ __global__ void __launch_bounds__(256) k_ld_op_mirror(const double *__restrict__
 
 // the upper ragged rows back out of the mirrored ones
 __global__ void __launch_bounds__(256) k_ld_op_upper(const double *__restrict__ full, const long *__restrict__ rowptr, const long *__restrict__ ptr,
-                                                      const int *__restrict__ first, const int *__restrict__ last, double *__restrict__ upper) {
-  const int j = (int)blockIdx.x;
+                                                      const int *__restrict__ first, const int *__restrict__ last, double *__restrict__ upper, long blk0) {
+  const int j = (int)(blk0 + blockIdx.x);
   const long src = ptr[j] - first[j], up = rowptr[j] - j;
   for (int k = j + (int)threadIdx.x; k <= last[j]; k += 256) upper[up + k] = full[src + k];
 }
@@ -329,8 +330,10 @@ int finish_create(const char *who, long snps, const std::vector<int> &h_last, De
   MXA_HIP(hipMemcpy(base.p, h_base.data(), sizeof(long) * (size_t)snps, hipMemcpyHostToDevice));
   hipStream_t s = nullptr;
   MXA_HIP(hipStreamCreateWithFlags(&s, hipStreamDefault));   // blocking: ordered against the caller's default-stream work
-  hipLaunchKernelGGL(k_ld_op_mirror, dim3((unsigned)snps), dim3(256), 0, s, (const double *)upper.p, (const long *)rowptr.p, (const long *)ptr.p, (const int *)first.p,
-                     (const int *)last.p, (double *)full.p);
+  launch_in_block_chunks(snps, [&](unsigned nb, long blk0) {
+    hipLaunchKernelGGL(k_ld_op_mirror, dim3(nb), dim3(256), 0, s, (const double *)upper.p, (const long *)rowptr.p, (const long *)ptr.p, (const int *)first.p,
+                       (const int *)last.p, (double *)full.p, blk0);
+  });
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) { (void)hipStreamDestroy(s); MXA_HIP(e); }
@@ -455,8 +458,10 @@ extern "C" int mxa_ld_op_rows(void *op, double *rows) {
   const size_t bytes = sizeof(double) * (size_t)o->entries;
   if (!dev && (need_device_bytes(who, bytes) || tmp.alloc(bytes))) return 1;
   double *d = dev ? rows : (double *)tmp.p;
-  hipLaunchKernelGGL(k_ld_op_upper, dim3((unsigned)o->snps), dim3(256), 0, o->stream, (const double *)o->d_full, (const long *)o->d_rowptr, (const long *)o->d_ptr,
-                     (const int *)o->d_first, (const int *)o->d_last, d);
+  launch_in_block_chunks(o->snps, [&](unsigned nb, long blk0) {
+    hipLaunchKernelGGL(k_ld_op_upper, dim3(nb), dim3(256), 0, o->stream, (const double *)o->d_full, (const long *)o->d_rowptr, (const long *)o->d_ptr,
+                       (const int *)o->d_first, (const int *)o->d_last, d, blk0);
+  });
   MXA_HIP(hipGetLastError());
   if (!dev) MXA_HIP(hipMemcpyAsync(rows, d, bytes, hipMemcpyDeviceToHost, o->stream));
   MXA_HIP(hipStreamSynchronize(o->stream));

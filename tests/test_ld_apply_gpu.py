@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 U, NC = ar.U, ar.NC
 SENTINEL = -12345.678
 SHAPES = [(777, 515), (130, 1031), (1300, 67)]
-NS = (1, 3, NC, NC + 1, 40)
+NS = (1, 3, NC, NC + 1, 40, 2, 4, 7, 9, 15)
 ROUTES = ("plain", "pairwise-missing", "pairwise-missing-free")
 UNIT_COLUMNS = (0, 31, 32, 255, 256, 257, 511, 512, 699)
 

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 U = opr.U
 SENTINEL = -12345.678
 SHAPES = [(777, 515), (130, 1031), (1300, 67)]
-NS = (1, 3, 16, 17, 40)
+NS = (1, 3, 16, 17, 40, 2, 4, 7, 9, 15)           # every kernel of apply_device: <1, 8>, <2, 8>, <4, 4> partial and full, <8, 4> and <16, 4> partial and full
 ROUTES = ("plain", "pairwise-missing", "pairwise-missing-free")
 UNIT_COLUMNS = (0, 31, 32, 255, 256, 257, 511, 512, 699)
 SHIFTS = (0.0, 0.5, -2.0)

@@ -299,26 +299,10 @@ def test_more_than_two_to_the_31_stored_entries(mx):
     if torch.cuda.mem_get_info()[0] < 40 * 10 ** 9:
         pytest.skip("needs 40 GB of free device memory")
     dev = torch.device("cuda", 0)
-    snps, indiv, w = 100_000, 64, 32_767
-    rng = np.random.default_rng([snps, indiv])
-    Z = rng.binomial(2, rng.uniform(0.05, 0.95, size=snps)[:, None], size=(snps, indiv)).astype(np.int8)
-    const = Z.min(axis=1) == Z.max(axis=1)
-    Z[const, 0], Z[const, 1] = 0, 2
-    X = np.ascontiguousarray(pack_plink(Z))
-    assert np.array_equal(ref.staged(X[:50])[:, :indiv], Z[:50])
-    Zl = Z.astype(np.int64)
-    f = Zl.sum(axis=1) / (2.0 * indiv)
-    diag = (Zl * Zl).sum(axis=1)
-    assert np.all(diag - 4.0 * indiv * f * f > 0)
-    last = ref.fixed_last(snps, w)
-    rowptr = ref.rowptr_of(last)
-    total = int(rowptr[-1])
-    assert total == 2_739_945_472 and total > 2 ** 31
-    # 10^5 sampled entries: half of them above flat index 2^31, 64 in the last row and the rows before it
-    k = np.concatenate([rng.integers(0, 2 ** 31, size=50_000), rng.integers(2 ** 31, total, size=49_936), np.arange(total - 64, total)])
-    si = np.searchsorted(rowptr, k, side="right") - 1
-    sj = si + (k - rowptr[si])
-    assert np.all(sj <= last[si]) and (k > 2 ** 31).sum() * 3 >= len(k) and (si == snps - 1).any() and len(k) == 100_000
+    from _ld_limits_ref import big_window_problem
+    P = big_window_problem()                                # the generator, shared with tests/test_ld_limits_gpu.py
+    snps, indiv, w, rng, X, Zl, f, diag = P["snps"], P["indiv"], P["w"], P["rng"], P["X"], P["Zl"], P["f"], P["diag"]
+    last, total, k, si, sj = P["last"], P["total"], P["k"], P["si"], P["sj"]
     r, b = ref.ld_ref_pairs((Zl[si] * Zl[sj]).sum(axis=1), diag[si], diag[sj], f[si], f[sj], indiv)
     Xd, fd, lastd = torch.from_numpy(X).to(dev), torch.from_numpy(f).to(dev), torch.from_numpy(last).to(dev)
     L = mx.lib.check_library_handle()

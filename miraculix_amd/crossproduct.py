@@ -130,7 +130,7 @@ PAIRWISE_SLOT_BYTES = 256 * 256 * 4                           # one int32 count 
 
 
 def ld_pairwise_group_rows(snps, window, scratch_mb=2048, pairs=6):
-    """Tile rows per group of the pairwise entries: as many as keep the count scratch (pairs slots of 256 KiB per band tile, a tile row holding up to
+    """Tile rows per group of the pairwise entries (LdGroups in csrc/mxa_ldwindow.hip, the fixed window): as many as keep the count scratch (pairs slots of 256 KiB per band tile, a tile row holding up to
     min(nb, ceil(window / 256) + 1) tiles) under scratch_mb MiB -- one tile row at least, the whole band at most."""
     nb = (snps + 255) // 256
     row_tiles = min(nb, (window + 255) // 256 + 1)
@@ -138,7 +138,7 @@ def ld_pairwise_group_rows(snps, window, scratch_mb=2048, pairs=6):
 
 
 def ld_pairwise_tiles(snps, window, group):
-    """The tile plan of the pairwise entries, restated: the band tiles of ld_band_tiles in groups of `group` tile rows; per band tile (I, J) six entries
+    """The tile plan of the pairwise entries (pairwise_group_tiles in csrc/mxa_ldwindow.hip), restated: the band tiles of ld_band_tiles in groups of `group` tile rows; per band tile (I, J) six entries
     (x, y, slot) over the stacked operand of 3 nb row blocks, x = plane_a * nb + I, y = plane_b * nb + J for the pairs of PAIRWISE_PAIRS, written to the
     scratch slots 6 q .. 6 q + 5 of the tile's position q within its group.  Returns the list of groups."""
     nb = (snps + 255) // 256

@@ -15,6 +15,7 @@
 #include "mxa_internal.h"
 #include "mxa_queue.h"
 #include "mxa_hostmem.h"
+#include "mxa_xprod.h"
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -116,11 +117,6 @@ __global__ void __launch_bounds__(256) k_xstage_planes(const uint8_t *__restrict
 }
 
 // ---- main kernel -----------------------------------------------------------------------------------------------
-constexpr int kXT = 256;              // tile edge (rows of X per operand block)
-constexpr int kXStageK = 128;         // genotypes per LDS stage = 32 packed bytes per row
-constexpr int kXStageBytes = kXStageK / 4;
-constexpr int kXOpBytes = kXT * kXStageBytes;     // 8 KiB per operand per stage
-constexpr int kXBufBytes = 2 * kXOpBytes;
 
 // 16 two-bit fields of a dword -> 16 int8 in 4 dwords (field order permuted identically for both operands)
 __device__ __forceinline__ v4i unpack16(uint32_t w) {
@@ -132,173 +128,19 @@ __device__ __forceinline__ v4i unpack16(uint32_t w) {
   return r;
 }
 
-// Element-wise map applied by the epilogue (round 3: the GRM / LD post-processing of the reference's binding, crossproduct.jl:83-152, FUSED into
-// the crossproduct -- SURVEY.md 8f-3 -- instead of three more passes over the 8 n^2-byte result).  Everything the map needs is known BEFORE the
-// product: the column sums of M = X X^T are X (X^T 1) and its diagonal is the row-wise sum of squares, both exact integers computed from the staged
-// 2-bit matrix (k_x_colsum, k_x_rowstats).  The same two functions serve the unfused kernels (k_grm_update, k_ld_center / k_ld_scale: kept for
-// MXA_XPROD_FUSED_POST=0 and as the bit-identity check of the tests): i = row index, j = column index of the element as stored.
-// The epilogue kinds: the POST argument of the kernels and the post_kind of their launchers (plain ints, so that the kernels' symbols stay what they were).
-// kPostGrm and kPostLd are also the `post` of crossprod_any.
-constexpr int kPostNone = 0;        // the plain crossproduct
-constexpr int kPostGrm = 1;         // GRM map
-constexpr int kPostLd = 2;          // LD map
-constexpr int kPostLdBand = 3;      // windowed LD: the LD map into band storage
-constexpr int kPostLdScores = 4;    // windowed LD: the LD map reduced to per-SNP scores
-constexpr int kPostCounts = 5;      // pairwise-complete LD: the raw counts into a scratch slot
-constexpr int kPostKinds = 6;
-struct XPost {
-  const double *u = nullptr;      // GRM: column sums cs of M;  LD: allele frequencies f
-  const double *w = nullptr;      // LD: 1 / sigma
-  const double *scal = nullptr;   // GRM: scal[0] = sum(cs), scal[1] = 2 sum f (1 - f)
-  double a = 0.0;                 // GRM: 1 / n;  LD: 4 * indiv
-  int do_scale = 0;
-  const int *last = nullptr;      // kPostLdBand, kPostLdScores: the general window's ends last[] (LdVarWindow; nullptr: the fixed window) ...
-  const long *rowptr = nullptr;   // ... and the row starts of its ragged storage; read by no other instantiation
-};
-// The two divisions of the reference (by the scalar c, by sigma_i and sigma_j) are multiplications by reciprocals formed once (<= 1 ulp from the
-// quotient; the stated tolerance of this path is 1e-12): an fp64 division is ~15 instructions on the pipe the epilogue shares with nothing else.
-// Every map is symmetric in (i, j) bit for bit -- the per-index operands are combined by a commutative operation first -- so that element (i, j) and
-// element (j, i) of a GRM / LD result are equal (the reference's order, two rank-1 updates one after the other, rounds them differently).
 __device__ __forceinline__ double grm_map(double v, double cs_i, double cs_j, double inv_n, double tot_nn, double inv_c, int do_scale) {
   v = fma(-(cs_i + cs_j), inv_n, v);   // BLAS.ger!(-1/indiv, col_sum, one_vector, M); BLAS.ger!(-1/indiv, one_vector, col_sum, M)  (cs_i + cs_j: exact integers)
   v = v + tot_nn;                      // M .+= sum(col_sum) / indiv^2
   if (do_scale) v *= inv_c;            // M ./= 2 sum f (1 - f)
   return v;
 }
-__device__ __forceinline__ double ld_center_map(double v, double f_i, double f_j, double four_indiv) { return fma(-four_indiv, f_i * f_j, v); }   // syr!('U', -4 indiv, f, M)
-__device__ __forceinline__ double ld_scale_map(double v, double is_i, double is_j) { return v * (is_i * is_j); }                                  // M ./= sigma; M ./= sigma' (is = 1 / sigma)
+
 
 // Epilogue shared by both engines.  32x32 C/D map: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5); element (gi, gj) = M[gi][gj].
 // The output holds columns [c0, ..) of M with leading dimension ld (whole matrix: c0 = 0, ld = n).
 // Direct image: M[gj, gi] at ans[gj + (gi-c0)*ld], lanes run along gj (256-byte segments).  Mirror image M[gi, gj] at
 // ans[gi + (gj-c0)*ld]: the tile is transposed through a per-wave LDS scratch (row stride 33 doubles: conflict-free both ways)
 // so its lanes run along gi as well.  AccT = v16i: exact int32 sums; v16f: sums of z z' / 4 (FP4 engine), exact, times 4.
-typedef float v16f __attribute__((ext_vector_type(16)));
-// the result is written once and never read by this kernel: non-temporal stores keep the 8 n^2 bytes from displacing the packed operand tiles, which ~n/256
-// tiles re-read, in the L2s and the Infinity Cache (MXA_XPROD_NT_STORE=0 at compile time: plain stores, for an A/B; round 3: docs/HISTORY.md)
-#ifndef MXA_XPROD_NT_STORE
-#define MXA_XPROD_NT_STORE 1
-#endif
-__device__ __forceinline__ void xstore(double *p, double v) {
-#if MXA_XPROD_NT_STORE
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-// ---- windowed LD (mxa_ld_band, mxa_ld_scores; by distance: mxa_ld_window_rows, mxa_ld_window_scores): the LD map of kPostLd on the tiles of a window,
-// written as band storage or ragged rows (kPostLdBand), or reduced to per-SNP scores (kPostLdScores).  These two instantiations reuse the kernels' arguments:
-// ans = the band / the rows / the partial buffer P, ld = its leading dimension ldb / the row stride of P, c0 = the window, post.do_scale = kind / adjust.
-// The general window arrives in post.last and post.rowptr (c0 = the ndiag of P then); post.last == nullptr is the fixed window: one wave-uniform branch.
-// tile diagonals dt = J - I a window touches: tile (I, J) holds the offsets j - i in [256 dt - 255, 256 dt + 255], so it meets the band iff
-// 256 dt - 255 <= window, i.e. dt <= (window + 255) / 256 = ceil(window / 256) -- one more diagonal than window / 256 unless the window ends on a tile edge
-__host__ __device__ __forceinline__ int ld_band_diagonals(long window) { return (int)((window + 255) / 256); }
-// The window, in one place, as a small object with two instances.  in(i, j): element (i, j), i <= j < n, of R belongs to the window of i; beyond(i_base, j_base, n),
-// wave-uniform: no row of the 32-row sub-block that starts at row i_base reaches column j_base >= i_base (i_base or j_base may lie in the padding at or
-// beyond n: nothing is indexed out of range); at(gi, gj, ld): where row gi stores its element gj; ndiag(): tile diagonals in the scores' partial buffer.
-// Fixed (mxa_ld_band, mxa_ld_scores and the pairwise pair): `window` SNPs on each side; the band band[(gj - gi) + gi * ld].
-struct LdFixedWindow {
-  long window;
-  __device__ __forceinline__ bool in(long i, long j) const { return j - i <= window; }
-  __device__ __forceinline__ bool beyond(long i_base, long j_base, long) const { return !in(i_base + 31, j_base); }
-  __device__ __forceinline__ size_t at(long gi, long gj, long ld) const { return (size_t)(gj - gi) + (size_t)gi * ld; }
-  __device__ __forceinline__ int ndiag() const { return ld_band_diagonals(window); }
-};
-// General (mxa_ld_window_*): j is in the window of i <= j iff j <= last[i], with i <= last[i] < n non-decreasing (base pairs, centimorgans, SNP counts and
-// chromosome ends alike: mxa_ld_window_bounds); ragged rows rows[(gj - gi) + rowptr[gi]], rowptr = the exclusive prefix sum of last[i] - i + 1.  A sub-block
-// is judged by its last row below n (last is non-decreasing); with i_base >= n that is row n - 1, whose last[n - 1] = n - 1 < i_base <= j_base.
-struct LdVarWindow {
-  const int *__restrict__ last;
-  const long *__restrict__ rowptr;
-  int nd;
-  __device__ __forceinline__ bool in(long i, long j) const { return j <= (long)last[i]; }
-  __device__ __forceinline__ bool beyond(long i_base, long j_base, long n) const { return j_base > (long)last[min(i_base + 31, n - 1)]; }
-  __device__ __forceinline__ size_t at(long gi, long gj, long) const { return (size_t)(gj - gi) + (size_t)rowptr[gi]; }
-  __device__ __forceinline__ int ndiag() const { return nd; }
-};
-// partial buffer of the scores: P[side][dt][row], side 0 = the tile's I rows (sums over gj), side 1 = its J rows (sums over gi; off the diagonal only)
-__host__ __device__ __forceinline__ size_t ld_score_slot(int side, int dt, int ndiag, long stride) { return ((size_t)side * (size_t)(ndiag + 1) + (size_t)dt) * (size_t)stride; }
-constexpr int kXScratchBytes = 4 * 32 * 33 * 8;   // the four waves' 32 x 33 epilogue scratch; the score reduction area lies behind it
-
-// The one store of the windowed entries: the only place that knows the band layout, the window tests, the summation order and the slots of P.  It serves the
-// crossproduct kernels (xprod_store_window below) and the combine kernel of the pairwise-complete entries (k_ld_pw_combine) alike: prep(a, b) readies the
-// lane's sub-block (a, b); val(a, b, r) is what goes to the LDS scratch for the element that accumulator register r of that sub-block holds in the crossproduct
-// kernels; fin(v, i, j) finishes a value read back from the scratch into the band entry (kPostLdBand; squared: v * v is stored) or the score term
-// (kPostLdScores) of element (i, j), i, j < n.  SCORES: the reduction, else the store; win: the window object (LdFixedWindow, LdVarWindow).
-template <bool SCORES, typename Win, typename Prep, typename Val, typename Fin>
-__device__ __forceinline__ void ld_window_store(const Win win, Prep prep, Val val, Fin fin, bool squared, char *smem, int wave, int lane, int wi, int wj, long i0, long j0,
-                                                long n, double *__restrict__ out, long ld) {
-  double *scratch = reinterpret_cast<double *>(smem) + wave * (32 * 33);
-  const int col = lane & 31, hh = lane >> 5, rq = 4 * hh;
-  if constexpr (!SCORES) {
-    // band storage band[(gj - gi) + gi * ld]: for fixed gi the band row is contiguous along gj, and the direct image runs its lanes along gj
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-        const long gj = gj_base + col;
-        if (gj_base + 31 < gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: the sub-block lies wholly below the diagonal or beyond the band
-        prep(a, b);
-#pragma unroll
-        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
-        if (gj < n) {
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + rq;
-            const long gi = gi_base + row;
-            if (gi <= gj && win.in(gi, gj)) {
-              const double v = fin(scratch[row * 33 + col], gj, gi);
-              xstore(&out[win.at(gi, gj, ld)], squared ? v * v : v);
-            }
-          }
-        }
-      }
-  } else {
-    // scores: t(r) summed along the rows of the tile (for its I rows) and, off the diagonal, along its columns (for its J rows); every sum in a fixed order:
-    // a lane over its elements, then (hh 0 + hh 1) + (second wave's hh 0 + hh 1) through the LDS; one store per slot, no atomics
-    const bool diag_tile = i0 == j0;
-    double rowacc[4] = {0.0, 0.0, 0.0, 0.0}, colacc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-        const long gj = gj_base + col, gi = gi_base + col;
-        // wave-uniform: no element of the sub-block is within the window (on the diagonal tile both triangles count: |gj - gi| <= window)
-        if (gj_base >= gi_base ? win.beyond(gi_base, gj_base, n) : win.beyond(gj_base, gi_base, n)) continue;
-        prep(a, b);
-#pragma unroll
-        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = val(a, b, r);
-        if (!diag_tile && gj < n) {                            // J side: lane = column gj, its 16 rows gi (gi < gj < n)
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + rq;
-            if (win.in(gi_base + row, gj)) colacc[b] += fin(scratch[row * 33 + col], gj, gi_base + row);
-          }
-        }
-        if (gi < n) {                                          // I side: lane = row gi, the columns gj_base + cc of its half
-#pragma unroll
-          for (int it = 0; it < 16; it++) {
-            const int cc = 2 * it + hh;
-            const long gjj = gj_base + cc;
-            if (gjj < n && win.in(min(gi, gjj), max(gi, gjj))) rowacc[a] += fin(scratch[col * 33 + cc], gi, gjj);
-          }
-        }
-      }
-    double *red = reinterpret_cast<double *>(smem + kXScratchBytes);   // red[side][wave][hh][a or b][32]
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      red[(((0 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = rowacc[q];
-      red[(((1 * 4 + wave) * 2 + hh) * 4 + q) * 32 + col] = colacc[q];
-    }
-    __syncthreads();
-    const int r = threadIdx.x, half = r >> 7, q = (r >> 5) & 3, c = r & 31, dt = (int)((j0 - i0) / kXT), ndiag = win.ndiag();
-    auto slot = [&](int side, int w) { return red[(((side * 4 + w) * 2 + 0) * 4 + q) * 32 + c] + red[(((side * 4 + w) * 2 + 1) * 4 + q) * 32 + c]; };
-    out[ld_score_slot(0, dt, ndiag, ld) + (size_t)(i0 + r)] = slot(0, half * 2 + 0) + slot(0, half * 2 + 1);          // row i0 + r: the waves (wi = half, wj = 0, 1)
-    if (!diag_tile) out[ld_score_slot(1, dt, ndiag, ld) + (size_t)(j0 + r)] = slot(1, 0 * 2 + half) + slot(1, 1 * 2 + half);   // row j0 + r: the waves (wi = 0, 1, wj = half)
-  }
-}
 
 // The crossproduct kernels' side of it: the scratch takes the accumulators as fp64, and a value read back is mapped with the LD map of kPostLd (post.u is the
 // caller's freq, of length n: fin is only ever called with i, j < n) -- into the band entry r, or the score term t(r).
@@ -328,22 +170,7 @@ __device__ __forceinline__ void xprod_store_window(const AccT (&acc)[4][4], char
   else store(LdFixedWindow{window});
 }
 
-// Count store (kPostCounts, pairwise-complete LD): the raw accumulators of the tile as int32 (FP4 engine: acc x 4, exact) into the scratch slot the tile entry
-// names (its fourth field), 65 536 ints.  Lane-linear and register-major in quads: registers 4 q .. 4 q + 3 of thread t at slot + q * 1024 + 4 t, one 16-byte
-// store per lane and quad (a wave writes 1 KiB contiguous); no LDS transpose.  The combine kernel reads the same addresses with the same lane <-> element map.
-constexpr size_t kPwSlotInts = (size_t)kXT * kXT;
-template <typename AccT>
-__device__ __forceinline__ void xprod_store_counts(const AccT (&acc)[4][4], int *__restrict__ scratch, int slot) {
-  int4 *p = reinterpret_cast<int4 *>(scratch + (size_t)slot * kPwSlotInts) + threadIdx.x;
-  auto cnt = [](auto v) -> int { if constexpr (__is_same(AccT, v16f)) return (int)(v * 4.0f); else return v; };
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-        p[((a * 4 + b) * 4 + q) * 256] = make_int4(cnt(acc[a][b][4 * q]), cnt(acc[a][b][4 * q + 1]), cnt(acc[a][b][4 * q + 2]), cnt(acc[a][b][4 * q + 3]));
-}
+
 
 // POST: kPostNone, kPostGrm, kPostLd (XPost above); each stored element is mapped with ITS OWN (row, column), so both images equal what
 // the unfused element-wise kernels produce.  With a map the 32 x 32 block goes to the LDS scratch first (static accumulator indices) and both images
@@ -367,7 +194,7 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
         const long gj = gj_base + col;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int row = (r & 3) + 8 * (r >> 2) + rq;
+          const int row = xacc_row(r, rq);
           const double v = (double)acc[a][b][r] * scale;
           if ((images & 1) && gi_base + row < n && gj < n) xstore(&ans[(size_t)gj + (size_t)(gi_base + row - c0) * ld], v);
           scratch[row * 33 + col] = v;
@@ -396,11 +223,11 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
         const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
         const long gj = gj_base + col, gi = gi_base + col;
 #pragma unroll
-        for (int r = 0; r < 16; r++) scratch[((r & 3) + 8 * (r >> 2) + rq) * 33 + col] = (double)acc[a][b][r] * scale;
+        for (int r = 0; r < 16; r++) scratch[xacc_row(r, rq) * 33 + col] = (double)acc[a][b][r] * scale;
         if ((images & 1) && gj < n) {                          // direct image: row index gj, column index gi_base + row
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + rq;
+            const int row = xacc_row(r, rq);
             if (gi_base + row < n) xstore(&ans[(size_t)gj + (size_t)(gi_base + row - c0) * ld], map(scratch[row * 33 + col], gj, gi_base + row));
           }
         }
@@ -747,40 +574,12 @@ static bool gang_order_tiles(std::vector<int4> &tiles) {
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 static thread_local bool tl_xprod_shared_device = false;   // set by the panel workers of snp_multiply_gpu when several panels share a device
 static std::mutex g_xprof_mutex;   // panels of one call run in several threads (MIRACULIX_NUM_GPUS): the profile counters are shared
-namespace {
-struct XEvent {   // RAII: events, streams and device buffers are released on every exit path
-  hipEvent_t e = nullptr;
-  ~XEvent() { if (e) (void)hipEventDestroy(e); }
-  int create(unsigned flags = hipEventDefault) { MXA_HIP(hipEventCreateWithFlags(&e, flags)); return 0; }
-};
-struct XStream {
-  hipStream_t s = nullptr;
-  ~XStream() { if (s) (void)hipStreamDestroy(s); }
-  int create(unsigned flags) { MXA_HIP(hipStreamCreateWithFlags(&s, flags)); return 0; }
-};
-struct XBuf {
-  void *p = nullptr;
-  ~XBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { MXA_HIP(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; } }
-};
-// Geometry of one call: X has `rows` rows, staged as nb tiles of 256 rows; a staged row is nslabs slabs of 128 genotypes (32 bytes, the pitch), one
-// K stage of the kernels each.
-struct XGeom {
-  long rows;
-  int nb, stages;
-  long nslabs;
-  XGeom(long k, long r) : rows(r), nb((int)((r + kXT - 1) / kXT)), stages((int)((k + kXStageK - 1) / kXStageK)), nslabs(stages) {}
-  long rows_pad() const { return (long)nb * kXT; }
-  size_t pitch() const { return (size_t)nslabs * kXStageBytes; }
-};
-}  // namespace
 
 // measured time of one 256 x 256 tile per K stage on one CU (FP4 / int8 MFMA): the estimates of the gang decision and of the ring
 static double tile_stage_ms(bool f4) { return f4 ? 0.66e-3 : 1.0e-3; }
 
 // the profile counts one launch per call, with the time between its two events
-static hipError_t profile_launch(const XEvent &e0, const XEvent &e1) {
+hipError_t profile_launch(const XEvent &e0, const XEvent &e1) {
   float ms = 0.f;
   const hipError_t err = hipEventElapsedTime(&ms, e0.e, e1.e);
   if (err == hipSuccess) { std::lock_guard<std::mutex> lk(g_xprof_mutex); profile().launches += 1; profile().total_ms += ms; }
@@ -882,31 +681,21 @@ static std::vector<int4> row_tiles(int nb, int i0, int i1) {
 // The tiles of a window, tile row by tile row: (i, j), i <= j <= jmax[i] (LdWindow::plan: a band of ld_band_diagonals tile diagonals, or the reach of the
 // tile row's last SNP).  A tile row is compact (neighbours that share row block i), which is what gang_order_tiles wants: a gang of 32 tiles is cut from
 // four adjacent tile rows.
-static std::vector<int4> window_tiles(const std::vector<int> &jmax) {
+std::vector<int4> window_tiles(const std::vector<int> &jmax) {
   std::vector<int4> tiles;
   for (int i = 0; i < (int)jmax.size(); i++)
     for (int j = i; j <= jmax[(size_t)i]; j++) tiles.push_back(make_int4(i, j, 1, 0));
   return tiles;
 }
 
-namespace {
-// The tile lists of a call's chunks, uploaded once: chunk c is d_tiles[first[c], first[c + 1]), in the gang order where gang_order_tiles took it (xcd[c]).
-// d_gang: the gangs' 32 control counters, then mid_cap ints for the counters of their meetings inside a tile, sized for the longest list.
-struct XTiles {
-  std::vector<int4> tiles;
-  std::vector<size_t> first;
-  std::vector<char> xcd;
-  size_t mid_cap = 0;
-  XBuf d_tiles, d_gang;
-  int launch(int c, const XGeom &g, bool f4, hipStream_t s, const uint8_t *d_X, double *d_ans, long ld, long c0, unsigned long long *d_diag, int post_kind,
-             const XPost &post) const {
-    return launch_tiles(g, f4, first[(size_t)c + 1] - first[(size_t)c], s, d_X, (const int4 *)d_tiles.p + first[(size_t)c], d_ans, ld, c0, d_diag, post_kind,
-                        post, xcd[(size_t)c] ? (int *)d_gang.p : nullptr, mid_cap);
-  }
-};
-}  // namespace
+// one launch of chunk c of the lists
+int XTiles::launch(int c, const XGeom &g, bool f4, hipStream_t s, const uint8_t *d_X, double *d_ans, long ld, long c0, unsigned long long *d_diag, int post_kind,
+                   const XPost &post) const {
+  return launch_tiles(g, f4, first[(size_t)c + 1] - first[(size_t)c], s, d_X, (const int4 *)d_tiles.p + first[(size_t)c], d_ans, ld, c0, d_diag, post_kind,
+                      post, xcd[(size_t)c] ? (int *)d_gang.p : nullptr, mid_cap);
+}
 
-static int upload_tiles(std::vector<std::vector<int4>> chunks, hipStream_t s, XTiles &t) {
+int upload_tiles(std::vector<std::vector<int4>> chunks, hipStream_t s, XTiles &t) {
   t.first.assign(chunks.size() + 1, 0);
   t.xcd.assign(chunks.size(), 0);
   for (size_t c = 0; c < chunks.size(); c++) {
@@ -1229,8 +1018,8 @@ static int postprocess_device(double *d_M, long rows, long k, int post, int do_s
 // *d_has3 = 1 when a staged field holds the value 3.  Host rows go through `bounce` (<= 256 MiB: kept by the caller, the pre-flight counts it).
 // planes_indiv > 0: the three planes Z, M, A of the pairwise-complete LD instead (k_xstage_planes; d_X holds 3 * rows_pad rows, *d_has3 = a missing code occurs).
 // mask_fields > 0: a row holds that many fields, its padding bits are staged as 00 (the GRM / LD entries); 0: the bytes as stored (the plain crossproduct).
-static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, bool is_plink, const XGeom &g, uint8_t *d_X, int *d_has3, XBuf &bounce,
-                         hipStream_t s, long planes_indiv = 0, long mask_fields = 0) {
+int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, bool is_plink, const XGeom &g, uint8_t *d_X, int *d_has3, XBuf &bounce,
+                         hipStream_t s, long planes_indiv, long mask_fields) {
   const long rows = g.rows;
   const size_t plane_bytes = (size_t)g.rows_pad() * g.pitch();
   MXA_HIP(hipMemsetAsync(d_X, 0, plane_bytes * (planes_indiv > 0 ? 3 : 1), s));
@@ -1260,7 +1049,7 @@ static int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_
 }
 
 // grid of the per-row passes over the staged operand (k_x_rowstats, k_pw_rowsums): (row tiles, K chunks of *spc slabs each), ~1024 blocks at least
-static dim3 rowstats_grid(const XGeom &g, long *spc) {
+dim3 rowstats_grid(const XGeom &g, long *spc) {
   const long chunks = std::max<long>(1, std::min<long>(g.nslabs, (1024 + g.nb - 1) / g.nb));
   *spc = (g.nslabs + chunks - 1) / chunks;
   return dim3((unsigned)g.nb, (unsigned)((g.nslabs + *spc - 1) / *spc));
@@ -1268,7 +1057,7 @@ static dim3 rowstats_grid(const XGeom &g, long *spc) {
 
 // What the GRM (kPostGrm) / LD (kPostLd) map fused into the epilogue needs, from the staged 2-bit matrix: ~2 passes over rows * k / 4 bytes instead of 3 over
 // 8 * rows^2.  xp points into st[2]; st[0..2] are kept by the caller until the product has run.
-static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post, int do_scale, const double *d_f, XBuf (&st)[3], hipStream_t s, XPost &xp) {
+int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post, int do_scale, const double *d_f, XBuf (&st)[3], hipStream_t s, XPost &xp) {
   const long rows = g.rows, rows_pad = g.rows_pad(), nslabs = g.nslabs, ntiles = g.nb;
   if (st[0].alloc(sizeof(int) * (size_t)nslabs * 128) || st[1].alloc(sizeof(unsigned long long) * (size_t)rows_pad) || st[2].alloc(sizeof(double) * (size_t)(rows_pad + 4))) return 1;
   MXA_HIP(hipMemsetAsync(st[1].p, 0, sizeof(unsigned long long) * (size_t)rows_pad, s));
@@ -1294,10 +1083,9 @@ static int fused_post_stats(const XGeom &g, const uint8_t *d_X, long k, int post
   return 0;
 }
 
-constexpr long kXFusedMaxRows = 29000000L;   // k_x_rowstats: 16 * 3 * (3 rows) must fit 32 bits
 
 // engine: FP4 while the fp32 accumulator is provably exact (sum z z' < 2^24), int8 beyond (MXA_XPROD_ENGINE=i8 forces int8, for A/B runs)
-static int pick_engine(const int *d_has3, long k, hipStream_t s, bool &f4) {
+int pick_engine(const int *d_has3, long k, hipStream_t s, bool &f4) {
   int has3 = 1;
   MXA_HIP(hipMemcpyAsync(&has3, d_has3, sizeof(int), hipMemcpyDeviceToHost, s));
   MXA_HIP(hipStreamSynchronize(s));
@@ -1430,1477 +1218,7 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   return 0;
 }
 
-// ---- windowed LD: the band |i - j| <= window of R, as LAPACK lower band storage (scores == 0: out = band, leading dimension ldb, flag = kind) or reduced to
-// the LD scores (scores != 0: out = scores, flag = adjust).  O(snps * window) work and memory: the tiles of band_tiles through the same kernels as mxa_ld.
-// zeros of the band's tail band[d + i * ldb], i + d >= n: window (window + 1) / 2 elements of the last `window` SNPs, not a pass over the band
-__global__ void __launch_bounds__(256) k_ld_band_tail(double *__restrict__ band, long ldb, long n, long window) {
-  const long i = n - 1 - (long)blockIdx.x;                    // blockIdx.x < window < n
-  for (long d = n - i + threadIdx.x; d <= window; d += 256) band[(size_t)d + (size_t)i * ldb] = 0.0;
-}
-// scores[i] = the slots of row i in a fixed order: the I side of the tiles (I, I + dt), then the J side of the tiles (I - dt, I); a slot exists iff its tile
-// does, and tile row I holds the tiles up to column jmax[I] (nb ints, non-decreasing)
-__global__ void __launch_bounds__(256) k_ld_score_finish(const double *__restrict__ P, long n, long stride, const int *__restrict__ jmax, int ndiag, double *__restrict__ scores) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int I = (int)(i / kXT);
-  double s = 0.0;
-  for (int dt = 0; dt <= ndiag; dt++) if (I + dt <= jmax[I]) s += P[ld_score_slot(0, dt, ndiag, stride) + (size_t)i];
-  for (int dt = 1; dt <= ndiag; dt++) if (I - dt >= 0 && jmax[I - dt] >= I) s += P[ld_score_slot(1, dt, ndiag, stride) + (size_t)i];
-  scores[i] = s;
-}
-
-// a host result of the windowed entries: the scores or the ragged rows as they are, or the compact device band (leading dimension window + 1) into the
-// caller's band of leading dimension ldb
-static int ld_window_download(const double *d_res, size_t obytes, long snps, long window, double *out, long ldb, bool compact, hipStream_t s) {
-  if (compact || ldb == window + 1) MXA_HIP(hipMemcpyAsync(out, d_res, obytes, hipMemcpyDeviceToHost, s));
-  else {   // a wider host ldb: one download, then the rows d <= window of every column (the rows beyond stay the caller's)
-    std::vector<double> h((size_t)(window + 1) * (size_t)snps);
-    MXA_HIP(hipMemcpyAsync(h.data(), d_res, obytes, hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    for (long i = 0; i < snps; i++) memcpy(out + (size_t)i * ldb, h.data() + (size_t)i * (window + 1), sizeof(double) * (size_t)(window + 1));
-  }
-  return 0;
-}
-
-namespace {
-// One call of a windowed entry: everything around the route's own staging and tile launches.  begin(): the shared argument checks, the tile plan, the sizes,
-// the pre-flight, the stream, the operand / result / partial buffers and the events; start() and finish() enclose the launches: d_dst (leading dimension
-// ld_dst) is where they write -- the band, the rows, or the scores' partial buffer P -- and finish() turns it into the result at d_res and delivers that.
-// Two ways of constructing it: the fixed window (`window` SNPs on each side; result = band of leading dimension ldb, or scores) and the general one
-// (last != nullptr: the window of SNP i ends at last[i]; result = ragged rows, or scores).  Both end in the same plan, jmax[] per tile row.
-// A third result of the general window, set_pairs(): the pairs above a cutoff as CSR (mxa_ld_window_pairs*).  `out` is then the caller's rowptr, and a host
-// result leaves from one device buffer d_out = rowptr (snps + 1 longs), val (capacity doubles), col (capacity ints); finish_pairs() instead of finish().
-struct LdWindow {
-  const char *who;
-  const unsigned char *plink;
-  long snps, indiv, window;
-  const int *last;             // the caller's, host or device; nullptr: the fixed window
-  double *out;
-  long ldb;
-  bool scores;
-  int flag;                    // kind (band, rows, pairs) / adjust (scores)
-  bool pairs = false, fill = false;   // the CSR result; fill: col / val are written (else the count-only call)
-  int *col = nullptr;
-  double *val = nullptr;
-  long capacity = 0;           // entries of col / val (0 on a count-only call)
-  bool apply = false;          // the window applied to a matrix (mxa_ld_window_apply*): out = Y, ldb = ldy, result = snps x ncols
-  int ncols = 0;
-  XGeom g;
-  long row_bytes = 0;
-  int ndiag = 0;               // tile diagonals of the partial buffer: the kernels' (ld_band_diagonals(window)), or max(jmax[I] - I)
-  std::vector<int> jmax;       // tile row I holds the tiles (I, I .. jmax[I])
-  size_t ntiles = 0, row_tiles_max = 0;
-  bool in_dev = false, out_dev = false;
-  size_t plane_bytes = 0, obytes = 0;
-  XStream st;
-  hipStream_t s = nullptr;
-  XBuf d_X, bounce, d_out, d_flag, d_P, d_jmax, d_last, d_rowptr;
-  XEvent e0, e1;
-  double *d_res = nullptr, *d_dst = nullptr;
-  long ld_res = 0, ld_dst = 0;
-  LdWindow(const char *who_, const unsigned char *plink_, long snps_, long indiv_, long window_, const int *last_, double *out_, long ldb_, bool scores_, int flag_)
-      : who(who_), plink(plink_), snps(snps_), indiv(indiv_), window(window_), last(last_), out(out_), ldb(ldb_), scores(scores_), flag(flag_), g(indiv_, snps_) {}
-  const uint8_t *X() const { return (const uint8_t *)d_X.p; }
-  bool general() const { return last != nullptr; }
-  // the epilogue kind of the crossproduct kernels and what they take for `c0`
-  int post_kind() const { return scores ? kPostLdScores : kPostLdBand; }
-  long post_c0() const { return general() ? (long)ndiag : window; }
-  void set_post(XPost &xp) const { xp.do_scale = flag; xp.last = (const int *)d_last.p; xp.rowptr = (const long *)d_rowptr.p; }
-  std::vector<int4> tiles() const { return window_tiles(jmax); }
-  void set_apply(int ncols_) { apply = true; ncols = ncols_; }
-  void set_pairs(int *col_, double *val_, long capacity_) { pairs = true; fill = col_ != nullptr; col = col_; val = val_; capacity = fill ? capacity_ : 0; }
-  // where the CSR result is formed on the device: the caller's arrays, or the pieces of d_out
-  long *d_pairs_rowptr() const { return out_dev ? reinterpret_cast<long *>(out) : (long *)d_out.p; }
-  double *d_pairs_val() const { return out_dev ? val : reinterpret_cast<double *>((long *)d_out.p + snps + 1); }
-  int *d_pairs_col() const { return out_dev ? col : reinterpret_cast<int *>(d_pairs_val() + capacity); }
-
-  // The tile plan.  Fixed: the band of ndiag tile diagonals.  General: `last` is fetched (host or device pointer) and checked, rowptr formed, and tile row I
-  // reaches as far as its last SNP does (last is non-decreasing), so every tile (I, I .. jmax[I]) holds a window element.
-  int plan(std::vector<long> &h_rowptr, std::vector<int> &h_last) {
-    jmax.resize((size_t)g.nb);
-    if (!general()) {
-      ndiag = ld_band_diagonals(window);
-      for (int I = 0; I < g.nb; I++) jmax[(size_t)I] = std::min(g.nb - 1, I + ndiag);
-    } else {
-      h_last.resize((size_t)snps);
-      MXA_HIP(hipMemcpy(h_last.data(), last, sizeof(int) * (size_t)snps, hipMemcpyDefault));
-      h_rowptr.resize((size_t)snps + 1);
-      h_rowptr[0] = 0;
-      for (long i = 0; i < snps; i++) {
-        const long l = h_last[(size_t)i];
-        if (l < i || l >= snps || (i > 0 && l < h_last[(size_t)i - 1])) {
-          set_error(1, "%s: need i <= last[i] < snps, non-decreasing (last[%ld] = %ld, snps %ld)", who, i, l, snps);
-          return 1;
-        }
-        h_rowptr[(size_t)i + 1] = h_rowptr[(size_t)i] + (l - i + 1);
-      }
-      ndiag = 0;
-      for (int I = 0; I < g.nb; I++) {
-        jmax[(size_t)I] = h_last[(size_t)std::min<long>((long)I * kXT + kXT - 1, snps - 1)] / kXT;
-        ndiag = std::max(ndiag, jmax[(size_t)I] - I);
-      }
-    }
-    for (int I = 0; I < g.nb; I++) {
-      const size_t t = (size_t)(jmax[(size_t)I] - I + 1);
-      ntiles += t;
-      row_tiles_max = std::max(row_tiles_max, t);
-    }
-    return 0;
-  }
-
-  // planes: of the staged operand; extra_bytes(): what the route allocates beyond the operand, the result and the partial buffer, for the pre-flight (called
-  // once the plan stands).  The checks run in the order in which the entries have always reported them, so the two that only one route has are passed in:
-  // route_error (a complete message, or nullptr) is reported behind "bad arguments", max_indiv (0: no bound) in front of the SNP bound; adj_msg, snps_msg:
-  // the route's wording.
-  template <typename Extra>
-  int begin(int planes, Extra extra_bytes, const char *route_error, long max_indiv, const char *adj_msg, const char *snps_msg) {
-    if (!plink || !out || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
-    if (route_error) { set_error(1, route_error, who); return 1; }
-    if (!general() && (window < 0 || window >= snps)) { set_error(1, "%s: need 0 <= window < snps (window %ld, snps %ld)", who, window, snps); return 1; }
-    if (flag != 0 && flag != 1) { set_error(1, "%s: %s must be 0 or 1", who, scores ? "adjust" : "kind"); return 1; }
-    if (!general() && !scores && ldb < window + 1) { set_error(1, "%s: need ldb >= window + 1 (ldb %ld, window %ld)", who, ldb, window); return 1; }
-    if (scores && flag && indiv < 3) { set_error(1, adj_msg, who); return 1; }
-    if (max_indiv && indiv > max_indiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, max_indiv); return 1; }
-    if (snps >= kXFusedMaxRows) { set_error(1, snps_msg, who, kXFusedMaxRows - 1); return 1; }
-    if (select_device() < 0) return 1;
-    std::vector<long> h_rowptr;
-    std::vector<int> h_last;
-    if (plan(h_rowptr, h_last)) return 1;
-    row_bytes = (indiv + 3) / 4;
-    in_dev = ptr_location(plink, nullptr) == 1;
-    out_dev = ptr_location(out, nullptr) == 1;
-    if (pairs && fill && ((ptr_location(col, nullptr) == 1) != out_dev || (val && (ptr_location(val, nullptr) == 1) != out_dev))) {   // val == nullptr: the library's own "no val" fill
-      set_error(1, "%s: rowptr, col and val must be all host or all device pointers", who);
-      return 1;
-    }
-    // a host band leaves from a compact device copy (leading dimension window + 1); the scores' partial buffer holds 2 (ndiag + 1) slots per SNP
-    plane_bytes = (size_t)g.rows_pad() * g.pitch();
-    obytes = sizeof(double) * (scores ? (size_t)snps : general() ? (size_t)h_rowptr.back() : (size_t)(window + 1) * (size_t)snps);
-    if (pairs) obytes = sizeof(long) * ((size_t)snps + 1) + (sizeof(double) + sizeof(int)) * (size_t)capacity;
-    if (apply) obytes = sizeof(double) * (size_t)snps * (size_t)ncols;   // a host Y leaves from a compact device copy (leading dimension snps)
-    const size_t pbytes = scores ? sizeof(double) * ld_score_slot(2, 0, ndiag, g.rows_pad()) : 0;
-    const size_t wbytes = sizeof(int) * (size_t)g.nb + (general() ? sizeof(int) * (size_t)snps + sizeof(long) * ((size_t)snps + 1) : 0);   // jmax, last, rowptr
-    size_t free_b = 0, total_b = 0;
-    MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t need = planes * plane_bytes + pbytes + wbytes + extra_bytes() + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
-    if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
-    if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
-    s = st.s;
-    if (d_X.alloc(planes * plane_bytes) || d_flag.alloc(sizeof(int)) || (!out_dev && d_out.alloc(obytes)) || (scores && d_P.alloc(pbytes))) return 1;
-    // the plan's arrays: synchronous copies (the host vectors end with this function)
-    if (scores) {
-      if (d_jmax.alloc(sizeof(int) * (size_t)g.nb)) return 1;
-      MXA_HIP(hipMemcpy(d_jmax.p, jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice));
-    }
-    if (general()) {
-      const bool rows = !scores && !pairs && !apply;   // the ragged rows' starts
-      if (d_last.alloc(sizeof(int) * (size_t)snps) || (rows && d_rowptr.alloc(sizeof(long) * ((size_t)snps + 1)))) return 1;
-      MXA_HIP(hipMemcpy(d_last.p, h_last.data(), sizeof(int) * (size_t)snps, hipMemcpyHostToDevice));
-      if (rows) MXA_HIP(hipMemcpy(d_rowptr.p, h_rowptr.data(), sizeof(long) * ((size_t)snps + 1), hipMemcpyHostToDevice));
-    }
-    d_res = out_dev ? out : (double *)d_out.p;
-    ld_res = out_dev ? ldb : window + 1;
-    d_dst = scores ? (double *)d_P.p : d_res;
-    ld_dst = scores ? g.rows_pad() : ld_res;
-    return e0.create() || e1.create();
-  }
-  int start() { MXA_HIP(hipEventRecord(e0.e, s)); return 0; }
-  int finish() {
-    if (scores) hipLaunchKernelGGL(k_ld_score_finish, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, (const double *)d_P.p, snps, g.rows_pad(), (const int *)d_jmax.p, ndiag, d_res);
-    else if (!general() && window > 0) hipLaunchKernelGGL(k_ld_band_tail, dim3((unsigned)window), dim3(256), 0, s, d_res, ld_res, snps, window);
-    MXA_HIP(hipGetLastError());
-    MXA_HIP(hipEventRecord(e1.e, s));
-    if (!out_dev && ld_window_download(d_res, obytes, snps, window, out, ldb, scores || general(), s)) return 1;
-    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
-    MXA_HIP(profile_launch(e0, e1));
-    return 0;
-  }
-  // the applied window: Y is complete on the device (d_res, leading dimension out_dev ? ldb : snps); a host Y takes its snps rows of every column
-  int finish_apply() {
-    MXA_HIP(hipEventRecord(e1.e, s));
-    if (!out_dev) MXA_HIP(hipMemcpy2DAsync(out, sizeof(double) * (size_t)ldb, d_res, sizeof(double) * (size_t)snps, sizeof(double) * (size_t)snps, (size_t)ncols, hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics, scratch and partials
-    MXA_HIP(profile_launch(e0, e1));
-    return 0;
-  }
-  // the CSR result: the total (d_total, the running base after the last group) is read once; a host result is rowptr and the first min(total, capacity)
-  // entries of col / val.  total > capacity: error 25, rowptr and *total valid.
-  int finish_pairs(const long *d_total, long *total) {
-    MXA_HIP(hipEventRecord(e1.e, s));
-    long h_total = 0;
-    MXA_HIP(hipMemcpyAsync(&h_total, d_total, sizeof(long), hipMemcpyDeviceToHost, s));
-    if (!out_dev) MXA_HIP(hipMemcpyAsync(out, d_pairs_rowptr(), sizeof(long) * ((size_t)snps + 1), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));   // lifetime of the route's tile lists, statistics and scratch
-    const size_t filled = (size_t)std::min(h_total, capacity);
-    if (!out_dev && filled) {
-      MXA_HIP(hipMemcpyAsync(val, d_pairs_val(), sizeof(double) * filled, hipMemcpyDeviceToHost, s));
-      MXA_HIP(hipMemcpyAsync(col, d_pairs_col(), sizeof(int) * filled, hipMemcpyDeviceToHost, s));
-      MXA_HIP(hipStreamSynchronize(s));
-    }
-    MXA_HIP(profile_launch(e0, e1));
-    *total = h_total;
-    if (fill && h_total > capacity) { set_error(25, "%s: %ld pairs pass the cutoff, capacity is %ld", who, h_total, capacity); return 1; }
-    return 0;
-  }
-};
-}  // namespace
-
-// the operand of the plain route: staged as it is, the engine, the frequencies on the device and the LD map's statistics (xp.u, xp.w, xp.a)
-namespace {
-struct LdPlainOperand {
-  bool f4 = false;
-  XBuf f_tmp, stats[3];
-  XPost xp;
-  int stage(LdWindow &c, const unsigned char *plink, bool is_plink, const double *freq) {
-    hipStream_t s = c.s;
-    if (stage_operand(plink, c.in_dev, c.row_bytes, is_plink, c.g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, 0, c.indiv)) return 1;   // padding bits are no individuals
-    if (pick_engine((const int *)c.d_flag.p, c.indiv, s, f4)) return 1;
-    const double *d_f = freq;
-    if (ptr_location(freq, nullptr) != 1) {
-      if (f_tmp.alloc(sizeof(double) * (size_t)c.snps)) return 1;
-      MXA_HIP(hipMemcpyAsync(f_tmp.p, freq, sizeof(double) * (size_t)c.snps, hipMemcpyHostToDevice, s));
-      d_f = (const double *)f_tmp.p;
-    }
-    return fused_post_stats(c.g, c.X(), c.indiv, kPostLd, 0, d_f, stats, s, xp);
-  }
-};
-}  // namespace
-
-// the plain route: the operand staged as it is, the LD map's statistics, and one launch of the window's tiles with the window epilogue
-int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
-                         bool is_plink, const double *freq) {
-  LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
-  if (c.begin(1, [] { return (size_t)0; }, freq ? nullptr : "%s: allele frequencies are required", 0, "%s: the adjusted estimator r^2 - (1 - r^2) / (indiv - 2) needs indiv >= 3",
-              "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
-  const XGeom &g = c.g;
-  hipStream_t s = c.s;
-  LdPlainOperand op;
-  if (op.stage(c, plink, is_plink, freq)) return 1;
-  XPost &xp = op.xp;
-  c.set_post(xp);                                         // kind / adjust, the general window's arrays (xprod_store_window)
-  XTiles t;
-  if (upload_tiles({c.tiles()}, s, t)) return 1;
-  if (c.start() || t.launch(0, g, op.f4, s, c.X(), c.d_dst, c.ld_dst, c.post_c0(), nullptr, c.post_kind(), xp)) return 1;
-  return c.finish();
-}
-
-// ---- pairwise-complete windowed LD (mxa_ld_band_pairwise, mxa_ld_scores_pairwise): Pearson's r of SNPs i, j over the individuals genotyped at BOTH.
-// With the planes Z, M, A of k_xstage_planes every ingredient is an exact integer crossproduct of rows:
-//   N = M_i.M_j   Sxy = Z_i.Z_j   Sx = Z_i.M_j   Sy = M_i.Z_j   Sxx = Sx + 2 A_i.M_j   Syy = Sy + 2 M_i.A_j
-//   num = N Sxy - Sx Sy   dx = N Sxx - Sx^2   dy = N Syy - Sy^2   r = num / sqrt(dx dy)
-// Six tile products per band tile (count store into a scratch slot each), then k_ld_pw_combine forms r per element and stores the band / reduces the scores
-// through the epilogue of mxa_ld_band / mxa_ld_scores itself (ld_window_store).  The band runs in groups of tile rows so that the scratch stays bounded.
-// num, dx, dy are formed in fp64 from the int32 counts: every product and difference is an integer below 4 indiv^2 < 2^53 (guarded by the caller), i.e. exact
-// whether or not the compiler contracts them; dx dy, the square root and the quotient are rounded once each.  The expression is symmetric in (i, j) bit for bit.
-constexpr long kPwMaxIndiv = 47453132L;   // 4 indiv^2 < 2^53
-constexpr int kPwPairs = 6;
-// the operand planes (A side from the I rows, B side from the J rows) of the six products, in slot order: N, Sxy, Sx, Sy, A_i.M_j, M_i.A_j
-__host__ __device__ constexpr int pw_plane_a(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? 0 : k == 3 ? 1 : k == 4 ? 2 : 1; }
-__host__ __device__ constexpr int pw_plane_b(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? 1 : k == 3 ? 0 : k == 4 ? 1 : 2; }
-
-__device__ __forceinline__ double pw_r(double N, double Sxy, double Sx, double Sy, double Ax, double Ay) {
-  const double Sxx = Sx + 2.0 * Ax, Syy = Sy + 2.0 * Ay;
-  const double num = N * Sxy - Sx * Sy, dx = N * Sxx - Sx * Sx, dy = N * Syy - Sy * Sy;   // exact integers
-  return __ddiv_rn(num, __dsqrt_rn(__dmul_rn(dx, dy)));                                    // dx dy = 0 (no shared individuals, or a SNP constant on them): 0 / 0 = NaN
-}
-// !SCORES: the stored entry r (ld_window_store squares it for kind 1); SCORES: the score term t(r) with the pair's own N, every operation rounded on its own
-template <bool SCORES>
-__device__ __forceinline__ double pw_value(double N, double Sxy, double Sx, double Sy, double Ax, double Ay, bool adjust) {
-  const double r = pw_r(N, Sxy, Sx, Sy, Ax, Ay);
-  if constexpr (!SCORES) return r;
-  const double r2 = __dmul_rn(r, r);
-  return adjust ? __dsub_rn(r2, __ddiv_rn(__dsub_rn(1.0, r2), __dsub_rn(N, 2.0))) : r2;
-}
-
-// One workgroup per band tile, the lane <-> element map of the crossproduct epilogue: thread t reads quad q of its sub-block (a, b) at slot + ((4 a + b) 4 + q) 1024 + 4 t,
-// where xprod_store_counts wrote it.  DENSE: the six counts of the tile's slots t.w .. t.w + 5.  !DENSE (no missing code in the whole matrix): slot t.w holds
-// Sxy only; M is all ones, so N = indiv and the other four are the per-SNP sums sz = sum z, sa = sum a (k_pw_rowsums) -- the same integers, hence the same bits.
-// Win: the window object, by value (LdFixedWindow: the band or its scores; LdVarWindow: ragged rows or their scores).
-template <bool SCORES, bool DENSE, typename Win>
-__global__ void __launch_bounds__(256) k_ld_pw_combine(const int *__restrict__ scratch, const int4 *__restrict__ btiles, const int *__restrict__ sz, const int *__restrict__ sa,
-                                                       long n, double indiv, double *__restrict__ out, long ld, Win win, int flag) {
-  __shared__ __attribute__((aligned(16))) char smem[kXScratchBytes + (SCORES ? 2 * 4 * 2 * 4 * 32 * 8 : 0)];
-  const int4 t = btiles[blockIdx.x];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wi = wave >> 1, wj = wave & 1;
-  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
-  const int4 *base = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + threadIdx.x;
-  constexpr size_t kSlotQuads = kPwSlotInts / 4;
-  const int col = lane & 31, rq = 4 * (lane >> 5);
-  const bool adjust = flag != 0;
-  int cnt[DENSE ? kPwPairs : 1][16];                         // the counts of the current sub-block, in accumulator register order
-  long gi_base = 0, gj = 0;
-  auto prep = [&](int a, int b) {
-    gi_base = i0 + wi * 128 + a * 32; gj = j0 + wj * 128 + b * 32 + col;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int4 *p = base + ((a * 4 + b) * 4 + q) * 256;
-#pragma unroll
-      for (int k = 0; k < (DENSE ? kPwPairs : 1); k++) {
-        const int4 w = p[(size_t)k * kSlotQuads];
-        cnt[k][4 * q] = w.x; cnt[k][4 * q + 1] = w.y; cnt[k][4 * q + 2] = w.z; cnt[k][4 * q + 3] = w.w;
-      }
-    }
-  };
-  auto val = [&](int, int, int r) -> double {
-    if constexpr (DENSE) return pw_value<SCORES>((double)cnt[0][r], (double)cnt[1][r], (double)cnt[2][r], (double)cnt[3][r], (double)cnt[4][r], (double)cnt[5][r], adjust);
-    else {
-      const long gi = gi_base + (r & 3) + 8 * (r >> 2) + rq;     // row of accumulator register r
-      return pw_value<SCORES>(indiv, (double)cnt[0][r], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj], adjust);
-    }
-  };
-  ld_window_store<SCORES>(win, prep, val, [](double v, long, long) { return v; }, !SCORES && flag != 0, smem, wave, lane, wi, wj, i0, j0, n, out, ld);
-}
-
-// per SNP row: sz = sum z (plane Z), sa = sum a (plane A) of the stacked operand, for the missing-free path.  Grid (row tiles, K chunks), thread = row of the tile
-// reading its 32-byte piece of every slab of the chunk (as k_x_rowstats); int32 atomics across the chunks (integer addition: order-independent).
-__global__ void __launch_bounds__(256) k_pw_rowsums(const uint8_t *__restrict__ X, long nslabs, long slabs_per_chunk, long nb, int *__restrict__ sz, int *__restrict__ sa) {
-  const long rt = blockIdx.x;
-  const long s0 = (long)blockIdx.y * slabs_per_chunk, s1 = min(nslabs, s0 + slabs_per_chunk);
-  int z = 0, a = 0;
-  for (long sl = s0; sl < s1; sl++) {
-    const uint4 *pz = reinterpret_cast<const uint4 *>(X + ((size_t)rt * nslabs + (size_t)sl) * kTileBytes + (size_t)threadIdx.x * kSlabBytes);
-    const uint4 *pa = reinterpret_cast<const uint4 *>(X + ((size_t)(2 * nb + rt) * nslabs + (size_t)sl) * kTileBytes + (size_t)threadIdx.x * kSlabBytes);
-    const uint4 z0 = pz[0], z1 = pz[1], a0 = pa[0], a1 = pa[1];
-    const uint32_t wz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w}, wa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-      z += __popc(wz[d] & 0x55555555u) + 2 * __popc(wz[d] & 0xAAAAAAAAu);
-      a += __popc(wa[d]);
-    }
-  }
-  const long r = rt * kTileRows + threadIdx.x;
-  if (z) atomicAdd(sz + r, z);
-  if (a) atomicAdd(sa + r, a);
-}
-
-// The plan of one group of window tile rows [i_lo, i_hi): per window tile (i, j <= jmax[i]) one entry of `band` (i, j, 1, first slot) and `pairs` entries of `prod`
-// over the stacked operand (plane_a nb + i, plane_b nb + j, 1, slot); slots are numbered from 0 within the group.  (miraculix_amd.crossproduct.ld_pairwise_tiles restates it.)
-static void pairwise_group_tiles(int nb, const std::vector<int> &jmax, int i_lo, int i_hi, int pairs, std::vector<int4> &prod, std::vector<int4> &band) {
-  int slot = 0;
-  for (int i = i_lo; i < i_hi; i++)
-    for (int j = i; j <= jmax[(size_t)i]; j++) {
-      band.push_back(make_int4(i, j, 1, slot));
-      // pairs == 1: the (Z, Z) product alone
-      for (int k = 0; k < pairs; k++) prod.push_back(pairs == 1 ? make_int4(i, j, 1, slot) : make_int4(pw_plane_a(k) * nb + i, pw_plane_b(k) * nb + j, 1, slot + k));
-      slot += pairs;
-    }
-}
-
-// The groups of a window whose tile products go through the count scratch (the pairwise-complete entries: pairs = 6 or 1; the CSR entries of the plain route:
-// pairs = 1): consecutive tile rows whose `pairs` slots of 256 KiB per window tile stay under `cap` bytes.  Fixed window: equally many rows each, sized by
-// the longest tile row; general window (tile rows of different lengths): as many rows as keep the group's own tiles under the cap.  One tile row at least
-// either way; the results do not depend on the groups.  Group q: tile rows [row0[q], row0[q + 1]), products prod[q], window tiles band[band_first[q] ..).
-namespace {
-constexpr size_t kPwSlotBytes = kPwSlotInts * sizeof(int);
-static size_t ld_scratch_cap() {   // MXA_LD_PAIRWISE_SCRATCH_MB, read per call
-  const char *e_cap = getenv("MXA_LD_PAIRWISE_SCRATCH_MB");
-  return (size_t)(e_cap && atol(e_cap) > 0 ? atol(e_cap) : 2048L) << 20;
-}
-struct LdGroups {
-  std::vector<int> row0;
-  int n = 0;
-  std::vector<std::vector<int4>> prod;
-  std::vector<int4> band;
-  std::vector<size_t> band_first;
-  size_t tiles_max = 0;
-  // tile_extra: bytes a window tile holds next to its count slots under the same cap (the partials of the apply entries)
-  LdGroups(const LdWindow &c, size_t cap, int pairs, size_t tile_extra = 0) : row0{0} {
-    const XGeom &g = c.g;
-    const size_t tile_bytes = (size_t)pairs * kPwSlotBytes + tile_extra;
-    if (!c.general()) {
-      const int rows_per_group = (int)std::max<size_t>(1, std::min<size_t>((size_t)g.nb, cap / (c.row_tiles_max * tile_bytes)));
-      for (int i = rows_per_group; i < g.nb; i += rows_per_group) row0.push_back(i);
-    } else {
-      const size_t cap_tiles = cap / tile_bytes;
-      size_t held = 0;
-      for (int i = 0; i < g.nb; i++) {
-        const size_t t = (size_t)(c.jmax[(size_t)i] - i + 1);
-        if (held && held + t > cap_tiles) { row0.push_back(i); held = 0; }
-        held += t;
-      }
-    }
-    n = (int)row0.size();
-    row0.push_back(g.nb);
-    prod.resize((size_t)n);
-    band_first.assign((size_t)n + 1, 0);
-    for (int q = 0; q < n; q++) {
-      band_first[(size_t)q] = band.size();
-      pairwise_group_tiles(g.nb, c.jmax, row0[(size_t)q], row0[(size_t)q + 1], pairs, prod[(size_t)q], band);
-      tiles_max = std::max(tiles_max, band.size() - band_first[(size_t)q]);
-    }
-    band_first.back() = band.size();
-  }
-};
-// the operand of the pairwise route: the three planes staged, the engine, and -- no missing code anywhere -- the per-SNP sums that replace five products
-struct LdPairwiseOperand {
-  bool f4 = false, dense = true;
-  int pairs = kPwPairs;
-  XBuf d_sums;
-  int *d_sz = nullptr, *d_sa = nullptr;
-  int stage(LdWindow &c, const unsigned char *plink) {
-    const XGeom &g = c.g;
-    hipStream_t s = c.s;
-    const char *e_dense = getenv("MXA_LD_PAIRWISE_DENSE");
-    if (stage_operand(plink, c.in_dev, c.row_bytes, true, g, (uint8_t *)c.d_X.p, (int *)c.d_flag.p, c.bounce, s, c.indiv)) return 1;
-    int has_missing = 1;
-    MXA_HIP(hipMemcpyAsync(&has_missing, c.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    // no plane holds a 3: the FP4 engine is exact while 4 indiv < 2^24 (pick_engine's rule); MXA_XPROD_ENGINE=i8 forces int8
-    f4 = 4 * c.indiv < (1L << 24);
-    if (const char *e = getenv("MXA_XPROD_ENGINE")) { if (!strcmp(e, "i8")) f4 = false; }
-    // no missing code anywhere: the (Z, Z) product alone, the rest from per-SNP sums (MXA_LD_PAIRWISE_DENSE=1 keeps the six products; bit-identical)
-    dense = has_missing || (e_dense && atoi(e_dense) != 0);
-    pairs = dense ? kPwPairs : 1;
-    if (!dense) {
-      if (d_sums.alloc(sizeof(int) * 2 * (size_t)g.rows_pad())) return 1;
-      d_sz = (int *)d_sums.p; d_sa = d_sz + g.rows_pad();
-      MXA_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int) * 2 * (size_t)g.rows_pad(), s));
-      long spc = 0;
-      const dim3 g_rows = rowstats_grid(g, &spc);
-      hipLaunchKernelGGL(k_pw_rowsums, g_rows, dim3(256), 0, s, c.X(), g.nslabs, spc, (long)g.nb, d_sz, d_sa);
-      MXA_HIP(hipGetLastError());
-    }
-    return 0;
-  }
-};
-}  // namespace
-
-// the pairwise route: the three planes staged, per group of tile rows the count products and their combine
-int ld_pairwise_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag) {
-  // the scratch of a group: `pairs` slots of 256 KiB per band tile, tile rows per group so that it stays under the cap (one tile row at least); read per call
-  const size_t cap = ld_scratch_cap();
-  const size_t slot_bytes = kPwSlotBytes;
-  LdWindow c(who, plink, snps, indiv, window, last, out, ldb, scores, flag);
-  // (the scratch is counted at its cap -- or at the one tile row of six products it cannot go below -- unless the whole window needs less)
-  if (c.begin(3, [&] { return std::min(std::max(cap, c.row_tiles_max * kPwPairs * slot_bytes), c.ntiles * kPwPairs * slot_bytes); }, nullptr, kPwMaxIndiv,
-              "%s: the adjusted estimator r^2 - (1 - r^2) / (N - 2) needs indiv >= 3", "%s: at most %ld SNPs per call")) return 1;
-  const XGeom &g = c.g;
-  hipStream_t s = c.s;
-  XBuf d_scr, d_bt;
-  LdPairwiseOperand op;
-  if (op.stage(c, plink)) return 1;
-  const bool f4 = op.f4, dense = op.dense;
-  const int pairs = op.pairs;
-  int *d_sz = op.d_sz, *d_sa = op.d_sa;
-  LdGroups gr(c, cap, pairs);
-  const int ngroups = gr.n;
-  const std::vector<int> &group_row0 = gr.row0;
-  const std::vector<size_t> &band_first = gr.band_first;
-  XTiles t;
-  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
-  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * slot_bytes)) return 1;
-  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  if (c.start()) return 1;
-  const XPost none{};
-  for (int q = 0; q < ngroups; q++) {
-    // the products of the group into the scratch, then its combine, one behind the other on the call's stream (the next group reuses the scratch)
-    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
-    const dim3 grid((unsigned)(band_first[(size_t)q + 1] - band_first[(size_t)q]));
-    const int4 *bt = (const int4 *)d_bt.p + band_first[(size_t)q];
-    // the instantiation for (scores, dense, window object)
-    auto combine = [&](auto win) {
-      using Win = decltype(win);
-      auto go = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const int *)d_scr.p, bt, (const int *)d_sz, (const int *)d_sa, snps, (double)indiv, c.d_dst, c.ld_dst, win, flag); };
-      if (scores) { if (dense) go(k_ld_pw_combine<true, true, Win>); else go(k_ld_pw_combine<true, false, Win>); }
-      else { if (dense) go(k_ld_pw_combine<false, true, Win>); else go(k_ld_pw_combine<false, false, Win>); }
-    };
-    if (c.general()) combine(LdVarWindow{(const int *)c.d_last.p, (const long *)c.d_rowptr.p, c.ndiag});
-    else combine(LdFixedWindow{window});
-    MXA_HIP(hipGetLastError());
-  }
-  if (c.finish()) return 1;
-  debug_info("%s: %d group(s) of up to %d tile rows, %d product(s) per band tile (%s), %s engine", who, ngroups, group_row0[1], pairs, dense ? "six counts" : "no missing code: per-SNP sums",
-             f4 ? "FP4" : "int8");
-  return 0;
-}
-
-// ---- pairs above a cutoff as CSR (mxa_ld_window_pairs, mxa_ld_window_pairs_pairwise): the candidates i < j <= last[i] whose q = fl(r r) >= min_r2, compacted
-// on the device.  Both routes run the window's tile products once into the count scratch (kPostCounts; the plain route one slot per window tile), in the
-// groups of LdGroups; per group k_ld_select counts (WRITE = false), the scan kernels turn the counts into positions, and k_ld_select runs again and writes
-// (WRITE = true), recomputing its masks from the scratch, which is still in place.  Every position is a sum of counts in a fixed order: no atomics.
-// The providers: r of one element from the counts of its sub-block (cnt[slot][register], the lane <-> element map of k_ld_pw_combine), bit for bit what the
-// rows entries store at kind 0 -- the plain map of xprod_store_window's fin, or pw_r as k_ld_pw_combine calls it.
-struct LdPairsPlain {
-  static constexpr int kSlots = 1;
-  const double *__restrict__ u, *__restrict__ w;
-  double a;
-  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long gi, long gj) const {
-    return ld_scale_map(ld_center_map((double)cnt[0][reg], u[gj], u[gi], a), w[gj], w[gi]);
-  }
-};
-struct LdPairsCounts {
-  static constexpr int kSlots = kPwPairs;
-  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long, long) const {
-    return pw_r((double)cnt[0][reg], (double)cnt[1][reg], (double)cnt[2][reg], (double)cnt[3][reg], (double)cnt[4][reg], (double)cnt[5][reg]);
-  }
-};
-struct LdPairsSums {
-  static constexpr int kSlots = 1;
-  const int *__restrict__ sz, *__restrict__ sa;
-  double indiv;
-  __device__ __forceinline__ double r(const int (&cnt)[kSlots][16], int reg, long gi, long gj) const {
-    return pw_r(indiv, (double)cnt[0][reg], (double)sz[gi], (double)sz[gj], (double)sa[gi], (double)sa[gj]);
-  }
-};
-// The one decision of both passes: q = fl(r r), kept iff q >= min_r2 (a NaN r: the comparison is false).  Nothing here can be contracted.
-__device__ __forceinline__ bool ld_pair_keep(double r, double min_r2, double &q) {
-  q = __dmul_rn(r, r);
-  return q >= min_r2;
-}
-
-// One workgroup per window tile.  Element (gi, gj) of the tile is held by the lane the crossproduct epilogue gives it: lane & 31 runs along gj, the two 32-lane
-// halves of a wave hold rows 4 apart, so a ballot is two 32-bit words of the table mask[row][word], word = the row's 32-column sub-block, ascending in gj.
-// Count pass: cnt[tile][row] = the row's popcount.  Write pass: cnt holds rel[tile][row], the row's kept pairs in the tiles to the left (k_ld_pairs_rowscan);
-// position = rowptr[gi] + rel + popcounts of the row's lower words + of its own word below the lane; a position >= capacity is dropped.
-// val == nullptr (the selection entries, which need the graph alone): the write pass still rebuilds its masks from the counts in the first loop, as ever; its
-// second loop stores col only and skips the reload of the counts and the second evaluation of r.
-template <bool WRITE, typename Prov, typename Win>
-__global__ void __launch_bounds__(256) k_ld_select(const int *__restrict__ scratch, const int4 *__restrict__ btiles, long n, Prov prov, Win win, double min_r2, int kind,
-                                                   int *__restrict__ cnt, const long *__restrict__ rowptr, int *__restrict__ col, double *__restrict__ val, long capacity) {
-  __shared__ unsigned mask[kXT][8];
-  __shared__ int below[WRITE ? kXT : 1][8];                  // kept pairs of the row in its lower words
-  __shared__ long base[WRITE ? kXT : 1];                     // rowptr[gi] + rel
-  const int4 t = btiles[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
-  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
-  const int4 *slot = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + tid;
-  constexpr size_t kSlotQuads = kPwSlotInts / 4;
-  const int c = lane & 31, hh = lane >> 5;
-  int counts[Prov::kSlots][16];                              // the counts of the current sub-block, in accumulator register order
-  auto load = [&](int a, int b) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int4 *p = slot + ((a * 4 + b) * 4 + q) * 256;
-#pragma unroll
-      for (int k = 0; k < Prov::kSlots; k++) {
-        const int4 w = p[(size_t)k * kSlotQuads];
-        counts[k][4 * q] = w.x; counts[k][4 * q + 1] = w.y; counts[k][4 * q + 2] = w.z; counts[k][4 * q + 3] = w.w;
-      }
-    }
-  };
-#pragma unroll
-  for (int k = 0; k < 8; k++) mask[tid][k] = 0u;             // sub-blocks skipped below keep no pair
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-      if (gj_base + 31 <= gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: no element above the diagonal, or none within the window
-      load(a, b);
-      const long gj = gj_base + c;
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        const long gi = gi_base + row;
-        bool keep = false;
-        if (gi < gj && gj < n && win.in(gi, gj)) {
-          double q;
-          keep = ld_pair_keep(prov.r(counts, reg, gi, gj), min_r2, q);
-        }
-        const unsigned long long bal = __ballot(keep);
-        if (c == 0) mask[wi * 128 + a * 32 + row][wj * 4 + b] = (unsigned)(bal >> (32 * hh));
-      }
-    }
-  __syncthreads();
-  int *mine = cnt + (size_t)blockIdx.x * kXT + tid;
-  if constexpr (!WRITE) {
-    int total = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) total += __popc(mask[tid][k]);
-    *mine = total;
-  } else {
-    int run = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { below[tid][k] = run; run += __popc(mask[tid][k]); }
-    base[tid] = i0 + tid < n ? rowptr[i0 + tid] + (long)*mine : 0L;
-    const bool want_val = val != nullptr;
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-        if (gj_base + 31 <= gi_base || win.beyond(gi_base, gj_base, n)) continue;
-        if (want_val) load(a, b);
-        const long gj = gj_base + c;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-          const int row = wi * 128 + a * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh, word = wj * 4 + b;
-          const unsigned m = mask[row][word];
-          if ((m >> c) & 1u) {                               // kept by the decision above: gi < gj < n
-            const long pos = base[row] + (long)(below[row][word] + __popc(m & ((1u << c) - 1u)));
-            if (pos < capacity) {
-              col[pos] = (int)gj;
-              if (want_val) {
-                double q;
-                const double r = prov.r(counts, reg, i0 + row, gj);
-                ld_pair_keep(r, min_r2, q);
-                val[pos] = kind ? q : r;
-              }
-            }
-          }
-        }
-      }
-  }
-}
-
-// Between the two passes of a group: one workgroup per tile row I = i_lo + blockIdx.x of the group, thread = row.  cnt over the row's tiles (J ascending,
-// tfirst[I] = the window tiles in front of tile row I) becomes the exclusive offsets rel; the row totals are scanned within the tile row (rowptr[gi] = the
-// offset inside the tile row for now) and the tile row's total goes to rowsum[blockIdx.x].
-__global__ void __launch_bounds__(256) k_ld_pairs_rowscan(int *__restrict__ cnt, const long *__restrict__ tfirst, int i_lo, long n, long *__restrict__ rowptr,
-                                                          long *__restrict__ rowsum) {
-  __shared__ long sc[kXT];
-  const int tid = threadIdx.x, I = i_lo + (int)blockIdx.x;
-  const long t0 = tfirst[I] - tfirst[i_lo], t1 = tfirst[I + 1] - tfirst[i_lo];
-  int run = 0;                                               // < n: fits an int
-  for (long t = t0; t < t1; t++) {
-    int *p = cnt + (size_t)t * kXT + tid;
-    const int v = *p;
-    *p = run;
-    run += v;
-  }
-  sc[tid] = run;
-  __syncthreads();
-  for (int off = 1; off < kXT; off <<= 1) {
-    const long v = tid >= off ? sc[tid - off] : 0L;
-    __syncthreads();
-    sc[tid] += v;
-    __syncthreads();
-  }
-  const long gi = (long)I * kXT + tid;
-  if (gi < n) rowptr[gi] = sc[tid] - run;
-  if (tid == kXT - 1) rowsum[blockIdx.x] = sc[tid];
-}
-// One workgroup: rowsum[0 .. nrows) of the group's tile rows -> their exclusive prefix sums from the running base *base (the pairs of all earlier groups), and
-// *base moves on by the group's total.  Thread t sums a run of consecutive tile rows, the runs are scanned through the LDS.
-__global__ void __launch_bounds__(1024) k_ld_pairs_groupscan(long *__restrict__ rowsum, int nrows, long *__restrict__ base) {
-  __shared__ long sc[1024];
-  const int tid = threadIdx.x, per = (nrows + 1023) / 1024, r0 = min(nrows, tid * per), r1 = min(nrows, r0 + per);
-  const long start = *base;
-  long run = 0;
-  for (int r = r0; r < r1; r++) run += rowsum[r];
-  sc[tid] = run;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const long v = tid >= off ? sc[tid - off] : 0L;
-    __syncthreads();
-    sc[tid] += v;
-    __syncthreads();
-  }
-  long at = start + sc[tid] - run;
-  for (int r = r0; r < r1; r++) { const long v = rowsum[r]; rowsum[r] = at; at += v; }
-  if (tid == 1023) *base = start + sc[tid];
-}
-// rowptr[gi] of the group's rows: the offset inside the tile row plus the tile row's start; behind the last group rowptr[n] = the total
-__global__ void __launch_bounds__(256) k_ld_pairs_rowptr(long *__restrict__ rowptr, const long *__restrict__ rowstart, int i_lo, long n, const long *__restrict__ base, int is_last) {
-  const long gi = ((long)i_lo + blockIdx.x) * kXT + threadIdx.x;
-  if (gi < n) rowptr[gi] += rowstart[blockIdx.x];
-  if (is_last && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) rowptr[n] = *base;
-}
-
-// both routes of the CSR entries (pairwise: the pairwise-complete r; else the plain route with is_plink and freq).  no_val: the library's own filling call
-// with col alone (ld_prune_window); the public entries pass false and reject a lone NULL as ever.
-static int ld_pairs_any(const char *who, const unsigned char *plink, long snps, long indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
-                        long capacity, long *total, bool pairwise, bool is_plink, const double *freq, bool no_val = false) {
-  if (!last || !rowptr || !total) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (!no_val && (col == nullptr) != (val == nullptr)) { set_error(1, "%s: col and val must both be given (the filling call) or both be NULL (the count-only call)", who); return 1; }
-  if (col && capacity < 0) { set_error(1, "%s: capacity must not be negative (%ld)", who, capacity); return 1; }
-  if (!(min_r2 >= 0.0) || min_r2 > DBL_MAX) { set_error(1, "%s: min_r2 must be finite and not negative", who); return 1; }
-  const size_t cap = ld_scratch_cap();
-  LdWindow c(who, plink, snps, indiv, 0, last, reinterpret_cast<double *>(rowptr), 0, false, kind);
-  c.set_pairs(col, val, capacity);
-  const int pairs_max = pairwise ? kPwPairs : 1;
-  // the scratch as ld_pairwise_any counts it, the per-(tile, row) counters of a group (1 KiB per window tile), and per tile row tfirst and the row sums
-  auto extra = [&] {
-    const size_t scr = std::min(std::max(cap, c.row_tiles_max * pairs_max * kPwSlotBytes), c.ntiles * pairs_max * kPwSlotBytes);
-    return scr + std::min(c.ntiles, std::max(cap / kPwSlotBytes, c.row_tiles_max)) * kXT * sizeof(int) + sizeof(long) * (2 * (size_t)c.g.nb + 2);
-  };
-  if (c.begin(pairwise ? 3 : 1, extra, pairwise || freq ? nullptr : "%s: allele frequencies are required", pairwise ? kPwMaxIndiv : 0L, "%s",
-              pairwise ? "%s: at most %ld SNPs per call" : "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
-  const XGeom &g = c.g;
-  hipStream_t s = c.s;
-  LdPlainOperand plain;
-  LdPairwiseOperand pw;
-  if (pairwise ? pw.stage(c, plink) : plain.stage(c, plink, is_plink, freq)) return 1;
-  const bool f4 = pairwise ? pw.f4 : plain.f4;
-  const int pairs = pairwise ? pw.pairs : 1;
-  LdGroups gr(c, cap, pairs);
-  std::vector<long> tfirst((size_t)g.nb + 1, 0);
-  for (int I = 0; I < g.nb; I++) tfirst[(size_t)I + 1] = tfirst[(size_t)I] + (c.jmax[(size_t)I] - I + 1);
-  XTiles t;
-  XBuf d_scr, d_bt, d_cnt, d_rows;                           // d_rows: tfirst (nb + 1 longs), the groups' row sums (nb), the running base (1)
-  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
-  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * kPwSlotBytes) || d_cnt.alloc(gr.tiles_max * kXT * sizeof(int)) ||
-      d_rows.alloc(sizeof(long) * (2 * (size_t)g.nb + 2))) return 1;
-  long *d_tfirst = (long *)d_rows.p, *d_rowsum = d_tfirst + g.nb + 1, *d_base = d_rowsum + g.nb;
-  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  MXA_HIP(hipMemcpyAsync(d_tfirst, tfirst.data(), sizeof(long) * tfirst.size(), hipMemcpyHostToDevice, s));
-  MXA_HIP(hipMemsetAsync(d_base, 0, sizeof(long), s));
-  if (c.start()) return 1;
-  const XPost none{};
-  const LdVarWindow win{(const int *)c.d_last.p, nullptr, c.ndiag};
-  long *d_rowptr = c.d_pairs_rowptr();
-  for (int q = 0; q < gr.n; q++) {
-    // the group's products into the scratch; count; scan (the running base crosses the groups on the device: the host does not wait); write
-    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
-    const dim3 grid((unsigned)(gr.band_first[(size_t)q + 1] - gr.band_first[(size_t)q]));
-    const int4 *bt = (const int4 *)d_bt.p + gr.band_first[(size_t)q];
-    const int i_lo = gr.row0[(size_t)q], nrows = gr.row0[(size_t)q + 1] - i_lo;
-    auto select = [&](auto write, auto prov) {
-      hipLaunchKernelGGL((k_ld_select<decltype(write)::value, decltype(prov), LdVarWindow>), grid, dim3(256), 0, s, (const int *)d_scr.p, bt, snps, prov, win, min_r2, kind,
-                         (int *)d_cnt.p, (const long *)d_rowptr, c.d_pairs_col(), c.d_pairs_val(), c.capacity);
-    };
-    auto pass = [&](auto write) {
-      if (!pairwise) select(write, LdPairsPlain{plain.xp.u, plain.xp.w, plain.xp.a});
-      else if (pw.dense) select(write, LdPairsCounts{});
-      else select(write, LdPairsSums{pw.d_sz, pw.d_sa, (double)indiv});
-    };
-    pass(std::false_type());
-    hipLaunchKernelGGL(k_ld_pairs_rowscan, dim3((unsigned)nrows), dim3(256), 0, s, (int *)d_cnt.p, (const long *)d_tfirst, i_lo, snps, d_rowptr, d_rowsum);
-    hipLaunchKernelGGL(k_ld_pairs_groupscan, dim3(1), dim3(1024), 0, s, d_rowsum, nrows, d_base);
-    hipLaunchKernelGGL(k_ld_pairs_rowptr, dim3((unsigned)nrows), dim3(256), 0, s, d_rowptr, (const long *)d_rowsum, i_lo, snps, (const long *)d_base, q == gr.n - 1 ? 1 : 0);
-    if (c.fill) pass(std::true_type());
-    MXA_HIP(hipGetLastError());
-  }
-  if (c.finish_pairs(d_base, total)) return 1;
-  debug_info("%s: %d group(s), %d product(s) per window tile, %s engine, %ld pairs", who, gr.n, pairs, f4 ? "FP4" : "int8", *total);
-  return 0;
-}
-
-// ---- the window applied to a matrix (mxa_ld_window_apply, mxa_ld_window_apply_pairwise): Y = T_w(R) X, Y[i, c] = sum over first[i] <= j <= last[i] of
-// t(r_ij) X[j, c], X and Y snps x n column-major.  Neither the rows nor the band are written: both routes run the window's tile products once into the count
-// scratch (kPostCounts, the groups of LdGroups, as the CSR entries do), k_ld_apply_tile turns every window tile into two partials per chunk of kLdApplyNC
-// columns -- the I side P_I[i][c] = sum_j t_ij X[j, c] over the tile's elements i <= j, the J side P_J[j][c] = sum_i t_ij X[i, c] over its elements i < j --
-// and k_ld_apply_finish adds the partials of a group to Y in the canonical order of a row block B: the J sides of the tiles (I, B), I ascending, then the I
-// sides of the tiles (B, J), J ascending.  Groups are consecutive tile rows and the running sum passes through Y between them, so the association of every
-// sum is the same for every group partition; inside a tile the order is fixed by the lane <-> element map alone and every column runs the same
-// instructions, so it does not depend on the engine, on where the pointers live, on the scratch size or on n.  No floating-point atomics.
-// t: term 0 = r, the providers' value (bit for bit what the rows entries store at kind 0); 1 = fl(r r); 2 = the adjusted term of the scores entries -- the
-// plain route r2 - (1 - r2) (1 / (indiv - 2)) as xprod_store_window forms it, the pairwise route with the pair's own N as pw_value<true> does.
-constexpr int kLdApplyNC = 16;                                          // columns of X per workgroup
-constexpr int kLdApplyXBytes = 2 * kXT * kLdApplyNC * 8;                // xs[side][row][NC]: the X rows of tile rows I and J; afterwards the two halves of a side's partial
-constexpr int kLdApplyLds = kLdApplyXBytes + kXScratchBytes + 4 * 32 * 4;   // + the four waves' 32 x 33 sub-block of t and their 32 row masks: 99 840 bytes
-constexpr long kLdApplyMaxCols = 65535L * kLdApplyNC;                   // grid.y
-
-template <typename Prov>
-__device__ __forceinline__ double ld_apply_term(const Prov &prov, const int (&cnt)[Prov::kSlots][16], int reg, long gi, long gj, int term, double inv_adj) {
-  // Every operation below is rounded on its own.  They are written as operators under this pragma and not as __dmul_rn / __dsub_rn: those are plain operators
-  // inside the toolchain's header, compiled there with contraction allowed, and once inlined the compiler fuses r r - p or r2 - q g into an fma all the same.
-#pragma clang fp contract(off)
-  const double r = prov.r(cnt, reg, gi, gj);
-  if (term == 0) return r;
-  const double r2 = r * r;
-  if (term == 1) return r2;
-  const double q = 1.0 - r2;
-  if constexpr (__is_same(Prov, LdPairsPlain)) {
-    const double p = q * inv_adj;
-    return r2 - p;
-  } else {
-    double N;
-    if constexpr (__is_same(Prov, LdPairsCounts)) N = (double)cnt[0][reg]; else N = prov.indiv;
-    const double p = q / (N - 2.0);
-    return r2 - p;
-  }
-}
-
-// Grid (window tiles of the group, column chunks).  The counts are read with the lane <-> element map of k_ld_select; a wave takes its 128 x 128 quadrant
-// sub-block by sub-block: t of the 32 x 32 sub-block goes to the wave's padded LDS scratch (0 outside the window) and the row masks of the ballot say which
-// elements count -- an element outside the window is skipped, not multiplied.  Then lane (c = lane & 31, hh = lane >> 5) owns the 8 columns 8 hh .. 8 hh + 7
-// of the chunk: for the J side it is column gj_base + c and walks the 32 rows of the sub-block (X[gi, .] an LDS broadcast), for the I side it is row
-// gi_base + c and walks the 32 columns (t read transposed, stride 33).  A lane's sum runs over rows / columns ascending within a sub-block and over the
-// sub-blocks a (b) ascending; the two waves that share rows (columns) are added as wj = 0 + wj = 1 (wi = 0 + wi = 1) through the LDS.
-template <typename Prov, typename Win>
-__global__ void __launch_bounds__(256) k_ld_apply_tile(const int *__restrict__ scratch, const int4 *__restrict__ btiles, long n, Prov prov, Win win, int term,
-                                                       const double *__restrict__ X, long ldx, int ncols, double *__restrict__ P) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NC = kLdApplyNC;
-  const int4 t = btiles[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave >> 1, wj = wave & 1;
-  const int c = lane & 31, hh = lane >> 5, kh = 8 * hh;
-  const long i0 = (long)t.x * kXT, j0 = (long)t.y * kXT;
-  const int c0 = (int)blockIdx.y * NC;
-  double *xs = reinterpret_cast<double *>(smem);
-  double *tsc = reinterpret_cast<double *>(smem + kLdApplyXBytes) + wave * (32 * 33);
-  unsigned *rmask = reinterpret_cast<unsigned *>(smem + kLdApplyXBytes + kXScratchBytes) + wave * 32;
-  double inv_adj = 0.0;
-  if constexpr (__is_same(Prov, LdPairsPlain)) inv_adj = term == 2 ? 1.0 / (prov.a * 0.25 - 2.0) : 0.0;   // prov.a = 4 indiv
-  for (int e = tid; e < 2 * kXT * NC; e += 256) {           // e = (side NC + k) 256 + row: the threads run along the rows of a column of X
-    const int row = e & (kXT - 1), k = (e >> 8) % NC, side = e / (kXT * NC);
-    const long g = (side ? j0 : i0) + row;
-    xs[(side * kXT + row) * NC + k] = g < n && c0 + k < ncols ? X[(size_t)g + (size_t)(c0 + k) * (size_t)ldx] : 0.0;
-  }
-  __syncthreads();
-  const int4 *slot = reinterpret_cast<const int4 *>(scratch + (size_t)t.w * kPwSlotInts) + tid;
-  constexpr size_t kSlotQuads = kPwSlotInts / 4;
-  int counts[Prov::kSlots][16];                              // the counts of the current sub-block, in accumulator register order
-  double rowacc[4][8], colacc[4][8];
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-#pragma unroll
-    for (int k = 0; k < 8; k++) rowacc[q][k] = colacc[q][k] = 0.0;
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      const long gi_base = i0 + wi * 128 + a * 32, gj_base = j0 + wj * 128 + b * 32;
-      if (gj_base + 31 < gi_base || win.beyond(gi_base, gj_base, n)) continue;   // wave-uniform: wholly below the diagonal, or no element within the window
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int4 *p = slot + ((a * 4 + b) * 4 + q) * 256;
-#pragma unroll
-        for (int k = 0; k < Prov::kSlots; k++) {
-          const int4 w = p[(size_t)k * kSlotQuads];
-          counts[k][4 * q] = w.x; counts[k][4 * q + 1] = w.y; counts[k][4 * q + 2] = w.z; counts[k][4 * q + 3] = w.w;
-        }
-      }
-      const long gj = gj_base + c;
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        const long gi = gi_base + row;
-        const bool ok = gi <= gj && gj < n && win.in(gi, gj);
-        double tv = 0.0;
-        if (ok) tv = ld_apply_term(prov, counts, reg, gi, gj, term, inv_adj);
-        tsc[row * 33 + c] = tv;
-        const unsigned long long bal = __ballot(ok);
-        if (c == 0) rmask[row] = (unsigned)(bal >> (32 * hh));
-      }
-      __builtin_amdgcn_wave_barrier();                       // the wave reads what it wrote: LDS operations of one wave complete in order
-      // J side: column gj, the rows gi < gj of the sub-block
-      const double *xi = xs + ((wi * 128 + a * 32) * NC + kh);
-#pragma unroll 2
-      for (int row = 0; row < 32; row++) {
-        if (((rmask[row] >> c) & 1u) && gi_base + row != gj) {
-          const double tv = tsc[row * 33 + c];
-#pragma unroll
-          for (int k = 0; k < 8; k++) colacc[b][k] = fma(tv, xi[row * NC + k], colacc[b][k]);
-        }
-      }
-      // I side: row gi_base + c, the columns of the sub-block
-      const unsigned mine = rmask[c];
-      const double *xj = xs + ((kXT + wj * 128 + b * 32) * NC + kh);
-#pragma unroll 2
-      for (int cc = 0; cc < 32; cc++) {
-        if ((mine >> cc) & 1u) {
-          const double tv = tsc[c * 33 + cc];
-#pragma unroll
-          for (int k = 0; k < 8; k++) rowacc[a][k] = fma(tv, xj[cc * NC + k], rowacc[a][k]);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  // the partials of the tile: P[tile][side][row][ncols]; a side is the sum of its two halves, formed through the LDS where X was
-  double *Pt = P + (size_t)blockIdx.x * 2 * kXT * (size_t)ncols;
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int k = 0; k < 8; k++) xs[(wj * kXT + wi * 128 + a * 32 + c) * NC + kh + k] = rowacc[a][k];
-  __syncthreads();
-  for (int e = tid; e < kXT * NC; e += 256) {
-    const int row = e / NC, k = e % NC;
-    if (c0 + k < ncols) Pt[(size_t)row * (size_t)ncols + (size_t)(c0 + k)] = xs[row * NC + k] + xs[(kXT + row) * NC + k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int b = 0; b < 4; b++)
-#pragma unroll
-    for (int k = 0; k < 8; k++) xs[(wi * kXT + wj * 128 + b * 32 + c) * NC + kh + k] = colacc[b][k];
-  __syncthreads();
-  for (int e = tid; e < kXT * NC; e += 256) {
-    const int row = e / NC, k = e % NC;
-    if (c0 + k < ncols) Pt[(size_t)(kXT + row) * (size_t)ncols + (size_t)(c0 + k)] = xs[row * NC + k] + xs[(kXT + row) * NC + k];
-  }
-}
-
-// Per group of tile rows [i_lo, i_hi): one thread per (row i, column c) of the row blocks B = i_lo .. jmax[i_hi - 1] the group touches.  Y[i, c] takes, in this
-// order, the J sides of the group's tiles (I, B), I ascending from max(i_lo, imin[B]) (imin[B] = the first tile row that reaches B; jmax is non-decreasing),
-// and, where B is one of the group's tile rows, the I sides of its tiles (B, J), J ascending.  tfirst[I] = the window tiles in front of tile row I.
-__global__ void __launch_bounds__(256) k_ld_apply_finish(const double *__restrict__ P, int ncols, const long *__restrict__ tfirst, const int *__restrict__ jmax,
-                                                         const int *__restrict__ imin, int i_lo, int i_hi, long n, long nrows, double *__restrict__ Y, long ldy,
-                                                         long blk0) {
-  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (idx >= nrows * (long)ncols) return;
-  const long i = (long)i_lo * kXT + idx / ncols;
-  const int col = (int)(idx % ncols);
-  if (i >= n) return;
-  const int B = (int)(i / kXT), rr = (int)(i % kXT);
-  double *y = Y + (size_t)i + (size_t)col * (size_t)ldy;
-  double sum = *y;
-  auto part = [&](long tile, int side) { return P[((size_t)(tile * 2 + side) * kXT + (size_t)rr) * (size_t)ncols + (size_t)col]; };
-  const int i_end = min(i_hi - 1, B);
-  for (int I = max(i_lo, imin[B]); I <= i_end; I++) sum += part(tfirst[I] - tfirst[i_lo] + (B - I), 1);
-  if (B < i_hi) {
-    const int J1 = jmax[B];
-    for (int J = B; J <= J1; J++) sum += part(tfirst[B] - tfirst[i_lo] + (J - B), 0);
-  }
-  *y = sum;
-}
-
-// both routes of the apply entries (pairwise: the pairwise-complete r; else the plain route with is_plink and freq)
-static int ld_apply_any(const char *who, const unsigned char *plink, long snps, long indiv, const int *last, int term, const double *X, long ldx, long n, double *Y,
-                        long ldy, bool pairwise, bool is_plink, const double *freq) {
-  if (!last || !X || !Y) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (n < 1 || n > kLdApplyMaxCols) { set_error(1, "%s: need 1 <= n <= %ld (n %ld)", who, kLdApplyMaxCols, n); return 1; }
-  if (term < 0 || term > 2) { set_error(1, "%s: term must be 0, 1 or 2", who); return 1; }
-  if (term == 2 && indiv < 3) { set_error(1, "%s: the adjusted term needs indiv >= 3", who); return 1; }
-  if (snps > 0 && (ldx < snps || ldy < snps)) { set_error(1, "%s: need ldx >= snps and ldy >= snps (ldx %ld, ldy %ld, snps %ld)", who, ldx, ldy, snps); return 1; }
-  const size_t cap = ld_scratch_cap();
-  LdWindow c(who, plink, snps, indiv, 0, last, Y, ldy, false, 0);
-  c.set_apply((int)n);
-  const int pairs_max = pairwise ? kPwPairs : 1;
-  const size_t part_bytes = sizeof(double) * 2 * kXT * (size_t)n;   // the partials of a window tile: they share the cap with its count slots
-  bool x_dev = false;
-  // the scratch and the partials as ld_pairwise_any counts the scratch, the device copy of a host X, the window tiles' list and the plan's arrays
-  auto extra = [&] {
-    x_dev = ptr_location(X, nullptr) == 1;
-    const size_t tile_bytes = pairs_max * kPwSlotBytes + part_bytes;
-    return std::min(std::max(cap, c.row_tiles_max * tile_bytes), c.ntiles * tile_bytes) + (x_dev ? 0 : sizeof(double) * (size_t)snps * (size_t)n) +
-           c.ntiles * sizeof(int4) + sizeof(long) * ((size_t)c.g.nb + 1) + 2 * sizeof(int) * (size_t)c.g.nb;
-  };
-  if (c.begin(pairwise ? 3 : 1, extra, pairwise || freq ? nullptr : "%s: allele frequencies are required", pairwise ? kPwMaxIndiv : 0L, "%s",
-              pairwise ? "%s: at most %ld SNPs per call" : "%s: at most %ld SNPs per call (the fused statistics)")) return 1;
-  const XGeom &g = c.g;
-  hipStream_t s = c.s;
-  LdPlainOperand plain;
-  LdPairwiseOperand pw;
-  if (pairwise ? pw.stage(c, plink) : plain.stage(c, plink, is_plink, freq)) return 1;
-  const bool f4 = pairwise ? pw.f4 : plain.f4;
-  const int pairs = pairwise ? pw.pairs : 1;
-  LdGroups gr(c, cap, pairs, part_bytes);
-  // the plan's arrays on the device: tfirst (nb + 1 longs), then jmax and imin (nb ints each)
-  std::vector<long> tfirst((size_t)g.nb + 1, 0);
-  std::vector<int> imin((size_t)g.nb, 0);
-  for (int I = 0; I < g.nb; I++) tfirst[(size_t)I + 1] = tfirst[(size_t)I] + (c.jmax[(size_t)I] - I + 1);
-  for (int B = 0, I = 0; B < g.nb; B++) { while (c.jmax[(size_t)I] < B) I++; imin[(size_t)B] = I; }   // jmax[B] >= B ends the search
-  XTiles t;
-  XBuf d_scr, d_bt, d_part, d_plan, d_xm;
-  if (upload_tiles(std::move(gr.prod), s, t)) return 1;
-  if (d_bt.alloc(gr.band.size() * sizeof(int4)) || d_scr.alloc(gr.tiles_max * (size_t)pairs * kPwSlotBytes) || d_part.alloc(gr.tiles_max * part_bytes) ||
-      d_plan.alloc(sizeof(long) * ((size_t)g.nb + 1) + 2 * sizeof(int) * (size_t)g.nb) || (!x_dev && d_xm.alloc(sizeof(double) * (size_t)snps * (size_t)n))) return 1;
-  long *d_tfirst = (long *)d_plan.p;
-  int *d_jmax = (int *)(d_tfirst + g.nb + 1), *d_imin = d_jmax + g.nb;
-  MXA_HIP(hipMemcpyAsync(d_bt.p, gr.band.data(), gr.band.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  MXA_HIP(hipMemcpyAsync(d_tfirst, tfirst.data(), sizeof(long) * tfirst.size(), hipMemcpyHostToDevice, s));
-  MXA_HIP(hipMemcpyAsync(d_jmax, c.jmax.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice, s));
-  MXA_HIP(hipMemcpyAsync(d_imin, imin.data(), sizeof(int) * (size_t)g.nb, hipMemcpyHostToDevice, s));
-  // X once to the device (compact), Y cleared once: its snps rows of every column, nothing else
-  const double *d_x = X;
-  long ld_x = ldx;
-  if (!x_dev) {
-    MXA_HIP(hipMemcpy2DAsync(d_xm.p, sizeof(double) * (size_t)snps, X, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)snps, (size_t)n, hipMemcpyHostToDevice, s));
-    d_x = (const double *)d_xm.p;
-    ld_x = snps;
-  }
-  double *d_y = c.d_res;
-  const long ld_y = c.out_dev ? ldy : snps;
-  MXA_HIP(hipMemset2DAsync(d_y, sizeof(double) * (size_t)ld_y, 0, sizeof(double) * (size_t)snps, (size_t)n, s));
-  if (c.start()) return 1;
-  const XPost none{};
-  const LdVarWindow win{(const int *)c.d_last.p, nullptr, c.ndiag};
-  const unsigned chunks = (unsigned)((n + kLdApplyNC - 1) / kLdApplyNC);
-  static unsigned long long lds_mask[3] = {0, 0, 0};
-  for (int q = 0; q < gr.n; q++) {
-    // the group's products into the scratch, its tiles' partials, and the partials into Y (the next group reuses the scratch and the partials)
-    if (t.launch(q, g, f4, s, c.X(), (double *)d_scr.p, 0, 0, nullptr, kPostCounts, none)) return 1;
-    const dim3 grid((unsigned)(gr.band_first[(size_t)q + 1] - gr.band_first[(size_t)q]), chunks);
-    const int4 *bt = (const int4 *)d_bt.p + gr.band_first[(size_t)q];
-    auto tile = [&](auto prov, int which) {
-      constexpr auto K = &k_ld_apply_tile<decltype(prov), LdVarWindow>;
-      if (ensure_dyn_lds(reinterpret_cast<const void *>(K), kLdApplyLds, &lds_mask[which])) return 1;
-      hipLaunchKernelGGL(K, grid, dim3(256), kLdApplyLds, s, (const int *)d_scr.p, bt, snps, prov, win, term, d_x, ld_x, (int)n, (double *)d_part.p);
-      return 0;
-    };
-    if (!pairwise ? tile(LdPairsPlain{plain.xp.u, plain.xp.w, plain.xp.a}, 0) : pw.dense ? tile(LdPairsCounts{}, 1) : tile(LdPairsSums{pw.d_sz, pw.d_sa, (double)indiv}, 2)) return 1;
-    const int i_lo = gr.row0[(size_t)q], i_hi = gr.row0[(size_t)q + 1];
-    const long nrows = std::min(snps, ((long)c.jmax[(size_t)i_hi - 1] + 1) * kXT) - (long)i_lo * kXT;
-    // One thread per (row, column) of the group: the limit of a launch is 2^32 threads, not 2^31 workgroups, so this goes in pieces as well (every thread
-    // owns its Y[i, c]: no order between the pieces).  No test reaches the second piece: under the default 2 GiB scratch cap a group holds nrows n <= 2^26,
-    // and 2^32 (row, column) pairs in one group need more than 100 GB of partial sums.
-    launch_in_block_chunks((nrows * n + 255) / 256, [&](unsigned nb, long blk0) {
-      hipLaunchKernelGGL(k_ld_apply_finish, dim3(nb), dim3(256), 0, s, (const double *)d_part.p, (int)n, (const long *)d_tfirst, (const int *)d_jmax,
-                         (const int *)d_imin, i_lo, i_hi, snps, nrows, d_y, ld_y, blk0);
-    });
-    MXA_HIP(hipGetLastError());
-  }
-  if (c.finish_apply()) return 1;
-  debug_info("%s: %d group(s), %d product(s) per window tile, %s engine, %ld column(s) in %u chunk(s)", who, gr.n, pairs, f4 ? "FP4" : "int8", n, chunks);
-  return 0;
-}
-
-// ---- greedy selection on the pairs graph (mxa_ld_prune_csr, mxa_ld_window_prune, mxa_ld_window_prune_pairwise).  G: the strict upper CSR (rowptr, col) read as
-// an undirected graph.  a comes before b iff priority[a] < priority[b], or they are equal and a < b (priority == nullptr: a < b).  Result: the greedy walk in
-// that order -- keep a SNP iff none of its neighbours is kept --, i.e. the lexicographically first maximal independent set, which is unique: nothing below
-// depends on a schedule.  state[v]: 0 undecided, r > 0 kept in round r, kPruneRemoved.  Round r = 1, 2, .. is two launches that end on their own:
-//   k_ld_prune_edges     one wave per row i of the upper CSR, lanes over its columns j, reading the states round r - 1 left.  Row i is active iff i is undecided or
-//                        was kept in round r - 1:  i kept in r - 1, j undecided: rm[j] = r;  i undecided, j kept (any age): rm[i] = r;  both undecided:
-//                        bl[the later one] = r.  rm ("remove") and bl ("blocked") are round stamps: every writer of a round writes the same r, rounds only
-//                        grow, so they are never cleared.
-//   k_ld_prune_vertices  an undecided v with rm[v] == r is removed; else with bl[v] != r it is kept (state r); else it waits.  One integer atomicAdd per
-//                        workgroup of its undecided and of its kept count (integer sums: no order).
-// The upper triangle suffices: an edge {i < j} with an undecided endpoint has i undecided (row i is active), or i kept -- then row i was active in the round after
-// i was kept and removed every undecided upper neighbour, j among them --, or i removed, and then nothing is to do.  A kept j > i is seen from row i, which is
-// active while i is undecided.  v is kept only when all its earlier neighbours are removed and none is kept, which is the walk's decision; v is removed only next
-// to a kept SNP, and that SNP comes before v (it was kept with all its earlier neighbours decided).  The first undecided SNP in the order is never blocked, so
-// every round decides one: rounds <= snps.
-// The host enqueues the rounds in batches (kPruneBatch0 rounds, doubling up to kPruneBatchMax) and reads the batch's undecided counts once; the first zero is
-// the round of convergence, so `rounds` does not depend on the batching, and a round behind it returns at its first load (und_prev).
-constexpr int kPruneRemoved = -1, kPruneBatch0 = 8, kPruneBatchMax = 128, kPruneNoOwner = 0x7fffffff;
-constexpr unsigned long long kPruneNoKey = ~0ull;
-
-// a 64-bit key with key(p) < key(q) iff p < q for all non-NaN doubles; -0.0 and +0.0 share one key
-__device__ __forceinline__ unsigned long long prune_key(double p) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(p + 0.0);
-  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-
-__global__ void __launch_bounds__(256) k_ld_prune_edges(const long *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ prio, long n, int round,
-                                                        const int *__restrict__ state, int *__restrict__ rm, int *__restrict__ bl, const int *__restrict__ und_prev,
-                                                        long blk0) {
-  if (und_prev && *und_prev == 0) return;                    // converged in an earlier round of this batch
-  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const int lane = threadIdx.x & 63, si = state[i];
-  if (si != 0 && (si != round - 1 || round == 1)) return;   // neither undecided nor kept in the previous round (kPruneRemoved is never round - 1)
-  const long k1 = rowptr[i + 1];
-  const double pi = prio ? prio[i] : 0.0;
-  bool remove_i = false, block_i = false;
-  for (long k = rowptr[i] + lane; k < k1; k += 64) {
-    const int j = col[k], sj = state[j];
-    if (si != 0) {
-      if (sj == 0) atomicMax(&rm[j], round);
-    } else if (sj > 0) remove_i = true;
-    else if (sj == 0) {                                      // i < j: i comes first unless j's priority is strictly smaller
-      if (prio && prio[j] < pi) block_i = true;
-      else atomicMax(&bl[j], round);
-    }
-  }
-  if (remove_i) atomicMax(&rm[i], round);
-  if (block_i) atomicMax(&bl[i], round);
-}
-
-__global__ void __launch_bounds__(256) k_ld_prune_vertices(long n, int round, int *__restrict__ state, const int *__restrict__ rm, const int *__restrict__ bl,
-                                                           int *__restrict__ und, unsigned long long *__restrict__ kept, const int *__restrict__ und_prev) {
-  if (und_prev && *und_prev == 0) return;
-  const long v = (long)blockIdx.x * 256 + threadIdx.x;
-  int waits = 0, keeps = 0;
-  if (v < n && state[v] == 0) {
-    if (rm[v] == round) state[v] = kPruneRemoved;
-    else if (bl[v] != round) { state[v] = round; keeps = 1; }
-    else waits = 1;
-  }
-  const int nw = __syncthreads_count(waits), nk = __syncthreads_count(keeps);
-  if (threadIdx.x == 0) {
-    if (nw) atomicAdd(und, nw);
-    if (nk) atomicAdd(kept, (unsigned long long)nk);
-  }
-}
-
-// the results from the final states: keep, and the start of the owner pass (a kept SNP owns itself)
-__global__ void __launch_bounds__(256) k_ld_prune_result(long n, const int *__restrict__ state, unsigned char *__restrict__ keep, int *__restrict__ owner,
-                                                         unsigned long long *__restrict__ key) {
-  const long v = (long)blockIdx.x * 256 + threadIdx.x;
-  if (v >= n) return;
-  const bool kept = state[v] > 0;
-  keep[v] = kept ? 1 : 0;
-  if (owner) owner[v] = kept ? (int)v : kPruneNoOwner;
-  if (key) key[v] = kPruneNoKey;
-}
-
-// The owner pass, once after convergence, one wave per row over all rows: on every edge with exactly one kept endpoint the dropped endpoint takes the minimum
-// over its kept neighbours in the order.  KEY: atomicMin of the neighbours' priority keys; then (!KEY) atomicMin of the index among the neighbours whose key is
-// that minimum (prio == nullptr: every neighbour).  The row's own minimum is reduced over the wave first: one atomic per row for it.
-template <bool KEY>
-__global__ void __launch_bounds__(256) k_ld_prune_owner(const long *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ prio, long n,
-                                                        const int *__restrict__ state, unsigned long long *__restrict__ key, int *__restrict__ owner, long blk0) {
-  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const int lane = threadIdx.x & 63;
-  const bool ki = state[i] > 0;
-  const long k1 = rowptr[i + 1];
-  const unsigned long long key_i = prio ? prune_key(prio[i]) : 0ull, want_i = !KEY && prio && !ki ? key[i] : 0ull;
-  unsigned long long best_key = kPruneNoKey;
-  int best = kPruneNoOwner;
-  for (long k = rowptr[i] + lane; k < k1; k += 64) {
-    const int j = col[k];
-    const bool kj = state[j] > 0;
-    if (ki == kj) continue;
-    if (ki) {                                                // i kept, j dropped
-      if constexpr (KEY) atomicMin(&key[j], key_i);
-      else if (!prio || key[j] == key_i) atomicMin(&owner[j], (int)i);
-    } else {                                                 // j kept, i dropped
-      if constexpr (KEY) best_key = min(best_key, prune_key(prio[j]));
-      else if (!prio || prune_key(prio[j]) == want_i) best = min(best, j);
-    }
-  }
-  if (ki) return;                                            // wave-uniform
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    if constexpr (KEY) best_key = min(best_key, (unsigned long long)__shfl_xor((long long)best_key, off));
-    else best = min(best, __shfl_xor(best, off));
-  }
-  if (lane == 0) {
-    if constexpr (KEY) { if (best_key != kPruneNoKey) atomicMin(&key[i], best_key); }
-    else if (best != kPruneNoOwner) atomicMin(&owner[i], best);
-  }
-}
-
-// the checks of a caller's CSR on the device: rowptr first (bad |= 1), and only behind a sound rowptr -- every range then lies inside [0, rowptr[n]), the
-// length the caller vouches for -- the columns, one wave per row (bad |= 2)
-__global__ void __launch_bounds__(256) k_ld_prune_check_rowptr(const long *__restrict__ rowptr, long n, int *__restrict__ bad) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && ((i == 0 && rowptr[0] != 0) || rowptr[i + 1] < rowptr[i])) atomicOr(bad, 1);
-}
-__global__ void __launch_bounds__(256) k_ld_prune_check_col(const long *__restrict__ rowptr, const int *__restrict__ col, long n, int *__restrict__ bad, long blk0) {
-  if (*bad) return;
-  const long i = (blk0 + blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const long k0 = rowptr[i], k1 = rowptr[i + 1];
-  for (long k = k0 + (threadIdx.x & 63); k < k1; k += 64) {
-    const long j = col[k];
-    if (j <= i || j >= n || (k > k0 && col[k - 1] >= j)) atomicOr(bad, 2);
-  }
-}
-__global__ void __launch_bounds__(256) k_ld_prune_check_nan(const double *__restrict__ prio, long n, int *__restrict__ bad) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && prio[i] != prio[i]) atomicOr(bad, 4);
-}
-
-static int prune_need(const char *who, size_t bytes) {
-  size_t free_b = 0, total_b = 0;
-  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (bytes > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, bytes >> 30, free_b >> 30); return 1; }
-  return 0;
-}
-// what ld_prune_graph allocates: state, rm, bl; the owner pass's keys; the device copies of host outputs; the counters
-static size_t prune_graph_bytes(long snps, bool with_owner, bool with_prio, bool out_dev) {
-  const size_t n = (size_t)snps;
-  return 3 * sizeof(int) * n + (with_owner && with_prio ? sizeof(unsigned long long) * n : 0) + (out_dev ? 0 : n + (with_owner ? sizeof(int) * n : 0)) + 4096;
-}
-
-// priority on the device and free of NaN: *d_prio = the caller's device pointer, or an upload into `tmp`; nullptr stays nullptr
-static int prune_priority(const char *who, long snps, const double *priority, XBuf &tmp, XBuf &d_bad, hipStream_t s, const double **d_prio) {
-  *d_prio = priority;
-  if (!priority) return 0;
-  if (ptr_location(priority, nullptr) == 1) {
-    if (d_bad.alloc(sizeof(int))) return 1;
-    MXA_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_ld_prune_check_nan, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, priority, snps, (int *)d_bad.p);
-    MXA_HIP(hipGetLastError());
-    int bad = 0;
-    MXA_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    if (bad) { set_error(1, "%s: priority holds a NaN", who); return 1; }
-    return 0;
-  }
-  for (long i = 0; i < snps; i++)
-    if (priority[i] != priority[i]) { set_error(1, "%s: priority[%ld] is NaN", who, i); return 1; }
-  if (prune_need(who, sizeof(double) * (size_t)snps) || tmp.alloc(sizeof(double) * (size_t)snps)) return 1;
-  MXA_HIP(hipMemcpyAsync(tmp.p, priority, sizeof(double) * (size_t)snps, hipMemcpyHostToDevice, s));
-  *d_prio = (const double *)tmp.p;
-  return 0;
-}
-
-// the checks of the outputs all three entries share; *out_dev: keep (and owner) are device pointers
-static int prune_outputs(const char *who, const unsigned char *keep, const int *owner, bool *out_dev) {
-  *out_dev = ptr_location(keep, nullptr) == 1;
-  if (owner && (ptr_location(owner, nullptr) == 1) != *out_dev) { set_error(1, "%s: keep and owner must be both host or both device pointers", who); return 1; }
-  return 0;
-}
-
-// The graph step on device arrays (d_prio may be nullptr, d_col too when the graph has no edge).  Every argument has been checked.
-static int ld_prune_graph(const char *who, long snps, const long *d_rowptr, const int *d_col, const double *d_prio, unsigned char *keep, int *owner, bool out_dev,
-                          long *n_kept, int *rounds, hipStream_t s) {
-  const size_t n = (size_t)snps;
-  if (prune_need(who, prune_graph_bytes(snps, owner != nullptr, d_prio != nullptr, out_dev))) return 1;
-  XBuf d_state, d_cnt, d_key, d_keep, d_owner;               // d_state: state, rm, bl; d_cnt: kept (8 bytes), then the batch's undecided counts
-  if (d_state.alloc(3 * sizeof(int) * n) || d_cnt.alloc(sizeof(unsigned long long) + sizeof(int) * kPruneBatchMax)) return 1;
-  if (owner && d_prio && d_key.alloc(sizeof(unsigned long long) * n)) return 1;
-  if (!out_dev && (d_keep.alloc(n) || (owner && d_owner.alloc(sizeof(int) * n)))) return 1;
-  int *state = (int *)d_state.p, *rm = state + n, *bl = rm + n;
-  unsigned long long *d_kept = (unsigned long long *)d_cnt.p;
-  int *d_und = (int *)(d_kept + 1);
-  unsigned char *r_keep = out_dev ? keep : (unsigned char *)d_keep.p;
-  int *r_owner = !owner ? nullptr : out_dev ? owner : (int *)d_owner.p;
-  MXA_HIP(hipMemsetAsync(state, 0, 3 * sizeof(int) * n, s));
-  MXA_HIP(hipMemsetAsync(d_kept, 0, sizeof(unsigned long long), s));
-  // One wave per row (edge and owner passes): 64 snps threads, 2^32 of them from 2^26 SNPs on, so these sweeps run in pieces (launch_in_block_chunks; the
-  // pieces of a round read the states the round before left and write round stamps and atomic minima only, so their order does not matter).  One thread per
-  // SNP in the vertex passes: snps is an int, a single launch.
-  const long rows_blocks = (snps + 3) / 4;
-  const dim3 vert_grid((unsigned)((snps + 255) / 256));
-  int h_und[kPruneBatchMax];
-  int round = 0, done = 0;
-  for (int batch = kPruneBatch0; !done; batch = std::min(2 * batch, kPruneBatchMax)) {
-    MXA_HIP(hipMemsetAsync(d_und, 0, sizeof(int) * (size_t)batch, s));
-    for (int b = 0; b < batch; b++) {
-      round++;
-      const int *prev = b ? d_und + b - 1 : nullptr;
-      launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
-        hipLaunchKernelGGL(k_ld_prune_edges, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, round, (const int *)state, rm, bl, prev, blk0);
-      });
-      hipLaunchKernelGGL(k_ld_prune_vertices, vert_grid, dim3(256), 0, s, snps, round, state, (const int *)rm, (const int *)bl, d_und + b, d_kept, prev);
-    }
-    MXA_HIP(hipGetLastError());
-    MXA_HIP(hipMemcpyAsync(h_und, d_und, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < batch && !done; b++)
-      if (h_und[b] == 0) done = round - batch + b + 1;
-  }
-  hipLaunchKernelGGL(k_ld_prune_result, vert_grid, dim3(256), 0, s, snps, (const int *)state, r_keep, r_owner, (unsigned long long *)d_key.p);
-  if (owner) {
-    if (d_prio) launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
-      hipLaunchKernelGGL(k_ld_prune_owner<true>, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner, blk0);
-    });
-    launch_in_block_chunks(rows_blocks, [&](unsigned nb, long blk0) {
-      hipLaunchKernelGGL(k_ld_prune_owner<false>, dim3(nb), dim3(256), 0, s, d_rowptr, d_col, d_prio, snps, (const int *)state, (unsigned long long *)d_key.p, r_owner, blk0);
-    });
-  }
-  MXA_HIP(hipGetLastError());
-  unsigned long long h_kept = 0;
-  MXA_HIP(hipMemcpyAsync(&h_kept, d_kept, sizeof(h_kept), hipMemcpyDeviceToHost, s));
-  if (!out_dev) {
-    MXA_HIP(hipMemcpyAsync(keep, r_keep, n, hipMemcpyDeviceToHost, s));
-    if (owner) MXA_HIP(hipMemcpyAsync(owner, r_owner, sizeof(int) * n, hipMemcpyDeviceToHost, s));
-  }
-  MXA_HIP(hipStreamSynchronize(s));
-  *n_kept = (long)h_kept;
-  if (rounds) *rounds = done;
-  debug_info("%s: %ld of %ld SNPs kept in %d round(s)", who, (long)h_kept, snps, done);
-  return 0;
-}
-
-static int ld_prune_csr(const char *who, long snps, const long *rowptr, const int *col, const double *priority, unsigned char *keep, int *owner, long *n_kept, int *rounds) {
-  if (snps <= 0 || !rowptr || !keep || !n_kept) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (select_device() < 0) return 1;
-  bool out_dev = false;
-  if (prune_outputs(who, keep, owner, &out_dev)) return 1;
-  XStream st;
-  if (st.create(hipStreamDefault)) return 1;                 // blocking: ordered against the caller's default-stream work
-  hipStream_t s = st.s;
-  XBuf d_rp, d_cl, d_pr, d_bad, d_bad2;
-  const size_t n = (size_t)snps;
-  const bool rp_dev = ptr_location(rowptr, nullptr) == 1, cl_dev = ptr_location(col, nullptr) == 1;
-  // rowptr: checked where it lies; a host copy of its last entry gives the number of pairs
-  long nnz = 0;
-  std::vector<long> h_rp;
-  const long *h_rowptr = rowptr;
-  if (rp_dev) {
-    if (d_bad.alloc(sizeof(int))) return 1;
-    MXA_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_ld_prune_check_rowptr, dim3((unsigned)((snps + 255) / 256)), dim3(256), 0, s, rowptr, snps, (int *)d_bad.p);
-    MXA_HIP(hipGetLastError());
-    int bad = 0;
-    MXA_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipMemcpyAsync(&nnz, rowptr + snps, sizeof(long), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    if (bad) { set_error(1, "%s: rowptr needs rowptr[0] == 0 and must not decrease", who); return 1; }
-    if (!cl_dev && nnz) {                                    // host columns under a device rowptr: the host check below wants the rows
-      h_rp.resize(n + 1);
-      MXA_HIP(hipMemcpy(h_rp.data(), rowptr, sizeof(long) * (n + 1), hipMemcpyDeviceToHost));
-      h_rowptr = h_rp.data();
-    }
-  } else {
-    if (rowptr[0] != 0) { set_error(1, "%s: rowptr[0] must be 0 (%ld)", who, rowptr[0]); return 1; }
-    for (long i = 0; i < snps; i++)
-      if (rowptr[i + 1] < rowptr[i]) { set_error(1, "%s: rowptr decreases at row %ld", who, i); return 1; }
-    nnz = rowptr[snps];
-  }
-  if (nnz && !col) { set_error(1, "%s: bad arguments", who); return 1; }
-  const long *d_rowptr = rowptr;
-  const int *d_col = col;
-  if (!rp_dev) {
-    if (prune_need(who, sizeof(long) * (n + 1)) || d_rp.alloc(sizeof(long) * (n + 1))) return 1;
-    MXA_HIP(hipMemcpyAsync(d_rp.p, rowptr, sizeof(long) * (n + 1), hipMemcpyHostToDevice, s));
-    d_rowptr = (const long *)d_rp.p;
-  }
-  if (cl_dev && nnz) {
-    if (!d_bad.p && d_bad.alloc(sizeof(int))) return 1;
-    MXA_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s));
-    launch_in_block_chunks((snps + 3) / 4, [&](unsigned nb, long blk0) {
-      hipLaunchKernelGGL(k_ld_prune_check_col, dim3(nb), dim3(256), 0, s, d_rowptr, col, snps, (int *)d_bad.p, blk0);
-    });
-    MXA_HIP(hipGetLastError());
-    int bad = 0;
-    MXA_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    MXA_HIP(hipStreamSynchronize(s));
-    if (bad) { set_error(1, "%s: the columns of a row need i < col < snps, strictly ascending", who); return 1; }
-  } else if (nnz) {
-    for (long i = 0; i < snps; i++)
-      for (long k = h_rowptr[i]; k < h_rowptr[i + 1]; k++)
-        if (col[k] <= i || col[k] >= snps || (k > h_rowptr[i] && col[k - 1] >= col[k])) {
-          set_error(1, "%s: the columns of a row need i < col < snps, strictly ascending (row %ld, col %d)", who, i, col[k]);
-          return 1;
-        }
-    if (prune_need(who, sizeof(int) * (size_t)nnz) || d_cl.alloc(sizeof(int) * (size_t)nnz)) return 1;
-    MXA_HIP(hipMemcpyAsync(d_cl.p, col, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, s));
-    d_col = (const int *)d_cl.p;
-  }
-  const double *d_prio = nullptr;
-  if (prune_priority(who, snps, priority, d_pr, d_bad2, s, &d_prio)) return 1;
-  return ld_prune_graph(who, snps, d_rowptr, d_col, d_prio, keep, owner, out_dev, n_kept, rounds, s);
-}
-
-// The window entries: the pairs driver twice on device arrays of the library's own -- the count-only call sizes col exactly, the filling call writes col alone
-// (no_val) -- and the graph step on them.  Neither the CSR nor a val array leaves the device; the second call's pre-flight sees rowptr and col allocated.
-static int ld_prune_window(const char *who, const unsigned char *plink, long snps, long indiv, const int *last, double min_r2, const double *priority, unsigned char *keep,
-                           int *owner, long *n_kept, int *rounds, bool pairwise, bool is_plink, const double *freq) {
-  if (!plink || !last || !keep || !n_kept || snps <= 0 || indiv <= 0) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (select_device() < 0) return 1;
-  bool out_dev = false;
-  if (prune_outputs(who, keep, owner, &out_dev)) return 1;
-  const size_t n = (size_t)snps;
-  XBuf d_rp, d_cl, d_pr, d_bad;
-  const double *d_prio = nullptr;
-  long total = 0;
-  {
-    XStream st;                                              // the priority's check and upload; the pairs driver brings its own stream
-    if (st.create(hipStreamDefault)) return 1;
-    if (prune_priority(who, snps, priority, d_pr, d_bad, st.s, &d_prio)) return 1;
-    MXA_HIP(hipStreamSynchronize(st.s));
-  }
-  const size_t graph = prune_graph_bytes(snps, owner != nullptr, priority != nullptr, out_dev);
-  if (prune_need(who, sizeof(long) * (n + 1) + graph) || d_rp.alloc(sizeof(long) * (n + 1))) return 1;
-  long *d_rowptr = (long *)d_rp.p;
-  if (ld_pairs_any(who, plink, snps, indiv, last, min_r2, 1, d_rowptr, nullptr, nullptr, 0, &total, pairwise, is_plink, freq, true)) return 1;
-  if (total) {
-    if (prune_need(who, sizeof(int) * (size_t)total + graph) || d_cl.alloc(sizeof(int) * (size_t)total)) return 1;
-    long again = 0;
-    if (ld_pairs_any(who, plink, snps, indiv, last, min_r2, 1, d_rowptr, (int *)d_cl.p, nullptr, total, &again, pairwise, is_plink, freq, true)) return 1;
-  }
-  XStream st;
-  if (st.create(hipStreamDefault)) return 1;
-  return ld_prune_graph(who, snps, d_rowptr, total ? (const int *)d_cl.p : nullptr, d_prio, keep, owner, out_dev, n_kept, rounds, st.s);
-}
-
 }  // namespace mxa
-
-extern "C" int mxa_ld_band_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind) {
-  mxa::clear_error();
-  return mxa::ld_pairwise_any("mxa_ld_band_pairwise", plink, snps, indiv, window, nullptr, band, ldb, false, kind);
-}
-
-extern "C" int mxa_ld_scores_pairwise(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust) {
-  mxa::clear_error();
-  return mxa::ld_pairwise_any("mxa_ld_scores_pairwise", plink, snps, indiv, window, nullptr, scores, 0, true, adjust);
-}
-
-extern "C" int mxa_ld_band(const unsigned char *plink, int snps, int indiv, int window, double *band, long ldb, int kind, int is_plink_format,
-                           const double *allele_freq) {
-  mxa::clear_error();
-  return mxa::ld_window_any("mxa_ld_band", plink, snps, indiv, window, nullptr, band, ldb, false, kind, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_scores(const unsigned char *plink, int snps, int indiv, int window, double *scores, int adjust, int is_plink_format,
-                             const double *allele_freq) {
-  mxa::clear_error();
-  return mxa::ld_window_any("mxa_ld_scores", plink, snps, indiv, window, nullptr, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
-}
-
-// ---- windowed LD by distance: the window of SNP i ends at last[i] (mxa_ld_window_bounds makes it from base pairs / centimorgans / SNP counts and chromosomes)
-extern "C" int mxa_ld_window_rows(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind, int is_plink_format, const double *allele_freq) {
-  mxa::clear_error();
-  if (!last) { mxa::set_error(1, "mxa_ld_window_rows: bad arguments"); return 1; }
-  return mxa::ld_window_any("mxa_ld_window_rows", plink, snps, indiv, 0, last, rows, 0, false, kind, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_window_scores(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust, int is_plink_format,
-                                    const double *allele_freq) {
-  mxa::clear_error();
-  if (!last) { mxa::set_error(1, "mxa_ld_window_scores: bad arguments"); return 1; }
-  return mxa::ld_window_any("mxa_ld_window_scores", plink, snps, indiv, 0, last, scores, 0, true, adjust, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_window_rows_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *rows, int kind) {
-  mxa::clear_error();
-  if (!last) { mxa::set_error(1, "mxa_ld_window_rows_pairwise: bad arguments"); return 1; }
-  return mxa::ld_pairwise_any("mxa_ld_window_rows_pairwise", plink, snps, indiv, 0, last, rows, 0, false, kind);
-}
-
-extern "C" int mxa_ld_window_scores_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double *scores, int adjust) {
-  mxa::clear_error();
-  if (!last) { mxa::set_error(1, "mxa_ld_window_scores_pairwise: bad arguments"); return 1; }
-  return mxa::ld_pairwise_any("mxa_ld_window_scores_pairwise", plink, snps, indiv, 0, last, scores, 0, true, adjust);
-}
-
-// ---- the pairs of a window with r^2 >= min_r2 as CSR of the strict upper triangle
-extern "C" int mxa_ld_window_pairs(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
-                                   long capacity, long *total, int is_plink_format, const double *allele_freq) {
-  mxa::clear_error();
-  return mxa::ld_pairs_any("mxa_ld_window_pairs", plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, false, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_window_pairs_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, int kind, long *rowptr, int *col, double *val,
-                                            long capacity, long *total) {
-  mxa::clear_error();
-  return mxa::ld_pairs_any("mxa_ld_window_pairs_pairwise", plink, snps, indiv, last, min_r2, kind, rowptr, col, val, capacity, total, true, true, nullptr);
-}
-
-// ---- the window applied to a matrix: Y = T_w(R) X without the rows
-extern "C" int mxa_ld_window_apply(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y, long ldy,
-                                   int is_plink_format, const double *allele_freq) {
-  mxa::clear_error();
-  return mxa::ld_apply_any("mxa_ld_window_apply", plink, snps, indiv, last, term, X, ldx, n, Y, ldy, false, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_window_apply_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, int term, const double *X, long ldx, int n, double *Y,
-                                            long ldy) {
-  mxa::clear_error();
-  return mxa::ld_apply_any("mxa_ld_window_apply_pairwise", plink, snps, indiv, last, term, X, ldx, n, Y, ldy, true, true, nullptr);
-}
-
-// ---- the greedy selection on the pairs graph: the graph step alone, and the window entries (pairs driver + graph step, all on the device)
-extern "C" int mxa_ld_prune_csr(int snps, const long *rowptr, const int *col, const double *priority, unsigned char *keep, int *owner, long *n_kept, int *rounds) {
-  mxa::clear_error();
-  return mxa::ld_prune_csr("mxa_ld_prune_csr", snps, rowptr, col, priority, keep, owner, n_kept, rounds);
-}
-
-extern "C" int mxa_ld_window_prune(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, const double *priority, unsigned char *keep, int *owner,
-                                   long *n_kept, int *rounds, int is_plink_format, const double *allele_freq) {
-  mxa::clear_error();
-  return mxa::ld_prune_window("mxa_ld_window_prune", plink, snps, indiv, last, min_r2, priority, keep, owner, n_kept, rounds, false, is_plink_format != 0, allele_freq);
-}
-
-extern "C" int mxa_ld_window_prune_pairwise(const unsigned char *plink, int snps, int indiv, const int *last, double min_r2, const double *priority, unsigned char *keep,
-                                            int *owner, long *n_kept, int *rounds) {
-  mxa::clear_error();
-  return mxa::ld_prune_window("mxa_ld_window_prune_pairwise", plink, snps, indiv, last, min_r2, priority, keep, owner, n_kept, rounds, true, true, nullptr);
-}
-
-// The window ends of a distance window, on the host (no device is touched): last[i] = the largest j >= i on i's chromosome with pos[j] - pos[i] <= max_dist
-// (one rounded fp64 subtraction, inclusive) and j - i <= max_snps.  All three bounds are monotone in j for fixed i and the end never moves back as i grows,
-// so one two-pointer sweep finds every end: O(snps).
-extern "C" int mxa_ld_window_bounds(int snps, const double *pos, const int *chrom, double max_dist, int max_snps, int *last, long *rowptr) {
-  mxa::clear_error();
-  const char *who = "mxa_ld_window_bounds";
-  if (snps <= 0 || !last) { mxa::set_error(1, "%s: bad arguments", who); return 1; }
-  if (!pos && max_snps < 0) { mxa::set_error(1, "%s: neither a distance bound (pos) nor a SNP bound (max_snps >= 0) is given", who); return 1; }
-  if (!(max_dist >= 0.0)) { mxa::set_error(1, "%s: max_dist must not be negative or NaN", who); return 1; }
-  if (pos)
-    for (long i = 0; i < snps; i++) {
-      if (pos[i] != pos[i]) { mxa::set_error(1, "%s: position %ld is NaN", who, i); return 1; }
-      if (i > 0 && (!chrom || chrom[i] == chrom[i - 1]) && pos[i] < pos[i - 1]) { mxa::set_error(1, "%s: position %ld decreases inside a chromosome", who, i); return 1; }
-    }
-  if (chrom) {   // contiguous: a code that starts a run has not been seen before
-    std::vector<int> seen;
-    for (long i = 0; i < snps; i++)
-      if (i == 0 || chrom[i] != chrom[i - 1]) seen.push_back(chrom[i]);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { mxa::set_error(1, "%s: the SNPs of a chromosome are not contiguous", who); return 1; }
-  }
-  long j = 0;                                               // the end of the window of i - 1: the window of i reaches at least as far
-  for (long i = 0; i < snps; i++) {
-    if (j < i) j = i;
-    while (j + 1 < snps && (!chrom || chrom[j + 1] == chrom[i]) && (!pos || pos[j + 1] - pos[i] <= max_dist) && (max_snps < 0 || j + 1 - i <= (long)max_snps)) j++;
-    last[i] = (int)j;
-  }
-  if (rowptr) {
-    rowptr[0] = 0;
-    for (long i = 0; i < snps; i++) rowptr[i + 1] = rowptr[i] + ((long)last[i] - i + 1);
-  }
-  return 0;
-}
 
 extern "C" int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, double *ans, bool is_plink_format) {
   // positional meaning as in the reference: arg 2 = packed (inner) dimension, arg 3 = output dimension

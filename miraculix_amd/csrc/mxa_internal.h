@@ -286,7 +286,9 @@ int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_t
 // G_tn: the OTHER stored orientation (rows = the K index); the main kernel then runs in the transposed-operand form k_gemm_i8_tn, one launch per tile of 32
 // expanded columns.  Returns 2 (nothing enqueued) when that would take more passes than the fp64 MFMA tile costs or the plan has several column chunks.
 
-// mxa_crossprod.hip: the two windowed-LD host drivers, also run by the LD operator object (mxa_ldop.hip) into a device buffer of ragged rows.
+// mxa_ldwindow.hip: the host drivers of the band / rows / scores entries -- ld_window_any: the plain route, the window epilogue of the crossproduct kernels;
+// ld_pairwise_any: the pairwise-complete route, through the count scratch (LdCountRun) -- also run by the LD operator object (mxa_ldop.hip) into a device
+// buffer of ragged rows.  What the crossproduct, window, pruning and operator units share beyond these two lies in mxa_xprod.h.
 // window / ldb: the fixed entries' band (last == nullptr); last: the general window (rows: out = rowptr[snps] doubles; scores: snps).  out: host or device.
 int ld_window_any(const char *who, const unsigned char *plink, long snps, long indiv, long window, const int *last, double *out, long ldb, bool scores, int flag,
                   bool is_plink, const double *freq);

@@ -1,6 +1,6 @@
 // mxa_ldop.hip -- the LD operator object: the window's values T staged once in device memory, then applied and ridge-solved there (last subsection).
 //
-// Creation runs the existing rows driver (ld_window_any / ld_pairwise_any of mxa_crossprod.hip) into a device buffer of the upper ragged rows, so T is bit
+// Creation runs the existing rows driver (ld_window_any / ld_pairwise_any of mxa_ldwindow.hip) into a device buffer of the upper ragged rows, so T is bit
 // for bit what mxa_ld_window_rows(_pairwise) stores; k_ld_op_mirror turns them into the MIRRORED ragged rows: row j holds T[j, first[j] .. last[j]]
 // contiguously at full[ptr[j] ..].  By symmetry T[i, j] = full[ptr[j] + i - first[j]], so a workgroup of 256 consecutive output rows i that sweeps j upwards
 // reads 256 consecutive doubles per j (k_ld_op_apply): the object is streamed once per chunk of columns, X[j, .] is a wave-uniform load.
@@ -14,6 +14,7 @@
 #include "../../include/miraculix_amd.h"
 #include "mxa_internal.h"
 #include "mxa_ldop_host.h"
+#include "mxa_xprod.h"
 
 namespace mxa {
 
@@ -21,8 +22,6 @@ namespace {
 constexpr int kOpRows = 256;         // output rows per workgroup of the apply (one per thread)
 constexpr int kOpMaxNC = 16;         // columns a thread keeps in registers
 constexpr int kDotRows = 1024;       // rows per workgroup of the vector kernels: the partial count depends on snps alone
-constexpr long kOpMaxSnps = 29000000L;     // the rows drivers' limits (mxa_crossprod.hip), checked here before any memory is asked for
-constexpr long kOpMaxIndivPairwise = 47453132L;
 constexpr int kOpMaxSolveCols = 65535;     // a column of the solve is one gridDim.y of its vector kernels
 
 struct LdOp {
@@ -45,13 +44,6 @@ LdOp *live_op(void *p) {
   std::lock_guard<std::mutex> lock(g_live_mutex);
   return g_live.count(p) ? static_cast<LdOp *>(p) : nullptr;
 }
-
-struct DevBuf {                      // RAII device buffer
-  void *p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { MXA_HIP(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
-  void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
 
 struct DeviceGuard {                 // the object's device for the length of a call
   int prev = -1;
@@ -311,13 +303,13 @@ bool operands_overlap(const double *a, long lda, const double *b, long ldb, long
 }
 
 // takes the upper rows (device, `entries` doubles, owned by `upper`) and the checked window; builds the object and releases the upper rows
-int finish_create(const char *who, long snps, const std::vector<int> &h_last, DevBuf &upper, void **out) {
+int finish_create(const char *who, long snps, const std::vector<int> &h_last, XBuf &upper, void **out) {
   std::vector<int> h_first((size_t)snps);
   std::vector<long> h_rowptr((size_t)snps + 1), h_ptr((size_t)snps + 1);
   long mirrored = 0;
   const long entries = ldop_layout(snps, h_last.data(), h_first.data(), h_rowptr.data(), h_ptr.data(), &mirrored);
   if (need_device_bytes(who, (size_t)ldop_object_bytes(snps, mirrored))) return 1;
-  DevBuf full, first, last, ptr, rowptr, base, xt, flag;
+  XBuf full, first, last, ptr, rowptr, base, xt, flag;
   std::vector<long> h_base((size_t)snps);
   for (long j = 0; j < snps; j++) h_base[(size_t)j] = h_ptr[(size_t)j] - h_first[(size_t)j];
   if (full.alloc(sizeof(double) * (size_t)mirrored) || first.alloc(sizeof(int) * (size_t)snps) || last.alloc(sizeof(int) * (size_t)snps) ||
@@ -374,8 +366,8 @@ int create_any(const char *who, const unsigned char *plink, int snps, int indiv,
   if (!pairwise && !freq) { set_error(1, "%s: allele frequencies are required", who); return 1; }
   if (kind != 0 && kind != 1) { set_error(1, "%s: kind must be 0 or 1", who); return 1; }
   // what the rows driver would reject is rejected before the memory pre-flight, so that error 12 never stands in for error 1
-  if (snps >= kOpMaxSnps) { set_error(1, "%s: at most %ld SNPs per call", who, kOpMaxSnps - 1); return 1; }
-  if (pairwise && indiv > kOpMaxIndivPairwise) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, kOpMaxIndivPairwise); return 1; }
+  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call", who, kXFusedMaxRows - 1); return 1; }
+  if (pairwise && indiv > kPwMaxIndiv) { set_error(1, "%s: at most %ld individuals per call (4 indiv^2 must stay below 2^53)", who, kPwMaxIndiv); return 1; }
   if (select_device() < 0) return 1;
   std::vector<int> h_last;
   if (fetch_last(who, snps, last, h_last)) return 1;
@@ -383,7 +375,7 @@ int create_any(const char *who, const unsigned char *plink, int snps, int indiv,
   const long entries = ldop_layout(snps, h_last.data(), nullptr, nullptr, nullptr, &mirrored);
   // the peak of the creation: the upper rows next to the mirrored ones (the rows driver checks its own staging against what is free once the upper rows stand)
   if (need_device_bytes(who, sizeof(double) * (size_t)entries + (size_t)ldop_object_bytes(snps, mirrored))) return 1;
-  DevBuf upper;
+  XBuf upper;
   if (upper.alloc(sizeof(double) * (size_t)entries)) return 1;
   const int rc = pairwise ? ld_pairwise_any(who, plink, snps, indiv, 0, last, (double *)upper.p, 0, false, kind)
                           : ld_window_any(who, plink, snps, indiv, 0, last, (double *)upper.p, 0, false, kind, is_plink != 0, freq);
@@ -431,14 +423,14 @@ extern "C" int mxa_ld_op_from_rows(int snps, const int *last, const double *rows
   if (!op) { set_error(1, "%s: bad arguments", who); return 1; }
   *op = nullptr;
   if (snps <= 0 || !last || !rows) { set_error(1, "%s: bad arguments", who); return 1; }
-  if (snps >= kOpMaxSnps) { set_error(1, "%s: at most %ld SNPs per call", who, kOpMaxSnps - 1); return 1; }
+  if (snps >= kXFusedMaxRows) { set_error(1, "%s: at most %ld SNPs per call", who, kXFusedMaxRows - 1); return 1; }
   if (select_device() < 0) return 1;
   std::vector<int> h_last;
   if (fetch_last(who, snps, last, h_last)) return 1;
   long mirrored = 0;
   const long entries = ldop_layout(snps, h_last.data(), nullptr, nullptr, nullptr, &mirrored);
   if (need_device_bytes(who, sizeof(double) * (size_t)entries + (size_t)ldop_object_bytes(snps, mirrored))) return 1;
-  DevBuf upper;
+  XBuf upper;
   if (upper.alloc(sizeof(double) * (size_t)entries)) return 1;
   MXA_HIP(hipMemcpy(upper.p, rows, sizeof(double) * (size_t)entries, hipMemcpyDefault));
   return finish_create(who, snps, h_last, upper, op);
@@ -454,7 +446,7 @@ extern "C" int mxa_ld_op_rows(void *op, double *rows) {
   DeviceGuard dg;
   if (dg.enter(o->device)) return 1;
   const bool dev = ptr_location(rows, nullptr) == 1;
-  DevBuf tmp;
+  XBuf tmp;
   const size_t bytes = sizeof(double) * (size_t)o->entries;
   if (!dev && (need_device_bytes(who, bytes) || tmp.alloc(bytes))) return 1;
   double *d = dev ? rows : (double *)tmp.p;
@@ -484,7 +476,7 @@ extern "C" int mxa_ld_op_apply(void *op, double shift, const double *X, long ldx
   if (x_dev == y_dev && operands_overlap(X, ldx, Y, ldy, snps, n)) { set_error(1, "%s: X and Y must not overlap", who); return 1; }
   const size_t cbytes = sizeof(double) * (size_t)snps * (size_t)n;       // a host operand's compact device copy (leading dimension snps)
   if (need_device_bytes(who, (x_dev ? 0 : cbytes) + (y_dev ? 0 : cbytes))) return 1;
-  DevBuf bx, by;
+  XBuf bx, by;
   if ((!x_dev && bx.alloc(cbytes)) || (!y_dev && by.alloc(cbytes))) return 1;
   const size_t col = sizeof(double) * (size_t)snps;
   if (!x_dev) MXA_HIP(hipMemcpy2DAsync(bx.p, col, X, sizeof(double) * (size_t)ldx, col, (size_t)n, hipMemcpyHostToDevice, o->stream));
@@ -519,7 +511,7 @@ extern "C" int mxa_ld_op_solve(void *op, double shift, const double *B, long ldb
   const int nblk = (int)((snps + kDotRows - 1) / kDotRows);
   const size_t pbytes = sizeof(double) * (size_t)nblk * (size_t)n, sbytes = (5 * sizeof(double) + 2 * sizeof(int)) * (size_t)n;
   if (need_device_bytes(who, (3 + (b_dev ? 0 : 1) + (x_dev ? 0 : 1)) * cbytes + pbytes + sbytes)) return 1;
-  DevBuf w_r, w_p, w_Ap, w_B, w_X, w_part, w_s;
+  XBuf w_r, w_p, w_Ap, w_B, w_X, w_part, w_s;
   if (w_r.alloc(cbytes) || w_p.alloc(cbytes) || w_Ap.alloc(cbytes) || (!b_dev && w_B.alloc(cbytes)) || (!x_dev && w_X.alloc(cbytes)) || w_part.alloc(pbytes) ||
       w_s.alloc(sbytes)) return 1;
   hipStream_t s = o->stream;

@@ -521,6 +521,48 @@ int mxa_ld_op_solve(void *op, double shift, const double *B, long ldb, int n, do
                     int *status);
 void mxa_ld_op_free(void **op);
 
+/* Association scan: per-SNP linear regression on packed genotypes -- the statistics the LD entries above start from.  For every SNP s and phenotype c the
+ * model y_c ~ 1 + Q + x_s, x_s = the genotype with missing calls replaced by the SNP's mean over its called individuals (what BOLT, fastGWA and regenie do).
+ * plink: snps rows of ceil(indiv / 4) bytes in PLINK coding (00 -> 0, 01 -> missing, 10 -> 1, 11 -> 2), host or device.  The padding fields of a row's last
+ *        byte (fields at and beyond indiv) are NOT individuals, whatever they hold.
+ * Y:     indiv x n phenotypes, column-major, ldy >= indiv.  Q: indiv x k covariate basis, column-major, ldq >= indiv, k >= 0; NULL iff k == 0.  Q is taken
+ *        as it is: its columns are expected to be orthonormal and to sum to zero -- exactly what mxa_assoc_basis produces.  An intercept is always fitted.
+ * Degrees of freedom: dof = indiv - k - 2 >= 1.
+ * Phenotypes, once per call, on the device: ybar_c = the column mean, y <- y - ybar_c; twice (the second pass for stability): a = Q^T y, y <- y - Q a; the
+ * result is Y~; syy_c = sum y~^2; T_b = sum_i b_i for every column b of B = [Y~ | Q].  The summation orders of these steps are fixed by indiv and k alone,
+ * no atomics; they are not otherwise specified.
+ * Per SNP, exact integers from popcounts of the raw row (c1, c2 = the numbers of codes 10 and 11): N = the called individuals, Sz = c1 + 2 c2,
+ * Szz = c1 + 4 c2.  Per SNP and column b of B: D_b = sum_i z_i b_i (z = the allele count, missing as 0: the library's own uncentred 'T' product on a one-shot
+ * packed object, whatever setOptions_compressed said) and M_b = sum over the SNP's missing individuals of b_i, in a fixed order that depends on indiv alone,
+ * no atomics.  Then, every operation rounded once, in this order:
+ *     mu   = Sz / N
+ *     v0   = (N Szz - Sz Sz) / N           numerator exact (integers below 4 indiv^2 < 2^53)
+ *     g_b  = fma(mu, M_b - T_b, D_b)       for every column b of [Y~ | Q]
+ *     sxx  = v0;  for q = 0 .. k-1 ascending: sxx = fma(-g_q, g_q, sxx)      (g_q: the Q columns)
+ *     beta = g_c / sxx                     (g_c: the column of Y~)
+ *     rss  = fma(-beta, g_c, syy_c)
+ *     se   = sqrt((rss / dof) / sxx)
+ *     t    = beta / se
+ * There is no special case: N == 0, a SNP constant on its called individuals and a SNP in the span of [1, Q] give non-finite results where the arithmetic
+ * says so; callers filter such SNPs, as for a monomorphic SNP in mxa_ld.  p-values are a wrapper's business (-|t| orders a clump).
+ * Results are identical from run to run, between host and device pointers and for every row-chunk size of the staging (a host matrix is staged in chunks of
+ * SNP rows, 256 MiB or MXA_ASSOC_CHUNK_ROWS rows each: each chunk is scanned, then appended to the packed object, so the raw matrix is never resident as a
+ * whole).  They are NOT promised bit-identical between different n (or k): the product's narrow-n routes use different arithmetic.
+ * mxa_assoc_basis (host only, no device needed): centres the q columns of W (indiv x q, ldw >= indiv), orthonormalises them in place order by Gram-Schmidt
+ *   applied twice and writes Q (indiv x q, ldq >= indiv).  Errors (return 1, mxa_last_error() == 1, Q untouched): NULL pointers, indiv < 1, q < 0, ldw or ldq
+ *   below indiv, a non-finite entry, a column whose norm after the two passes is at most indiv 2^-52 times its centred norm (constant or dependent; the
+ *   message names it).
+ * mxa_assoc_linear: beta, se, tstat: snps x n column-major, ldo >= snps; each optional, at least one required, those given all host or all device pointers;
+ *   nothing is written beyond row snps - 1 of a column or beyond column n - 1.  nobs (optional, snps ints, host or device) receives N; dof (optional, host)
+ *   receives indiv - k - 2.  plink, Y and Q are host or device pointers, each independently.  Errors (return 1, mxa_last_error() == 1, outputs untouched, all
+ *   decided before a device is selected): NULL plink or Y; snps, indiv or n below 1; k < 0; n + k > 65535; Q == NULL with k > 0; a leading dimension too small;
+ *   indiv - k - 2 < 1; indiv > 47 453 132; all three result pointers NULL; mixed host and device result pointers.  12: not enough device memory (the packed
+ *   object, the staging chunk, B and its row-packed copy, the snps x (n + k) arrays D and M, device copies of host operands).  Runs on the selected device (no
+ *   MIRACULIX_NUM_GPUS sharding). */
+int mxa_assoc_basis(int indiv, const double *W, long ldw, int q, double *Q, long ldq);
+int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta, double *se,
+                     double *tstat, long ldo, int *nobs, int *dof);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

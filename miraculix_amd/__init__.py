@@ -11,5 +11,7 @@ from . import crossproduct  # noqa: F401
 from . import compressed_operations  # noqa: F401
 from . import read_plink  # noqa: F401
 from . import solve  # noqa: F401
+from . import assoc  # noqa: F401
 from .crossproduct import ld_prune, ld_prune_csr  # noqa: F401
+from .assoc import assoc_basis, assoc_linear  # noqa: F401
 from .lib import load_shared_library, set_library_path, check_library_handle  # noqa: F401

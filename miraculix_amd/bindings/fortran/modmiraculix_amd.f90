@@ -21,6 +21,7 @@ module modmiraculix_amd
  public :: mxa_ld_prune_csr, mxa_ld_window_prune, mxa_ld_window_prune_pairwise
  public :: mxa_ld_window_apply, mxa_ld_window_apply_pairwise
  public :: mxa_ld_op_bytes, mxa_ld_op_create, mxa_ld_op_create_pairwise, mxa_ld_op_from_rows, mxa_ld_op_rows, mxa_ld_op_apply, mxa_ld_op_solve, mxa_ld_op_free
+ public :: mxa_assoc_basis, mxa_assoc_linear
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -322,6 +323,23 @@ module modmiraculix_amd
    import c_ptr
    type(c_ptr), intent(inout) :: op
   end subroutine
+
+  ! association scan: beta, se, t of y_c ~ 1 + Q + x_s for every SNP s (missing calls imputed by the SNP's mean); Q from mxa_assoc_basis (host only), or
+  ! c_null_ptr with k = 0; beta, se, tstat: snps x n, ld ldo, each c_loc or c_null_ptr (one at least); nobs: snps ints or c_null_ptr; dof: c_loc of one int or c_null_ptr
+  function mxa_assoc_basis(indiv, W, ldw, ncov, Q, ldq) bind(C, name='mxa_assoc_basis') result(rc)   ! ncov: the header's q (Fortran does not tell q from Q)
+   import c_int, c_long, c_ptr
+   integer(c_int), value, intent(in) :: indiv, ncov
+   type(c_ptr), value, intent(in) :: W, Q
+   integer(c_long), value, intent(in) :: ldw, ldq
+   integer(c_int) :: rc
+  end function
+  function mxa_assoc_linear(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo, nobs, dof) bind(C, name='mxa_assoc_linear') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, Y, Q, beta, se, tstat, nobs, dof
+   integer(c_int), value, intent(in) :: snps, indiv, n, k
+   integer(c_long), value, intent(in) :: ldy, ldq, ldo
+   integer(c_int) :: rc
+  end function
 
   ! incremental staging: the object is filled by blocks of SNP rows (objects larger than any buffer the caller could hold)
   function mxa_plink2compressed_begin(snps, indiv, max_n, compressed) bind(C, name='mxa_plink2compressed_begin') result(rc)

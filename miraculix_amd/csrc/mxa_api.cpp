@@ -333,7 +333,9 @@ static int reserve_small_routes(Handle *h, int n) {
 }
 
 thread_local int tl_single_override = -1;
-thread_local bool tl_no_warmup = false;   // one-shot objects (dgemm_plink) skip the warm-up products
+thread_local bool tl_no_warmup = false;   // one-shot objects (dgemm_plink, mxa_assoc_linear) skip the warm-up products
+thread_local int tl_centered_override = -1;   // -1: options().centered; 0 / 1: this thread's products are uncentred / centred whatever setOptions_compressed said
+static bool product_centered() { return tl_centered_override >= 0 ? tl_centered_override != 0 : options().centered; }
 static thread_local bool tl_in_warmup = false;
 
 // First-call costs belong to plink2compressed, not to the first dgemm_compressed (round 6).  The phase clock of the reference's harness showed its FIRST product
@@ -539,7 +541,7 @@ int append_rows(Handle *h, const uint8_t *rows, long snp_begin, long nrows, cons
       if (sync_foreign_producer(src_dev)) return 1;
     }
     if (launch_recode(rows, (size_t)bps, snp_begin, nrows, h->indiv, 0, h->snp_major, s)) return 1;
-    if (!f_rows && launch_allele_freq(rows, nrows, h->indiv, h->d_f + snp_begin, s)) return 1;
+    if (!f_rows && h->has_f && launch_allele_freq(rows, nrows, h->indiv, h->d_f + snp_begin, s)) return 1;   // (has_f cleared: an object without frequencies, see mxa_internal.h)
     MXA_HIP(hipStreamSynchronize(s));   // the caller may reuse its block buffer
   } else {
     const size_t chunk_bytes = (size_t)256 << 20;
@@ -551,7 +553,7 @@ int append_rows(Handle *h, const uint8_t *rows, long snp_begin, long nrows, cons
       const long nr = std::min(chunk_rows, nrows - r0);
       if (!check_hip(hipMemcpyAsync(bounce, rows + (size_t)r0 * bps, (size_t)nr * bps, hipMemcpyHostToDevice, s), __func__, __LINE__)) { rc = 1; break; }
       rc = launch_recode(bounce, (size_t)bps, snp_begin + r0, nr, h->indiv, 0, h->snp_major, s);
-      if (!rc && !f_rows) rc = launch_allele_freq(bounce, nr, h->indiv, h->d_f + snp_begin + r0, s);
+      if (!rc && !f_rows && h->has_f) rc = launch_allele_freq(bounce, nr, h->indiv, h->d_f + snp_begin + r0, s);
       if (!rc && !check_hip(hipStreamSynchronize(s), __func__, __LINE__)) rc = 1;
     }
     (void)hipFree(bounce);
@@ -673,7 +675,7 @@ constexpr int kSmallNMaxColsHost = 6;   // widest product that takes the guarded
 static int gemm_device(Handle *h, bool trans, int n, const double *dB, long ldb, double *dC, long ldc, long fill_rows, hipStream_t s, bool timing = true) {
   const PackedMatrix &G = trans ? h->snp_major : h->ind_major;   // reference picks d_plink for 'T' (dgemm_compressed_cuda.cu:270)
   const long m = G.rows, k = G.k;
-  const bool centered = options().centered;
+  const bool centered = product_centered();
   if (centered && !h->has_f) { set_error(6, "dgemm_compressed: centring requested but no allele frequencies were supplied to plink2compressed"); return 1; }
   if (ldb < k || ldc < m) { set_error(7, "dgemm_compressed: leading dimension too small (ldb %ld < %ld or ldc %ld < %ld)", ldb, k, ldc, m); return 1; }
   if (fill_rows < m || fill_rows > ldc) { set_error(7, "internal: fill_rows %ld outside [%ld, %ld]", fill_rows, m, ldc); return 1; }
@@ -936,7 +938,7 @@ static int gemm_host_pipelined(Handle *h, bool trans, int n, const double *B, lo
   const size_t b_bytes = b_host ? sizeof(double) * (size_t)k * n : 0, c_bytes = c_host ? sizeof(double) * (size_t)m * n : 0;
   if (std::max(b_bytes, c_bytes) < kPipeMinBytes) return 2;
   const bool kmode = b_bytes >= c_bytes;
-  const bool centered = options().centered;
+  const bool centered = product_centered();
   if (centered && !h->has_f) { set_error(6, "dgemm_compressed: centring requested but no allele frequencies were supplied to plink2compressed"); return 1; }
   if (n > h->max_n) h->max_n = n;
   if (ensure_workspace(h, n) || pipe_setup(h)) return 1;

@@ -1,0 +1,381 @@
+// mxa_assoc.hip -- the association scan: per-SNP linear regression y_c ~ 1 + Q + x_s on packed genotypes (include/miraculix_amd.h: mxa_assoc_linear; DESIGN.md
+// 3.6e).  The fp64 product does the work: D = Z^T B for B = [Y~ | Q] is the library's own uncentred 'T' product on a one-shot object.  What the product cannot
+// know -- the missing calls -- comes from ONE streaming pass over the raw PLINK rows (k_assoc_scan): the exact counts N, c1, c2 of every SNP by popcount, and
+// M_b = the sum of b over the SNP's missing individuals.  k_assoc_finish turns D, M and the counts into beta, se and t in the documented operation order.
+#include <hip/hip_runtime.h>
+#include <cstdlib>
+#include <cstring>
+#include "../../include/miraculix_amd.h"
+#include "mxa_internal.h"
+#include "mxa_assoc_host.h"
+#include "mxa_xprod.h"
+
+namespace mxa {
+
+namespace {
+
+struct alignas(8 * kAssocCols) AssocRow { double v[kAssocCols]; };   // one individual's 16 columns of B: one aligned 128-byte run
+
+// ---- the sums of the phenotype preparation: 256 threads, thread t takes the individuals t, t + 256, ... in ascending order, then a fixed tree -- the wave's
+// shuffles (32, 16, ..., 1), then (w0 + w1) + (w2 + w3) through the LDS.  The order depends on indiv alone.
+__device__ __forceinline__ double assoc_block_sum(double v, double *red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  const double r = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return r;
+}
+
+// out[x + y ld_out] = sum_i A[i, a] B[i, y] with a = x (diag == 0) or a = y (diag != 0: the squared norms, launched with gridDim.x == 1); A == nullptr: the
+// column sums of B.  One workgroup per output.
+__global__ void __launch_bounds__(256) k_assoc_dots(const double *__restrict__ A, long lda, const double *__restrict__ B, long ldb, long indiv,
+                                                     double *__restrict__ out, int ld_out, int diag) {
+  __shared__ double red[4];
+  const double *b = B + (size_t)blockIdx.y * (size_t)ldb;
+  const double *a = A ? A + (size_t)(diag ? blockIdx.y : blockIdx.x) * (size_t)lda : nullptr;
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < indiv; i += 256) acc = a ? __fma_rn(a[i], b[i], acc) : acc + b[i];
+  const double s = assoc_block_sum(acc, red);
+  if (threadIdx.x == 0) out[(size_t)blockIdx.x + (size_t)blockIdx.y * (size_t)ld_out] = s;
+}
+
+// y[i, c] -= sum[c] / indiv
+__global__ void __launch_bounds__(256) k_assoc_center(double *__restrict__ Y, long ldy, long indiv, const double *__restrict__ sum) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= indiv) return;
+  const double mean = __ddiv_rn(sum[blockIdx.y], (double)indiv);
+  double *y = Y + (size_t)blockIdx.y * (size_t)ldy;
+  y[i] = __dsub_rn(y[i], mean);
+}
+
+// y[i, c] <- y[i, c] - sum_q Q[i, q] a[q, c]: the chain y = fma(-a[q, c], Q[i, q], y) over ascending q
+__global__ void __launch_bounds__(256) k_assoc_project(double *__restrict__ Y, long ldy, long indiv, const double *__restrict__ Q, long ldq, int k,
+                                                        const double *__restrict__ a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= indiv) return;
+  double *y = Y + (size_t)blockIdx.y * (size_t)ldy;
+  double v = y[i];
+  for (int q = 0; q < k; q++) v = __fma_rn(-a[q + (size_t)blockIdx.y * k], Q[(size_t)q * (size_t)ldq + i], v);
+  y[i] = v;
+}
+
+// the row-packed copy of B: chunk cc = blockIdx.y holds the columns [16 cc, 16 cc + 16) of every individual as one AssocRow (columns beyond ncols: zeros),
+// as k_ld_op_pack does for X
+__global__ void __launch_bounds__(256) k_assoc_pack(const double *__restrict__ B, long ldb, int ncols, long indiv, AssocRow *__restrict__ bp) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= indiv) return;
+  const int c0 = (int)blockIdx.y * kAssocCols;
+  AssocRow r;
+#pragma unroll
+  for (int c = 0; c < kAssocCols; c++) r.v[c] = c0 + c < ncols ? B[(size_t)(c0 + c) * (size_t)ldb + i] : 0.0;
+  bp[(size_t)blockIdx.y * (size_t)indiv + i] = r;
+}
+
+// ---- the scan: one workgroup per SNP row blk0 + blockIdx.x of `rows` (compact pitch bps = ceil(indiv / 4)).  The row is cut into logical words of 16 bytes
+// = 64 genotypes, counted from the row's first byte; thread t takes the words t, t + 256, ... in ascending order, two in flight.  Every word is read with
+// 16-byte loads whatever the row's address: a row that starts `sh` bytes behind a 16-byte boundary takes the two aligned words its logical word lies in and
+// shifts them together (assoc_load_word) -- the same logical word, so the same sums, for every alignment.  Fields at and beyond indiv are
+// masked to 00 (N counts what is left: indiv - #01).  With H = (w >> 1) & 0x55.., L = w & 0x55..: 01 = L & ~H, 10 = H & ~L, 11 = H & L, counted by popcount;
+// for every 01 field the individual's packed row of B is added to the thread's 16 accumulators, ascending individual.  Reduction: the wave's shuffles, then
+// (w0 + w1) + (w2 + w3) through the LDS: nothing in the order depends on the data or the launch.  A row without any 01 stores zeros without reducing (the
+// sum of zeros).  first != 0: this launch also stores the counts.  *flag is raised when a 01 was seen.
+struct AssocWord { unsigned long long lo, hi; };
+
+// Logical word w of a row: its bytes [16 w, 16 w + 16) below bps, the rest zero.  Only aligned 16-byte words that hold at least one byte of the row are
+// loaded: such a word lies in the page of that byte, so nothing unmapped is touched even where it reaches before the first row or behind the last one.
+__device__ __forceinline__ AssocWord assoc_load_word(const uint8_t *__restrict__ row, long w, long bps, int sh) {
+  const long b0 = 16 * w, nb = bps - b0;                          // nb >= 1 bytes of the row from b0 on
+  const uint4 *a = reinterpret_cast<const uint4 *>(row + b0 - sh);
+  const uint4 x = a[0];
+  uint4 y = make_uint4(0u, 0u, 0u, 0u);
+  if (sh && 16 - sh < nb) y = a[1];                               // the logical word reaches into the next aligned one
+  const unsigned long long q0 = (unsigned long long)x.x | ((unsigned long long)x.y << 32), q1 = (unsigned long long)x.z | ((unsigned long long)x.w << 32);
+  const unsigned long long q2 = (unsigned long long)y.x | ((unsigned long long)y.y << 32), q3 = (unsigned long long)y.z | ((unsigned long long)y.w << 32);
+  const bool big = sh >= 8;
+  const int s8 = 8 * (sh & 7);
+  const unsigned long long A = big ? q1 : q0, B = big ? q2 : q1, C = big ? q3 : q2;
+  AssocWord r;
+  r.lo = s8 ? (A >> s8) | (B << (64 - s8)) : A;
+  r.hi = s8 ? (B >> s8) | (C << (64 - s8)) : B;
+  if (nb < 16) {                                                  // the row ends inside this word: what follows belongs to the next row, or to nobody
+    if (nb <= 8) { r.hi = 0ull; if (nb < 8) r.lo &= (1ull << (8 * nb)) - 1ull; }
+    else r.hi &= (1ull << (8 * (nb - 8))) - 1ull;
+  }
+  return r;
+}
+
+__device__ __forceinline__ void assoc_half(unsigned long long x, long fbase, long indiv, const AssocRow *__restrict__ bp, double (&acc)[kAssocCols], int &n01, int &n10,
+                                           int &n11) {
+  const long valid = indiv - fbase;
+  if (valid <= 0) return;
+  if (valid < 32) x &= (1ull << (2 * valid)) - 1ull;
+  const unsigned long long L = x & 0x5555555555555555ull, H = (x >> 1) & 0x5555555555555555ull;
+  unsigned long long miss = L & ~H;
+  n01 += __popcll(miss);
+  n10 += __popcll(H & ~L);
+  n11 += __popcll(H & L);
+  while (miss) {
+    const int bit = __ffsll((long long)miss) - 1;
+    const double2 *p = reinterpret_cast<const double2 *>(bp + (fbase + (bit >> 1)));
+#pragma unroll
+    for (int j = 0; j < kAssocCols / 2; j++) { const double2 v = p[j]; acc[2 * j] += v.x; acc[2 * j + 1] += v.y; }
+    miss &= miss - 1ull;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_assoc_scan(const uint8_t *__restrict__ rows, long bps, long indiv, long row0, const AssocRow *__restrict__ bp, int c0,
+                                                     int ncols, double *__restrict__ M, long ldm, int *__restrict__ nobs, int *__restrict__ c1,
+                                                     int *__restrict__ c2, int first, int *__restrict__ flag, long blk0) {
+  __shared__ double red[4][kAssocCols];
+  __shared__ int redi[4][3];
+  const long r = blk0 + blockIdx.x;
+  const uint8_t *row = rows + (size_t)r * (size_t)bps;
+  const int sh = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+  const long nwords = (bps + 15) / 16;
+  double acc[kAssocCols];
+#pragma unroll
+  for (int j = 0; j < kAssocCols; j++) acc[j] = 0.0;
+  int n01 = 0, n10 = 0, n11 = 0;
+  for (long w = threadIdx.x; w < nwords; w += 512) {
+    const AssocWord a = assoc_load_word(row, w, bps, sh);
+    AssocWord b = {0ull, 0ull};
+    if (w + 256 < nwords) b = assoc_load_word(row, w + 256, bps, sh);
+    assoc_half(a.lo, 64 * w, indiv, bp, acc, n01, n10, n11);
+    assoc_half(a.hi, 64 * w + 32, indiv, bp, acc, n01, n10, n11);
+    assoc_half(b.lo, 64 * (w + 256), indiv, bp, acc, n01, n10, n11);
+    assoc_half(b.hi, 64 * (w + 256) + 32, indiv, bp, acc, n01, n10, n11);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int any = __syncthreads_or(n01 != 0);
+  if (first) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { n01 += __shfl_down(n01, off, 64); n10 += __shfl_down(n10, off, 64); n11 += __shfl_down(n11, off, 64); }
+    if (lane == 0) { redi[wave][0] = n01; redi[wave][1] = n10; redi[wave][2] = n11; }
+  }
+  if (any) {
+#pragma unroll
+    for (int j = 0; j < kAssocCols; j++) {
+      double v = acc[j];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+      if (lane == 0) red[wave][j] = v;
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < kAssocCols && c0 + t < ncols) M[(size_t)(c0 + t) * (size_t)ldm + (size_t)(row0 + r)] = any ? (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]) : 0.0;
+  if (first && t >= 64 && t < 67) {
+    const int q = t - 64, s = (redi[0][q] + redi[1][q]) + (redi[2][q] + redi[3][q]);
+    if (q == 0) nobs[row0 + r] = (int)indiv - s;
+    else if (q == 1) c1[row0 + r] = s;
+    else c2[row0 + r] = s;
+  }
+  if (any && t == 128) *flag = 1;
+}
+
+// ---- the epilogue: one thread per (SNP, phenotype), every operation rounded once in the header's order
+__global__ void __launch_bounds__(256) k_assoc_finish(long snps, int n, int k, const int *__restrict__ nobs, const int *__restrict__ c1, const int *__restrict__ c2,
+                                                       const double *__restrict__ D, const double *__restrict__ M, long ld, const double *__restrict__ T,
+                                                       const double *__restrict__ syy, double dof, double *__restrict__ beta, double *__restrict__ se,
+                                                       double *__restrict__ tstat, long ldo, long blk0) {
+  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
+  if (idx >= snps * (long)n) return;
+  const long s = idx % snps;
+  const int c = (int)(idx / snps);
+  const long N = nobs[s], a1 = c1[s], a2 = c2[s];
+  const long Sz = a1 + 2 * a2, Szz = a1 + 4 * a2;
+  const double dN = (double)N;
+  const double mu = __ddiv_rn((double)Sz, dN);
+  const double v0 = __ddiv_rn((double)(N * Szz - Sz * Sz), dN);
+  double sxx = v0;
+  for (int q = 0; q < k; q++) {
+    const size_t at = (size_t)s + (size_t)(n + q) * (size_t)ld;
+    const double g = __fma_rn(mu, __dsub_rn(M[at], T[n + q]), D[at]);
+    sxx = __fma_rn(-g, g, sxx);
+  }
+  const size_t at = (size_t)s + (size_t)c * (size_t)ld;
+  const double g = __fma_rn(mu, __dsub_rn(M[at], T[c]), D[at]);
+  const double b = __ddiv_rn(g, sxx);
+  const double rss = __fma_rn(-b, g, syy[c]);
+  const double e = __dsqrt_rn(__ddiv_rn(__ddiv_rn(rss, dof), sxx));
+  const size_t o = (size_t)s + (size_t)c * (size_t)ldo;
+  if (beta) beta[o] = b;
+  if (se) se[o] = e;
+  if (tstat) tstat[o] = __ddiv_rn(b, e);
+}
+
+// ---- host side
+struct HandleHolder {                // the one-shot object is released on every exit path
+  Handle *h = nullptr;
+  ~HandleHolder() { if (h) destroy_handle(h); }
+};
+struct OneShotScope {                // this thread's products: single orientation, no warm-up, uncentred -- for the length of the call
+  int single = tl_single_override, centered = tl_centered_override;
+  bool no_warmup = tl_no_warmup;
+  OneShotScope() { tl_single_override = 1; tl_no_warmup = true; tl_centered_override = 0; }
+  ~OneShotScope() { tl_single_override = single; tl_no_warmup = no_warmup; tl_centered_override = centered; }
+};
+
+// rows of one staging chunk of a host matrix: MXA_ASSOC_CHUNK_ROWS, else what fits 256 MiB
+long assoc_chunk_rows(long snps, long bps) {
+  long rows = std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)bps));
+  const char *e = getenv("MXA_ASSOC_CHUNK_ROWS");
+  if (e && atol(e) > 0) rows = atol(e);
+  return std::min(rows, snps);
+}
+
+// *seen (host): a 01 field was met in an earlier pass; while it is clear the device flag is read once per call of this function, afterwards never again
+int scan_rows(const uint8_t *d_rows, long bps, long indiv, long row0, long nrows, const AssocRow *d_bp, int ncols, int ncc, double *d_M, long snps, int *d_cnt,
+              int *d_flag, bool *seen, hipStream_t s) {
+  for (int cc = 0; cc < ncc; cc++) {
+    if (cc == 1 && !*seen) {   // no missing call so far: M is zero (it was cleared) and the further column chunks need no pass
+      int flag = 0;
+      MXA_HIP(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+      MXA_HIP(hipStreamSynchronize(s));
+      if (!flag) break;
+      *seen = true;
+    }
+    launch_in_block_chunks(nrows, [&](unsigned nb, long b0) {
+      k_assoc_scan<<<nb, 256, 0, s>>>(d_rows, bps, indiv, row0, d_bp + (size_t)cc * (size_t)indiv, cc * kAssocCols, ncols, d_M, snps, d_cnt, d_cnt + snps,
+                                      d_cnt + 2 * snps, cc == 0, d_flag, b0);
+    });
+    MXA_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int assoc_linear(const unsigned char *plink, long snps, long indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta, double *se,
+                 double *tstat, long ldo, int *nobs, int *dof, bool out_dev) {
+  const char *who = "mxa_assoc_linear";
+  const int dev = select_device();
+  if (dev < 0) return 1;
+  const int ncols = n + k, ncc = (ncols + kAssocCols - 1) / kAssocCols, max_n = std::min(ncols, 32);
+  const long bps = (indiv + 3) / 4;
+  int p_dev = -1;
+  const bool in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;   // rows in this device's memory are scanned where they lie
+  const long chunk_rows = in_place ? snps : assoc_chunk_rows(snps, bps);
+  // ---- memory pre-flight: the packed object, the staging chunk, B and its row-packed copy, D and M, the counts, the device copies of host results
+  const size_t b_bytes = sizeof(double) * (size_t)indiv * (size_t)ncols, bp_bytes = sizeof(AssocRow) * (size_t)indiv * (size_t)ncc;
+  const size_t dm_bytes = sizeof(double) * (size_t)snps * (size_t)ncols, cnt_bytes = sizeof(int) * 3 * (size_t)snps;
+  const size_t out_bytes = sizeof(double) * (size_t)snps * (size_t)n, bounce_bytes = in_place ? 0 : (size_t)chunk_rows * (size_t)bps;
+  const int n_out = (beta != nullptr) + (se != nullptr) + (tstat != nullptr);
+  const size_t need = object_footprint(snps, indiv, max_n, true) + bounce_bytes + b_bytes + bp_bytes + 2 * dm_bytes + cnt_bytes + (out_dev ? 0 : n_out * out_bytes);
+  size_t free_b = 0, total_b = 0;
+  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu MB, free %zu MB", who, need >> 20, free_b >> 20); return 1; }
+
+  OneShotScope scope;
+  HandleHolder obj;
+  { void *o = nullptr; if (begin_handle(snps, indiv, max_n, &o, dev)) return 1; obj.h = reinterpret_cast<Handle *>(o); }
+  Handle *h = obj.h;
+  hipStream_t s = h->stream;
+  XBuf bB, bBp, bD, bM, bCnt, bSmall, bFlag, bounce, bOut[3];
+  const size_t small_doubles = (size_t)ncols + (size_t)n + (size_t)n + (size_t)k * (size_t)n;   // T, syy, column sums, a = Q^T y
+  if (bB.alloc(b_bytes) || bBp.alloc(bp_bytes) || bD.alloc(dm_bytes) || bM.alloc(dm_bytes) || bCnt.alloc(cnt_bytes) || bSmall.alloc(sizeof(double) * small_doubles) ||
+      bFlag.alloc(sizeof(int)) || (!in_place && bounce.alloc(bounce_bytes))) return 1;
+  double *out_d[3] = {beta, se, tstat};
+  if (!out_dev)
+    for (int j = 0; j < 3; j++)
+      if (out_d[j]) { if (bOut[j].alloc(out_bytes)) return 1; out_d[j] = (double *)bOut[j].p; }
+  double *dB = (double *)bB.p, *dD = (double *)bD.p, *dM = (double *)bM.p;
+  double *dT = (double *)bSmall.p, *dSyy = dT + ncols, *dSum = dSyy + n, *dA = dSum + n;
+  int *dCnt = (int *)bCnt.p, *dFlag = (int *)bFlag.p;
+  AssocRow *dBp = (AssocRow *)bBp.p;
+
+  // ---- B = [Y~ | Q] on the device
+  const size_t col = sizeof(double) * (size_t)indiv;
+  MXA_HIP(hipMemcpy2DAsync(dB, col, Y, sizeof(double) * (size_t)ldy, col, (size_t)n, hipMemcpyDefault, s));
+  double *dQ = dB + (size_t)n * (size_t)indiv;
+  if (k > 0) MXA_HIP(hipMemcpy2DAsync(dQ, col, Q, sizeof(double) * (size_t)ldq, col, (size_t)k, hipMemcpyDefault, s));
+  const unsigned iblocks = (unsigned)((indiv + 255) / 256);
+  k_assoc_dots<<<dim3(1, n), 256, 0, s>>>(nullptr, 0, dB, indiv, indiv, dSum, 1, 0);
+  k_assoc_center<<<dim3(iblocks, n), 256, 0, s>>>(dB, indiv, indiv, dSum);
+  for (int pass = 0; pass < 2 && k > 0; pass++) {
+    k_assoc_dots<<<dim3(k, n), 256, 0, s>>>(dQ, indiv, dB, indiv, indiv, dA, k, 0);
+    k_assoc_project<<<dim3(iblocks, n), 256, 0, s>>>(dB, indiv, indiv, dQ, indiv, k, dA);
+  }
+  k_assoc_dots<<<dim3(1, n), 256, 0, s>>>(dB, indiv, dB, indiv, indiv, dSyy, 1, 1);
+  k_assoc_dots<<<dim3(1, ncols), 256, 0, s>>>(nullptr, 0, dB, indiv, indiv, dT, 1, 0);
+  k_assoc_pack<<<dim3(iblocks, ncc), 256, 0, s>>>(dB, indiv, ncols, indiv, dBp);
+  MXA_HIP(hipGetLastError());
+  MXA_HIP(hipMemsetAsync(dM, 0, dm_bytes, s));
+  MXA_HIP(hipMemsetAsync(dFlag, 0, sizeof(int), s));
+
+  // ---- the scan and the staging of the product operand, chunk by chunk.  The uncentred product needs no allele frequencies: the object is one without them
+  // (has_f cleared), which spares append_rows its own pass over the raw rows and makes a product that ignored tl_centered_override an error, not a result.
+  h->has_f = false;
+  bool seen_missing = false;
+  for (long r0 = 0; r0 < snps; r0 += chunk_rows) {
+    const long nr = std::min(chunk_rows, snps - r0);
+    const uint8_t *d_rows = plink + (size_t)r0 * (size_t)bps;
+    if (!in_place) {
+      MXA_HIP(hipMemcpyAsync(bounce.p, d_rows, (size_t)nr * (size_t)bps, hipMemcpyDefault, s));
+      d_rows = (const uint8_t *)bounce.p;
+    }
+    if (scan_rows(d_rows, bps, indiv, r0, nr, dBp, ncols, ncc, dM, snps, dCnt, dFlag, &seen_missing, s)) return 1;
+    if (append_rows(h, d_rows, r0, nr, nullptr)) return 1;
+  }
+  if (end_handle(h)) return 1;
+
+  // ---- D = Z^T B, in column chunks no wider than the object's max_n
+  for (int c0 = 0; c0 < ncols; c0 += max_n) {
+    const int w = std::min(max_n, ncols - c0);
+    if (gemm_any(h, true, w, dB + (size_t)c0 * (size_t)indiv, indiv, dD + (size_t)c0 * (size_t)snps, snps, snps, false, false)) return 1;
+  }
+  const long total = snps * (long)n;
+  launch_in_block_chunks((total + 255) / 256, [&](unsigned nb, long b0) {
+    k_assoc_finish<<<nb, 256, 0, s>>>(snps, n, k, dCnt, dCnt + snps, dCnt + 2 * snps, dD, dM, snps, dT, dSyy, (double)(indiv - k - 2), out_d[0], out_d[1], out_d[2],
+                                      out_dev ? ldo : snps, b0);
+  });
+  MXA_HIP(hipGetLastError());
+  if (!out_dev) {
+    double *host[3] = {beta, se, tstat};
+    const size_t ocol = sizeof(double) * (size_t)snps;
+    for (int j = 0; j < 3; j++)
+      if (host[j]) MXA_HIP(hipMemcpy2DAsync(host[j], sizeof(double) * (size_t)ldo, out_d[j], ocol, ocol, (size_t)n, hipMemcpyDeviceToHost, s));
+  }
+  if (nobs) MXA_HIP(hipMemcpyAsync(nobs, dCnt, sizeof(int) * (size_t)snps, hipMemcpyDefault, s));
+  MXA_HIP(hipStreamSynchronize(s));
+  if (dof) *dof = (int)(indiv - k - 2);
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace mxa
+
+extern "C" int mxa_assoc_basis(int indiv, const double *W, long ldw, int q, double *Q, long ldq) {
+  using namespace mxa;
+  clear_error();
+  const char *who = "mxa_assoc_basis";
+  if (indiv < 1 || q < 0) { set_error(1, "%s: indiv must be positive and q must not be negative", who); return 1; }
+  if (!W || !Q) { set_error(1, "%s: W and Q must not be NULL", who); return 1; }
+  if (ldw < indiv || ldq < indiv) { set_error(1, "%s: need ldw >= indiv and ldq >= indiv (ldw %ld, ldq %ld, indiv %d)", who, ldw, ldq, indiv); return 1; }
+  if (q == 0) return 0;
+  int bad = -1;
+  const int rc = assoc_basis_host(indiv, W, ldw, q, Q, ldq, &bad);
+  if (rc == 2) { set_error(1, "%s: column %d of W holds a non-finite entry", who, bad); return 1; }
+  if (rc == 3) { set_error(1, "%s: column %d of W is constant or depends on the columns before it", who, bad); return 1; }
+  return 0;
+}
+
+extern "C" int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta,
+                                double *se, double *tstat, long ldo, int *nobs, int *dof) {
+  using namespace mxa;
+  clear_error();
+  const char *who = "mxa_assoc_linear";
+  const char *bad = assoc_linear_args(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo);
+  if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
+  int given = 0, on_dev = 0;
+  for (const double *p : {(const double *)beta, (const double *)se, (const double *)tstat})
+    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
+  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: beta, se and tstat must be all host or all device pointers", who); return 1; }
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  const int rc = assoc_linear(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo, nobs, dof, on_dev != 0);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  return rc;
+}

@@ -96,7 +96,7 @@ struct Handle {
   std::vector<std::pair<long, long>> staged_iv;   // disjoint [begin, end) blocks appended so far, sorted
   double *d_f = nullptr;     // snps
   double *h_f = nullptr;
-  bool has_f = false;
+  bool has_f = false;        // begin_handle sets it; a caller that clears it before append_rows gets an object WITHOUT frequencies: no block is counted, and a centred product is refused (error 6)
   int max_n = 0;
   Workspace ws;
   hipStream_t stream = nullptr;
@@ -136,6 +136,10 @@ int create_handle(const uint8_t *plink, size_t plink_pitch, const uint8_t *plink
 int single_orientation_policy();
 size_t object_footprint(long snps, long indiv, int max_n, bool single);   // device bytes of a staged object: packed copies (tile padding included) + workspace
 extern thread_local int tl_single_override;
+extern thread_local bool tl_no_warmup;          // one-shot objects skip the warm-up products of create_handle / end_handle
+// the centring of this thread's products, read next to options().centered: -1 = what setOptions_compressed said, 0 = uncentred, 1 = centred.  mxa_assoc_linear
+// needs the raw sums sum_i z_i b_i and sets 0 around its products; the process-wide Options are never rewritten.
+extern thread_local int tl_centered_override;
 void destroy_handle(Handle *h);
 // incremental staging of a single-orientation object: allocate (packed SNP-major matrix zeroed, workspace), then SNP-row blocks in any order, then seal.
 // rows: compact PLINK rows (pitch ceil(indiv/4)), host or device; f_rows nullable: the block's frequencies are then counted on the device (k_allele_freq).

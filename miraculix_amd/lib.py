@@ -143,6 +143,11 @@ def load_shared_library():
     L.mxa_ld_op_solve.restype = ctypes.c_int
     L.mxa_ld_op_free.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
     L.mxa_ld_op_free.restype = None
+    L.mxa_assoc_basis.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.mxa_assoc_basis.restype = ctypes.c_int
+    L.mxa_assoc_linear.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]
+    L.mxa_assoc_linear.restype = ctypes.c_int
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

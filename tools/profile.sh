@@ -20,6 +20,8 @@
 #   ld-prune [snps indiv window min_r2 reps]   LD pruning / clumping on the device (mxa_ld_window_prune, mxa_ld_prune_csr): products, select passes, rounds, owner pass; three priorities; against ld_pairs + the walk on the host
 #   ld-apply [snps indiv window reps]   the window applied to a matrix (mxa_ld_window_apply), n in {1, 16, 64}, against mxa_ld_window_scores and against mxa_ld_window_rows + a device band product in torch, one process, both engines
 #   ld-op [snps indiv window reps]   the LD operator object (mxa_ld_op_*): creation against mxa_ld_window_rows, apply at n in {1, 16, 64} against mxa_ld_window_apply with the byte model, a 50-iteration solve, one process
+#   assoc [snps indiv reps]   the association scan (mxa_assoc_linear) at n = 1, k = 15 and n = 16, k = 16, without and with 5 % missing calls, against the bare 'T' product of n + k columns on a resident object, one process
+#   assoc-kernels [snps indiv]   the library kernels inside mxa_assoc_linear, one by one: tools/perf_assoc.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -132,6 +134,16 @@ ld-op)
   # whole-call times of creation, apply and solve against the entries that redo the products, alternating calls; the text is what profiles/r14_ld_op.txt holds
   timeout -k 10 900 python3 tools/perf_ld_op.py ${1:-1000000} ${2:-50000} ${3:-1023} ${4:-5} 2>&1 | tee "$O/ld_op.txt" || exit 1
   cp -f "$O/ld_op.txt" "$R/profiles/r14_ld_op.txt" ;;
+assoc)
+  # whole-call time of the scan per shape and data set beside the bare 'T' product of the same run, alternating calls; the text is what profiles/r15_assoc.txt holds
+  timeout -k 10 900 python3 tools/perf_assoc.py ${1:-1000000} ${2:-50000} ${3:-5} 2>&1 | tee "$O/assoc.txt" || exit 1
+  cp -f "$O/assoc.txt" "$R/profiles/r15_assoc.txt" ;;
+assoc-kernels)
+  # per-kernel times of the second call of each data set and shape; the text is what profiles/r15_assoc_kernels.txt holds
+  D="$O/assoc_trace"; rm -rf "$D"; mkdir -p "$D"
+  ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc.py" ${1:-1000000} ${2:-50000} trace > "$O/assoc_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_trace_run.log"; exit 1; }
+  f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc.py summarize "$f" 2>&1 | tee "$O/assoc_kernels.txt" || exit 1
+  rm -rf "$D"; cp -f "$O/assoc_kernels.txt" "$R/profiles/r15_assoc_kernels.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

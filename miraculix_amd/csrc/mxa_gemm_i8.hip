@@ -160,7 +160,7 @@ constexpr int kSmallNMaxCols = 6;             // columns of a guarded small-n ch
 // Plain form (tn = 0): thread <-> packed row, 32 bytes per slab of 128 genotypes; the entries of B are wave-uniform.
 // Transposed-operand form (tn = 1): thread <-> individual (a packed column), one byte per packed row; K runs over the rows.
 // n <= kSmallNMaxCols columns.  SLOW (measured late in round 5 on 500k x 50k: 44 ms ('T') / 198 ms ('N') at n = 4): since then only chains of ONE column use it (n = 1 and a peeled
-// single column, where verdict class 2 needs inf / NaN or a span beyond 201 binades); wider chains are followed by gated launches of the fp64 kernels (mxa_api.cpp: guarded_small).
+// single column, where verdict class 2 needs inf / NaN or a span beyond 201 binades); wider chains are followed by gated launches of the fp64 kernels (mxa_product.cpp: guarded_small).
 struct SmallNFallback {
   const uint8_t *G;                 // nullptr: no fallback in this launch
   long nslabs, m, k;
@@ -1194,8 +1194,12 @@ int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_t
 }
 
 int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, long ldb, double *dC, long ldc, long fill_rows, bool centered, double *d_sumB,
-                   double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int *splits_out, int guard,
-                   const int **flag_out, double *colsum_scratch, int S_override, const PackedMatrix *G_tn, double *stats_part, const I8Chain *chain) {
+                   double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, const I8Opts &o) {
+  hipEvent_t ev0 = o.ev0, ev1 = o.ev1;
+  int *splits_out = o.splits_out, guard = o.guard, S_override = o.S_override;
+  const int **flag_out = o.flag_out;
+  double *colsum_scratch = o.colsum_scratch, *stats_part = o.stats_part;
+  const PackedMatrix *G_tn = o.G_tn; const I8Chain *chain = o.chain;
   const long m = G.rows, k = G.k;
   I8Chain ch1;
   if (guard == 2) {   // device-side verdict: this launch sequence is the chain of one class

@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <atomic>
 #include <cstdint>
 #include <functional>
+#include <mutex>
 #include <utility>
 #include <vector>
 #include "mxa_plan.h"
@@ -38,6 +40,7 @@ struct Options {
 };
 Options &options();
 int env_print_level();
+void print_compile_info(const char *what);   // the banner of the reference, once per process
 
 // One packed, recoded genotype matrix resident in HBM: `rows` rows of `k` genotypes, 2 bits each holding the
 // allele count z in {0,1,2} (PLINK code 01 "missing" already mapped to 0), zero padded to rows_pad x k_pad.
@@ -84,7 +87,7 @@ struct Handle {
   int device = 0;
   long snps = 0, indiv = 0;
   PackedMatrix snp_major;    // rows = snps,  k = indiv
-  PackedMatrix ind_major;    // rows = indiv, k = snps.  Every product can be computed from either copy (mxa_api.cpp: gemm_use_tr).
+  PackedMatrix ind_major;    // rows = indiv, k = snps.  Every product can be computed from either copy (mxa_product.cpp: gemm_use_tr).
   // Single-orientation object (MXA_SINGLE_ORIENTATION=1 at plink2compressed, or by itself when two copies do not fit the device; round 4): only the SNP-major copy exists -- half the HBM, half the staging.
   // ind_major then holds the DIMENSIONS of the missing copy (for the launch plans) with d == nullptr; 'T' products run in the plain form, 'N' products in the
   // transposed-operand forms (k_gemm<..., TR>, k_gemm_i8_tn), both on snp_major.
@@ -109,7 +112,7 @@ struct Handle {
   bool in_pending = false, out_pending = false;
   ObjectProfile prof;                        // per object, next to the process-wide profile()
   double prof_last_kernel_ms = 0.0, prof_last_in_ms = 0.0, prof_last_out_ms = 0.0;   // the most recent harvested durations (phase clock line)
-  // host-operand pipeline (mxa_api.cpp: gemm_host_pipelined): two compute streams for alternating chunks, events per chunk
+  // host-operand pipeline (mxa_product.cpp: gemm_host_pipelined): two compute streams for alternating chunks, events per chunk
   hipStream_t pipe[2] = {nullptr, nullptr};
   hipEvent_t pev[18] = {};                   // [0] start, [1] operands ready, [2..9] upload of chunk c, [10..17] chunk c computed
 };
@@ -125,8 +128,13 @@ Profile &profile();
 // path: 0 k_gemm, 1 k_lut, 2 k_gemm_i8, 4 decided on the device (flag != 0: k_lut, else k_gemm_i8; resolved by mxa_last_path())
 struct Geometry { long m = 0, k = 0; int n = 0, splits = 0, a = 0, c = 0, path = 0; const int *d_flag = nullptr; int flag_dev = 0; };
 Geometry &last_geometry();
+// process-wide state of mxa_api.cpp that the other host units read
+extern std::mutex g_prof_mutex;       // guards profile() / last_geometry(): the worker threads of multi-device objects write them too
+extern std::atomic<int> g_engine;     // multiply engine (mxa_set_engine)
+extern bool g_profile_on;
 
-// ---- host-side engine entry points shared by mxa_api.cpp (single device) and mxa_multi.cpp (SNP shards over several devices)
+// ---- host-side engine entry points: staging in mxa_stage.cpp, products in mxa_product.cpp; shared by mxa_api.cpp (single device) and mxa_multi.cpp (SNP shards
+// over several devices)
 // device < 0: taken from HIP_DEVICE / CUDA_DEVICE / the current device
 int create_handle(const uint8_t *plink, size_t plink_pitch, const uint8_t *plink_t, size_t plink_t_pitch, long snps, long indiv,
                   const double *f, int max_n, void **out, int device = -1);
@@ -146,6 +154,12 @@ void destroy_handle(Handle *h);
 int begin_handle(long snps, long indiv, int max_n, void **out, int device = -1);
 int append_rows(Handle *h, const uint8_t *rows, long snp_begin, long nrows, const double *f_rows);
 int end_handle(Handle *h);
+// the workspace of the products of n columns; the int8 workspace of the guarded route; the warm-up products of a new object (mxa_product.cpp, called when an
+// object is made or sealed)
+int ensure_workspace(Handle *h, int n);
+int reserve_small_routes(Handle *h, int n);
+int warm_up(Handle *h, bool host_caller);
+int refuse_while_staging(const Handle *h, const char *who);   // error 19 while the object is between _begin and _end
 // pointer classification: 0 = host, 1 = device / managed memory (its device in *dev)
 int ptr_location(const void *p, int *dev);
 // One product on one device object, operands anywhere: B (k x n, ld ldb) and C (m x n, ld ldc) may be host memory, memory of this
@@ -154,6 +168,8 @@ int ptr_location(const void *p, int *dev);
 // of a 'T' product passes its own row count so that it does not touch its neighbours' rows).  Asynchronous on the object's stream
 // unless sync; with timing the caller reads the events later with harvest_profile().
 int gemm_any(Handle *h, bool trans, int n, const double *B, long ldb, double *C, long ldc, long fill_rows, bool sync, bool timing);
+// the same product with both operands in the memory of the object's device; asynchronous on s.  With timing, ev0 / ev1 bracket the dominant kernel.
+int gemm_device(Handle *h, bool trans, int n, const double *dB, long ldb, double *dC, long ldc, long fill_rows, hipStream_t s, bool timing = true);
 int gram_any(Handle *h, int n, const double *V, long ldv, double *out, long ldo, bool sync);
 void harvest_profile(Handle *h);
 // B / V lives in the memory of device `src_dev` != the current one: whatever the caller enqueued on that device's default stream (the
@@ -225,36 +241,42 @@ int launch_colspan(const double *dB, long ldb, long k, int n, double *d_part, in
 int launch_colexp_from_part(const double *d_part, int n, int *d_E, int bias, hipStream_t s);
 int launch_colexp(const double *dB, long ldb, long k, int n, double *d_part, int *d_E, int bias, hipStream_t s, int *d_flag = nullptr, int max_span = 0,
                   int min_emax = 0, bool reset_flag = true);
-// d_E (nullable): per-column exponents for the denormal-operand mode
-// K-steps (16 genotypes) [S0, S0 + S_cnt) only; S_cnt < 0: to the end
-// run_if_set (nullable, device int): the kernel does nothing unless *run_if_set != 0
-int launch_pack_B(const double *dB, long ldb, long k, int n, double *dBp, long k_pad, int n_pad, int c, hipStream_t s, const int *d_E = nullptr, long S0 = 0,
-                  long S_cnt = -1, const int *run_if_set = nullptr, bool rowscale = false);
+// The optional arguments of launch_pack_B / launch_gemm / launch_finish / gemm_i8_device are aggregates with defaulted members: a call names what it sets.
+struct PackOpts {
+  const int *d_E = nullptr;          // per-column exponents for the denormal-operand mode
+  long S0 = 0, S_cnt = -1;           // K-steps (16 genotypes) [S0, S0 + S_cnt) only; S_cnt < 0: to the end
+  const int *run_if_set = nullptr;   // device int: the kernel does nothing unless *run_if_set != 0
+  bool rowscale = false;             // B rows pre-scaled for the v_and_b32 conversion (MODE 3, plain form)
+};
+int launch_pack_B(const double *dB, long ldb, long k, int n, double *dBp, long k_pad, int n_pad, int c, hipStream_t s, const PackOpts &o = {});
 int launch_colsums(const double *dB, long ldb, long k, int n, const double *d_f /*nullable*/, double *d_part,
                    double *d_sumB, double *d_sumfB, hipStream_t s);
 // ksplits_like: take the K pieces of another plan (row ranges of one product: identical sums)
 GemmPlan plan_gemm(long m, long k_pad, int n, const GemmPlan *ksplits_like = nullptr);
 // conversion variant of k_gemm for a tile of c column groups: 2 (v_bfe_u32) or 3 (v_and_b32 + B rows pre-scaled); MXA_GEMM_MODE overrides
 int gemm_default_mode(int c);
-// K splits [split_begin, split_end) only (split_end < 0: all)
-// run_if_set (nullable, device int; MODE 0 only): the kernel does nothing unless *run_if_set != 0 (fallback of the denormal-operand mode)
+struct GemmOpts {
+  int split_begin = 0, split_end = -1;   // K splits [split_begin, split_end) only (split_end < 0: all)
+  const int *run_if_set = nullptr;       // device int, MODE 0 only: the kernel does nothing unless *run_if_set != 0 (fallback of the denormal-operand mode)
+  bool tr = false;                       // transposed operand (k_gemm<..., TR>): the output rows are G's COLUMNS (p planned for m = G.k) and K runs over G's rows -- the 'N' product from the SNP-major copy; modes 0 and 2 only
+  int p_split0 = 0;                      // the K split whose partial sums land at dP (grouped K splits keep one GROUP of splits in the buffer: the group's first split; the host-operand pipeline addresses the whole buffer: 0)
+};
 // d_ctr: 9 ints of device memory for the work queues of this launch (zeroed here, on s); must not be shared with a launch that may run at the same time
-// tr: transposed operand (k_gemm<..., TR>): the output rows are G's COLUMNS (p planned for m = G.k) and K runs over G's rows -- the 'N' product from the
-// SNP-major copy; modes 0 and 2 only
-// p_split0: the K split whose partial sums land at dP (grouped K splits keep one GROUP of splits in the buffer: p_split0 = the group's first split;
-// the host-operand pipeline addresses the whole buffer: 0)
-int launch_gemm(const PackedMatrix &G, const double *dBp, double *dP, const GemmPlan &p, int mode, hipStream_t s, int *d_ctr, int split_begin = 0, int split_end = -1,
-                const int *run_if_set = nullptr, bool tr = false, int p_split0 = 0);
+int launch_gemm(const PackedMatrix &G, const double *dBp, double *dP, const GemmPlan &p, int mode, hipStream_t s, int *d_ctr, const GemmOpts &o = {});
 GemmPlan plan_lut(long m, long k_pad, int n);
 // run_if_set (nullable, device int): the kernel does nothing unless *run_if_set != 0 (fallback of the guarded small-n route)
 int launch_lut(const PackedMatrix &G, const double *dB, long ldb, int n, double *dP, const GemmPlan &p, hipStream_t s, const int *run_if_set = nullptr);
+struct FinishOpts {
+  const int *d_E = nullptr;               // per-column exponents of the denormal-operand mode: the scale-back
+  int e_splits = 0, e_stride = 0;         // host-operand pipeline: every e_splits K splits have exponents of their own, e_stride ints apart in d_E (0: one set)
+  const int *run_if_set = nullptr;        // device int: the kernel does nothing unless *run_if_set != 0
+  const int *unscaled_if_set = nullptr;   // device int: when *unscaled_if_set != 0 the partial sums were produced WITHOUT the operand scaling (MODE 0 fallback): d_E is ignored
+  int group_splits = 0;                   // > 0: dP holds only that many splits (one GROUP of the plan's K splits)
+  int group = 0;                          // bit 0: continue the running sum kept in C, bit 1: not the last group -- the raw sum is stored (no scale-back, no centring).  See fp64_grouped (mxa_product.cpp).
+};
 // fill_rows: rows [m, fill_rows) of every column are zero-filled (fill_rows <= ldc)
 int launch_finish(const double *dP, const GemmPlan &p, long m, int n, double *dC, long ldc, long fill_rows, int mode_trans,
-                  bool centered, const double *d_sumB, const double *d_sumfB, const double *d_f, hipStream_t s, const int *d_E = nullptr, int e_splits = 0,
-                  int e_stride = 0, const int *run_if_set = nullptr, const int *unscaled_if_set = nullptr, int group_splits = 0, int group = 0);
-// group_splits > 0: dP holds only that many splits (one GROUP of the plan's K splits); group bit 0: continue the running sum kept in C, bit 1: not the
-// last group -- the raw sum is stored (no scale-back, no centring).  See gemm_grouped (mxa_api.cpp).
-// unscaled_if_set (nullable, device int): when *unscaled_if_set != 0 the partial sums were produced WITHOUT the operand scaling (MODE 0 fallback): d_E is ignored
+                  bool centered, const double *d_sumB, const double *d_sumfB, const double *d_f, hipStream_t s, const FinishOpts &o = {});
 // per-device one-time hipFuncSetAttribute(MaxDynamicSharedMemorySize): function attributes are per device, `mask` has one bit per device
 int ensure_dyn_lds(const void *func, int bytes, unsigned long long *mask);
 int launch_transpose_2bit(const uint8_t *d_in, long rows, long cols, uint8_t *d_out, hipStream_t s);
@@ -279,10 +301,18 @@ int launch_sparse_times_plink(const uint8_t *dP, size_t pitch, long entries, int
 // verdict is that class); `first`: this call also launches the statistics pass, publishes E, the column sums and the three flag words, and carries the fp64
 // chains of class 2 inside its k_slice_B launch.  The caller enqueues the chains of all classes back to back; nothing waits for the host.
 struct I8Chain { int S0 = 0, S1 = 0, my_class = 0; bool first = true; bool fp64_rows = true; };   // fp64_rows: verdict class 2 is served by the fp64 chains inside the first chain's k_slice_B launch (false: by gated launches of the caller)
+struct I8Opts {   // (the members are described above and below; splits_out: the K splits of the plan that ran)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int *splits_out = nullptr, guard = 0;
+  const int **flag_out = nullptr;
+  double *colsum_scratch = nullptr;
+  int S_override = 0;
+  const PackedMatrix *G_tn = nullptr;
+  double *stats_part = nullptr;
+  const I8Chain *chain = nullptr;
+};
 int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, long ldb, double *dC, long ldc, long fill_rows, bool centered, double *d_sumB,
-                   double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int *splits_out, int guard = 0,
-                   const int **flag_out = nullptr, double *colsum_scratch = nullptr, int S_override = 0, const PackedMatrix *G_tn = nullptr,
-                   double *stats_part = nullptr, const I8Chain *chain = nullptr);
+                   double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, const I8Opts &o = {});
 // workspace for a chain with S digits (0: the default of n), before anything is enqueued; 2: the transposed-operand form declines this tile count
 int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_tn, Workspace &w, hipStream_t s);
 // stats_part (guard = 0): the column maxima / minima of B are already there (k_colmax_partial's layout, 128 n doubles; the caller's launch_colspan made them to

@@ -216,8 +216,10 @@ int launch_colspan(const double *dB, long ldb, long k, int n, double *d_part, in
   return 0;
 }
 
-int launch_pack_B(const double *dB, long ldb, long k, int n, double *dBp, long k_pad, int n_pad, int c, hipStream_t s, const int *d_E, long S0, long S_cnt,
-                  const int *run_if_set, bool rowscale) {
+int launch_pack_B(const double *dB, long ldb, long k, int n, double *dBp, long k_pad, int n_pad, int c, hipStream_t s, const PackOpts &o) {
+  const int *d_E = o.d_E, *run_if_set = o.run_if_set;
+  long S0 = o.S0, S_cnt = o.S_cnt;
+  const bool rowscale = o.rowscale;
   const long S_total = k_pad / 16;
   if (S_cnt < 0) S_cnt = S_total - S0;
   const long total = S_cnt * (long)(n_pad / 4) * 64;
@@ -739,8 +741,10 @@ static int launch_gemm_t(const PackedMatrix &G, const double *dBp, double *dP, c
   return 0;
 }
 
-int launch_gemm(const PackedMatrix &G, const double *dBp, double *dP, const GemmPlan &p, int mode, hipStream_t s, int *d_ctr, int split_begin, int split_end,
-                const int *run_if_set, bool tr, int p_split0) {
+int launch_gemm(const PackedMatrix &G, const double *dBp, double *dP, const GemmPlan &p, int mode, hipStream_t s, int *d_ctr, const GemmOpts &o) {
+  int split_begin = o.split_begin, split_end = o.split_end, p_split0 = o.p_split0;
+  const int *run_if_set = o.run_if_set;
+  const bool tr = o.tr;
   if (split_end < 0) split_end = p.splits;
   if (p_split0 < 0 || p_split0 > split_begin) { set_error(4, "internal: k_gemm partial-sum base split %d outside [0, %d]", p_split0, split_begin); return 1; }
   if (!G.d) { set_error(4, "internal: k_gemm was given a packed matrix that is not stored (single-orientation object)"); return 1; }
@@ -1011,8 +1015,9 @@ __global__ void __launch_bounds__(256) k_finish(const double *__restrict__ P, lo
 }
 
 int launch_finish(const double *dP, const GemmPlan &p, long m, int n, double *dC, long ldc, long fill_rows, int mode_trans, bool centered,
-                  const double *d_sumB, const double *d_sumfB, const double *d_f, hipStream_t s, const int *d_E, int e_splits, int e_stride, const int *run_if_set,
-                  const int *unscaled_if_set, int group_splits, int group) {
+                  const double *d_sumB, const double *d_sumfB, const double *d_f, hipStream_t s, const FinishOpts &o) {
+  const int *d_E = o.d_E, *run_if_set = o.run_if_set, *unscaled_if_set = o.unscaled_if_set;
+  const int e_splits = o.e_splits, e_stride = o.e_stride, group_splits = o.group_splits, group = o.group;
   if ((p.p_rows & 1) || (p.m_pad & 1)) { set_error(4, "internal: k_finish wants even tile heights (p_rows %ld, m_pad %ld)", p.p_rows, p.m_pad); return 1; }
   int p_shift = -1;
   if ((p.p_rows & (p.p_rows - 1)) == 0) { p_shift = 0; while ((1L << p_shift) < p.p_rows) p_shift++; }

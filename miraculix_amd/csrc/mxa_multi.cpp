@@ -58,7 +58,7 @@ class Worker {
 
  private:
   void loop() {
-    mark_thread_concurrent();   // strided downloads issued from here take the per-column path (see copy_columns in mxa_api.cpp)
+    mark_thread_concurrent();   // strided downloads issued from here take the per-column path (see copy_columns in mxa_product.cpp)
     for (;;) {
       std::function<int()> job;
       {

@@ -1,6 +1,6 @@
 """Round 5: what BASELINE config 4 at its full 5M x 200k x 128 needs on ONE device, checked here at sizes the oracle finishes in seconds.
 
-(1) GROUPED K splits (mxa_api.cpp: partial_budget, gemm_device): a product whose split-K partial sums would not fit beside the packed matrix runs
+(1) GROUPED K splits (mxa_product.cpp: partial_budget, fp64_grouped): a product whose split-K partial sums would not fit beside the packed matrix runs
     its K splits in groups with the running sum kept in C.  Same pieces, same ascending order of additions: bit-identical to the one-pass product.
     MXA_P_BUDGET_MB (read per call) forces the grouped path on small products.
 (2) Incremental staging (mxa_plink2compressed_begin / _rows / _end): the object is allocated first and filled by SNP-row blocks (host or device

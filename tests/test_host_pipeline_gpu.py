@@ -1,4 +1,4 @@
-"""Host B / C through the plain ABI at sizes where the transfers are pipelined behind the product (mxa_api.cpp:
+"""Host B / C through the plain ABI at sizes where the transfers are pipelined behind the product (mxa_product.cpp:
 gemm_host_pipelined): K-range launches with per-range exponents for a big B ('N'), row-range launches for a big C ('T').  The results
 must be bit-identical to the device-resident one-launch path (same split-K boundaries, same summation order, exact power-of-two
 scalings), honour padded leading dimensions, and agree with the oracle on sampled rows."""

@@ -13,6 +13,7 @@
 //   k_crossprod_i8  (longer K)  v_mfma_i32_32x32x32_i8, 7 VALU per 16 values, exact int32 for K < 2.3e8; the same K-step pipeline.
 #include "../../include/miraculix_amd.h"
 #include "mxa_internal.h"
+#include "mxa_lds.h"
 #include "mxa_queue.h"
 #include "mxa_hostmem.h"
 #include "mxa_xprod.h"
@@ -28,11 +29,7 @@
 
 namespace mxa {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-using gptr_t = const __attribute__((address_space(1))) void *;
-using lptr_t = __attribute__((address_space(3))) void *;
 
 // ---- the reference's PLINK -> 2-bit byte table (snp_multiply_cuda.h:202-210): 00->0, 10->1, 11->2, and a byte that
 // holds a missing pair (01) anywhere becomes 0xFF.  SWAR on 4 bytes at a time.
@@ -118,16 +115,7 @@ __global__ void __launch_bounds__(256) k_xstage_planes(const uint8_t *__restrict
 
 // ---- main kernel -----------------------------------------------------------------------------------------------
 
-// 16 two-bit fields of a dword -> 16 int8 in 4 dwords (field order permuted identically for both operands)
-__device__ __forceinline__ v4i unpack16(uint32_t w) {
-  v4i r;
-  r[0] = (int)(w & 0x03030303u);
-  r[1] = (int)((w >> 2) & 0x03030303u);
-  r[2] = (int)((w >> 4) & 0x03030303u);
-  r[3] = (int)((w >> 6) & 0x03030303u);
-  return r;
-}
-
+// (the int8 engine's unpack16 and the LDS-DMA dma16_s: mxa_lds.h)
 __device__ __forceinline__ double grm_map(double v, double cs_i, double cs_j, double inv_n, double tot_nn, double inv_c, int do_scale) {
   v = fma(-(cs_i + cs_j), inv_n, v);   // BLAS.ger!(-1/indiv, col_sum, one_vector, M); BLAS.ger!(-1/indiv, one_vector, col_sum, M)  (cs_i + cs_j: exact integers)
   v = v + tot_nn;                      // M .+= sum(col_sum) / indiv^2
@@ -246,9 +234,6 @@ __device__ __forceinline__ void xprod_store(const AccT (&acc)[4][4], char *smem,
 // 128 x 64 wave tiles stalled at 43-54 % of the int8 peak on their unpack VALU density; the round-1/2 int8 kernel k_crossprod2 -- 3-deep ring, the
 // packed words of a whole stage prefetched mid-stage -- ran 2704 cycles per stage of 2048 ideal at 2.38 GHz, issue-bound; round 3 moved the int8
 // engine onto the FP4 kernel's K-step pipeline below: 2272 cycles at 2.19 GHz, now power-bound like the FP4 engine.)
-__device__ __forceinline__ void xdma16_s(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory", "m0");
-}
 
 // ---- FP4 engine ----------------------------------------------------------------------------------------------------------------
 // Per stage of 128 genotypes TWO K-steps of 64 (v_mfma_scale_f32_32x32x64_f8f6f4, FP4
@@ -272,8 +257,6 @@ __device__ __forceinline__ v16f mfma_f4(const v4i &a, const v4i &b, const v16f &
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);   // cbsz = blgp = 4: e2m1; scales 2^0
 }
 
-// EXP (diagnostic instantiations only, results are wrong): 1 = no unpack VALU; 2 = no DMA / barrier / LDS reads inside the loop;
-// 3 = barrier only; 4 = DMA + LDS reads without the barrier; 5 = barrier + DMA, no LDS reads; 6 = barrier + LDS reads, no DMA
 // The same pipeline serves the int8 engine (I8, round 3): a "K-step of 64" is then two v_mfma_i32_32x32x32_i8 sub-steps -- the lane's two dwords of
 // a K-step unpack into two int8 fragments (14 VALU per sub-block instead of 6), 8 MFMAs per sub-block row instead of 4, exact int32 sums.  It replaced
 // k_crossprod2 (3-deep ring, words of a whole stage prefetched mid-stage: 2704 cycles per stage of 2048 ideal at 2.38 GHz -- issue-bound, not
@@ -286,7 +269,7 @@ template <> struct XFrag<true> { using type = FragI8; using acc = v16i; };
 // gang start together but drift apart inside a 2.6 ms tile; half way through the K range every member adds to the gang's counter and waits for the others --
 // bounded by the join time and by 4 % of the tile's own duration, whichever is shorter -- so that the second half streams in step again
 struct GangMid { int *ctr; int target; unsigned ticks; int parts; int stride; };   // parts - 1 meetings inside a tile, meeting q uses ctr[(q - 1) * stride]
-template <bool DIAG, int EXP, bool I8, int POST>
+template <bool DIAG, bool I8, int POST>
 __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long nslabs, int stages, const int4 t, size_t tile_index, long n, double *__restrict__ ans,
                                            long ld, long c0, unsigned long long *__restrict__ diag, const XPost &post, const GangMid gm = GangMid{nullptr, 0, 0, 1, 0}) {
   using FragT = typename XFrag<I8>::type;
@@ -305,7 +288,7 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
     for (int i = 0; i < 4; i++) {
       const int u = wave + 4 * i;
       const int op = u >> 3, uu = u & 7;
-      xdma16_s((op ? XJ : XI) + (size_t)stage * kTileBytes + uu * 1024, v_lane, lds0 + buf * kXBufBytes + op * kXOpBytes + uu * 1024);
+      dma16_s((op ? XJ : XI) + (size_t)stage * kTileBytes + uu * 1024, v_lane, lds0 + buf * kXBufBytes + op * kXOpBytes + uu * 1024);
     }
   };
 
@@ -342,10 +325,7 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
   FragT fa0[4], fb0[4], fa1[4], fb1[4];      // F[0] / F[1]
   auto unpack = [](const u32x2 &w) -> FragT {
     if constexpr (I8) { FragI8 r; r.lo = unpack16(w.x); r.hi = unpack16(w.y); return r; }
-    else {
-      if (EXP == 1) { v4i r = {(int)w.x, (int)w.y, (int)w.x, (int)w.y}; return r; }
-      return unpack_f4(w.x, w.y);
-    }
+    else return unpack_f4(w.x, w.y);
   };
   auto mma = [](const FragT &fa, const FragT &fb, const AccT &c) -> AccT {
     if constexpr (I8) return __builtin_amdgcn_mfma_i32_32x32x32_i8(fa.hi, fb.hi, __builtin_amdgcn_mfma_i32_32x32x32_i8(fa.lo, fb.lo, c, 0, 0, 0), 0, 0, 0);
@@ -369,14 +349,12 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
 #define MXA_F4_KSTEP(FA, FB, WAU, WBU, FAN, FBN, WAR, WBR, RD, DO_DMA)                                                                      \
   {                                                                                                                                        \
     _Pragma("unroll") for (int a = 0; a < 4; a++) {                                                                                        \
-      if (DO_DMA && EXP != 2 && EXP != 3 && EXP != 6) {                                                                                    \
+      if (DO_DMA) {                                                                                                                        \
         const int u = wave + 4 * a, op = u >> 3, uu = u & 7;                                                                               \
-        xdma16_s((op ? XJ : XI) + (size_t)dma_stage * kTileBytes + uu * 1024, v_lane, lds0 + dma_buf * kXBufBytes + op * kXOpBytes + uu * 1024); \
+        dma16_s((op ? XJ : XI) + (size_t)dma_stage * kTileBytes + uu * 1024, v_lane, lds0 + dma_buf * kXBufBytes + op * kXOpBytes + uu * 1024); \
       }                                                                                                                                    \
-      if (EXP != 2 && EXP != 3 && EXP != 5) {                                                                                              \
-        WAR[a] = *reinterpret_cast<const u32x2 *>((RD) + a_off + a * 32 * kXStageBytes);                                                   \
-        WBR[a] = *reinterpret_cast<const u32x2 *>((RD) + b_off + a * 32 * kXStageBytes);                                                   \
-      }                                                                                                                                    \
+      WAR[a] = *reinterpret_cast<const u32x2 *>((RD) + a_off + a * 32 * kXStageBytes);                                                     \
+      WBR[a] = *reinterpret_cast<const u32x2 *>((RD) + b_off + a * 32 * kXStageBytes);                                                     \
       FAN[a] = unpack(WAU[a]);                                                                                                             \
       FBN[a] = unpack(WBU[a]);                                                                                                             \
       _Pragma("unroll") for (int b = 0; b < 4; b++) acc[a][b] = mma(FA[a], FB[b], acc[a][b]);                                              \
@@ -414,11 +392,9 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
   for (int s = s_lo; s < s_hi; s++) {
     // stage start: stage s+1 must have landed -- exactly (NB-2) stages' DMAs may stay in flight (one stage's 4 units are issued per stage,
     // always); this wave's reads of buffer s%NB were issued a K-step ago and are complete; after the barrier that buffer is refilled
-    if (EXP != 2) {
-      if (EXP != 3 && EXP != 6) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NB - 2)) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (EXP != 4) __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NB - 2)) : "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
     const int dma_stage = min(s + NB, stages - 1), dma_buf = buf;
     buf = buf == NB - 1 ? 0 : buf + 1;
     const char *nxt = smem + buf * kXBufBytes;
@@ -439,13 +415,13 @@ __device__ __forceinline__ void xprod_tile(const uint8_t *__restrict__ X, long n
   else xprod_store<AccT, POST>(acc, smem, wave, lane, wi, wj, i0, j0, t.z, n, ans, ld, c0, post);
 }
 
-template <bool DIAG, int EXP = 0, int POST = kPostNone>
+template <bool DIAG, int POST = kPostNone>
 __global__ void __launch_bounds__(256, 1)
 k_crossprod_f4(const uint8_t *__restrict__ X, long nslabs, int stages, const int4 *__restrict__ tiles, long n, double *__restrict__ ans,
                long ld, long c0, unsigned long long *__restrict__ diag, XPost post) {
   const int4 t = tiles[blockIdx.x];
   if (t.z == 0) return;                         // padding entry of the XCD-aware tile order (whole workgroup, before any barrier)
-  xprod_tile<DIAG, EXP, false, POST>(X, nslabs, stages, t, blockIdx.x, n, ans, ld, c0, diag, post);
+  xprod_tile<DIAG, false, POST>(X, nslabs, stages, t, blockIdx.x, n, ans, ld, c0, diag, post);
 }
 template <bool DIAG, int POST = kPostNone>
 __global__ void __launch_bounds__(256, 1)
@@ -453,7 +429,7 @@ k_crossprod_i8(const uint8_t *__restrict__ X, long nslabs, int stages, const int
                long ld, long c0, unsigned long long *__restrict__ diag, XPost post) {
   const int4 t = tiles[blockIdx.x];
   if (t.z == 0) return;
-  xprod_tile<DIAG, 0, true, POST>(X, nslabs, stages, t, blockIdx.x, n, ans, ld, c0, diag, post);
+  xprod_tile<DIAG, true, POST>(X, nslabs, stages, t, blockIdx.x, n, ans, ld, c0, diag, post);
 }
 
 // ---- gang-synchronised persistent form (round 3) ------------------------------------------------------------------------------------------
@@ -524,7 +500,7 @@ k_crossprod_gang(const uint8_t *__restrict__ X, long nslabs, int stages, const i
       if (!t.z && threadIdx.x == 0)   // a padding entry never reaches the meetings: counted here
         for (int q = 0; q + 1 < mid_parts; q++) __hip_atomic_fetch_add(gm.ctr + (size_t)q * gm.stride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (t.z) xprod_tile<false, 0, I8, POST>(X, nslabs, stages, t, 0, n, ans, ld, c0, nullptr, post, gm);
+    if (t.z) xprod_tile<false, I8, POST>(X, nslabs, stages, t, 0, n, ans, ld, c0, nullptr, post, gm);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stores of the epilogue: the DMA bookkeeping of the next tile starts from an empty counter
     __syncthreads();                                   // ... and the LDS scratch of the epilogue is free (sh_val / sh_list are rewritten only after this barrier)
   }
@@ -596,7 +572,7 @@ static int launch_lds(dim3 grid, hipStream_t s, A... a) {
   return 0;
 }
 // the one-workgroup-per-tile instantiation of an engine
-template <bool I8, bool DIAG, int POST> constexpr auto k_tiles = I8 ? &k_crossprod_i8<DIAG, POST> : &k_crossprod_f4<DIAG, 0, POST>;
+template <bool I8, bool DIAG, int POST> constexpr auto k_tiles = I8 ? &k_crossprod_i8<DIAG, POST> : &k_crossprod_f4<DIAG, POST>;
 
 // f(std::integral_constant<int, K>()) for every epilogue kind K
 template <int... K, typename F>

@@ -20,6 +20,7 @@
 // Same LDS-DMA ring / mid-stage prefetch / unpack pipelining as k_crossprod2; A rows come from the tiled packed layout, the
 // int8 slices of B are pre-arranged in MFMA fragment order by k_slice_B so every LDS read is a lane-linear ds_read_b128.
 #include "mxa_internal.h"
+#include "mxa_lds.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -28,39 +29,18 @@
 
 namespace mxa {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-using lptr_t = __attribute__((address_space(3))) void *;
 
-__device__ __forceinline__ void idma16_s(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory", "m0");
-}
-// The same with the NON-TEMPORAL hint, for the packed genotype tiles: they are read once per pass and are far larger than the L2s and the Infinity
-// Cache, so letting them allocate there only costs bandwidth.  tools/hbm_read_probe.hip on MI355X: an LDS-DMA stream reads 6.9-7.0 TB/s with `nt`
-// against 6.4-6.5 without (plain 16-byte loads: 7.1 against 6.3).  The digit slabs, which every row block re-reads, keep the default policy.
+// the packed genotype tiles come in by the non-temporal LDS-DMA (dma16_p<true>, mxa_lds.h: read once per pass), the digit slabs, which every row block
+// re-reads, by the plain one
 #ifndef MXA_NT_STREAM
 #define MXA_NT_STREAM 1
 #endif
-__device__ __forceinline__ void idma16_stream(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-#if MXA_NT_STREAM
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0 nt" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory", "m0");
-#else
-  idma16_s(sbase, voff, lds_addr);
-#endif
-}
-__device__ __forceinline__ v4i iunpack16(uint32_t w) {
-  v4i r;
-  r[0] = (int)(w & 0x03030303u);
-  r[1] = (int)((w >> 2) & 0x03030303u);
-  r[2] = (int)((w >> 4) & 0x03030303u);
-  r[3] = (int)((w >> 6) & 0x03030303u);
-  return r;
-}
 
 // ---- slices in MFMA fragment order.  Bs[chunk][T][nt][lane][16]: T = K-step of 32 genotypes, nt = 32-wide tile of expanded
 // columns e = s * nc + jj (slice s, column jj of the chunk), lane = (col = lane&31, h = lane>>5), byte 4q+i of the lane =
 // digit of B[128(T/4) + 64h + 16(T%4) + 4i + q][chunk*nc + jj]: a lane of half h reads the 16 bytes (64 genotypes) 16h.. of its row
-// per 128-genotype stage and uses dword T%4 of them in K-step T%4; iunpack16 puts field 4i+q of that dword into byte i of register q.
+// per 128-genotype stage and uses dword T%4 of them in K-step T%4; unpack16 (mxa_lds.h) puts field 4i+q of that dword into byte i of register q.
 // Balanced radix-256 digits of one double, exactly, in integer arithmetic.  b = +-m * 2^ex (m < 2^53 an integer).  In units of the
 // last digit, 2^(E - 8S), the value is N = m * 2^p, p = ex - E + 8S: for p >= 0 the low p/8 digits are zero and the rest come from
 // m << (p % 8); for p < 0 the bits below the last digit are rounded off (to nearest).  At most 9 digits are non-zero: they are packed
@@ -219,7 +199,7 @@ __device__ __forceinline__ void small_n_fp64_row(const SmallNFallback &a, const 
 // tn_map (k_gemm_i8_tn): K-step T covers 32 consecutive K indices, byte 4q+i of lane (h, col) = digit of B[32 T + 16 h + 4 i + q]
 __global__ void __launch_bounds__(256) k_slice_B(const double *__restrict__ B, long ldb, long k, int n, const int *__restrict__ E, int S, int nc, int NT,
                                                  long T_total, int ncols, uint32_t *__restrict__ Bs, long total, const int *__restrict__ skip_if_set,
-                                                 SliceFused fu, int tn_map, SmallNFallback fb, int SG) {
+                                                 SliceFused fu, int tn_map, SmallNFallback fb) {
   __shared__ int sE[kSmallNMaxCols], sflag, scls;
   __shared__ double sSum[2][kSmallNMaxCols];
   if (fu.part) {   // guarded small-n chain (n <= kSmallNMaxCols)
@@ -261,15 +241,14 @@ __global__ void __launch_bounds__(256) k_slice_B(const double *__restrict__ B, l
     }
     E = sE;
   } else if (skip_if_set && *skip_if_set) return;   // guarded route: B is not exactly representable, the fp64 fallback does this product
-  // one thread per (q, slice group sg, column cj = chunk*nc + jj, h, T): reads the 4 values k = 128(T/4) + 64h + 16(T%4) + 4i + q (i = 0..3), writes dword q of
-  // lane (h, col) for each slice of its group.  q runs fastest, then the group, then the column: 16-byte lane records and 128-byte runs of doubles.
-  // Slice groups (round 6): with many digits per column (n = 1: 32) a thread per (q, cj, h, T) walked all S slices -- 62 000 threads of ~1100 instructions each for the
-  // 250k-row operand of a CG step, 11-12 us; SG threads share the slices (each derives the digits of its four values itself: same integers, same bytes written).
-  const long total_sg = total * SG;
-  for (long idx0 = (long)blockIdx.x * blockDim.x + threadIdx.x; idx0 < total_sg; idx0 += (long)gridDim.x * blockDim.x) {
+  // one thread per (q, column cj = chunk*nc + jj, h, T): reads the 4 values k = 128(T/4) + 64h + 16(T%4) + 4i + q (i = 0..3), writes dword q of
+  // lane (h, col) for each slice.  q runs fastest, then the column: 16-byte lane records and 128-byte runs of doubles.
+  // (Slice groups, round 6: with many digits per column (n = 1: 32) a thread walks all S slices -- 62 000 threads of ~1100 instructions each for the 250k-row
+  // operand of a CG step, 11-12 us.  Four threads sharing the slices of one (q, column, h, K-step) took the 100k-row operand from 11.5 to 10 us and the 250k-row
+  // one from 12 to 15 us, each deriving the digits of its four values again (profiles/r06_gram_step_kernel_timeline.txt): one thread stays.)
+  for (long idx0 = (long)blockIdx.x * blockDim.x + threadIdx.x; idx0 < total; idx0 += (long)gridDim.x * blockDim.x) {
     const int q = (int)(idx0 & 3);
-    const int sg = (int)((idx0 >> 2) % SG);
-    const long rest = (idx0 >> 2) / SG;
+    const long rest = idx0 >> 2;
     const int cj = (int)(rest % ncols);
     const long hT = rest / ncols;
     const int h = (int)(hT & 1);
@@ -281,8 +260,7 @@ __global__ void __launch_bounds__(256) k_slice_B(const double *__restrict__ B, l
       const long kk = tn_map ? 32 * T + 16 * h + 4 * i + q : 128 * (T >> 2) + 64 * h + 16 * (T & 3) + 4 * i + q;   // K order of the A operand: see k_gemm_i8 / k_gemm_i8_tn
       d[i] = (kk < k && cj < n) ? balanced_digits(B[kk + (long)cj * ldb], E[cj], S) : Digits9{0ull, 0u, 0};
     }
-    const int per = (S + SG - 1) / SG, s_begin = sg * per, s_end = s_begin + per < S ? s_begin + per : S;
-    for (int s = s_begin; s < s_end; s++) {
+    for (int s = 0; s < S; s++) {
       uint32_t w = 0;
 #pragma unroll
       for (int i = 0; i < 4; i++) w |= digit_of(d[i], S, s) << (8 * i);
@@ -293,47 +271,19 @@ __global__ void __launch_bounds__(256) k_slice_B(const double *__restrict__ B, l
   }
 }
 
-// K splits of a launch as a table of stage boundaries (round 5).  The integer partial sums are exact, so ANY partition of K gives the same result bit for
-// bit -- which frees the lengths: the splits are dealt in DECREASING length (the workgroups of split 0 are dispatched first), so the resident slots run dry
-// over a fraction of the shortest piece instead of a whole uniform one (391 strips x 5 splits on 512 slots: 3.82 rounds used to cost 4).
-constexpr int kMaxI8Splits = 64;
-struct SplitTab { int begin[kMaxI8Splits + 1]; };
-static SplitTab make_split_tab(int stages_total, int splits, int max_len) {
-  SplitTab t{};
-  // uniform lengths.  A taper (lengths from 1.4x to 0.6x of the mean, longest dispatched first) was measured: no gain for the transposed-operand kernel, a LOSS for
-  // k_gemm_i8, whose XCD-dealt groups want equal work (profiles/r05_i8_taper_ab.txt: config-5 shard 'N' 0.964 -> 0.999 ms).  The table form is kept.
-  constexpr double taper = 0.0;
-  const double mean = (double)stages_total / splits;
-  double acc = 0.0;
-  t.begin[0] = 0;
-  for (int i = 0; i < splits; i++) {
-    const double w = splits >= 3 ? 1.0 + taper * (1.0 - 2.0 * i / (double)(splits - 1)) : 1.0;   // 1 + a ... 1 - a
-    acc += w * mean;
-    int b = i + 1 == splits ? stages_total : (int)(acc + 0.5);
-    b = std::max(b, t.begin[i] + 1);
-    b = std::min(b, std::min(stages_total - (splits - 1 - i), t.begin[i] + max_len));
-    t.begin[i + 1] = b;
-  }
-  // (max_len clipped a piece: push the remainder onto the later ones; they are shorter than the mean, so there is room unless mean itself is at the bound)
-  for (int i = splits; i > 0 && t.begin[i] > t.begin[i - 1] + max_len; i--) t.begin[i - 1] = t.begin[i] - max_len;
-  t.begin[splits] = stages_total;
-  return t;
-}
-
 // ---- main kernel
 constexpr int kI8Waves = 4;
 constexpr int kI8StageK = 128;                    // genotypes per stage = one slab of the tiled layout
-constexpr int kI8ABytes = kTileRows * kSlabBytes; // 8 KiB
+static_assert(kPlanTileRows == kTileRows && kPlanSlabK == kI8StageK && kPlanI8ABytes == kTileRows * kSlabBytes, "plan_i8 (mxa_plan.h) plans for these tiles");
 
-template <int NT, int ROWS = kTileRows>
+template <int NT>
 struct I8Cfg {
-  static constexpr int kABytes = ROWS * kSlabBytes;   // the workgroup's rows of one packed tile: 8 KiB, or 4 KiB for a half-tile workgroup (ROWS = 128)
+  static constexpr int kABytes = kTileRows * kSlabBytes;   // the rows of one packed tile: 8 KiB
   static constexpr int kBBytes = 4 * NT * 1024;   // 4 K-steps x NT tiles x 1 KiB
   static constexpr int kBufBytes = kABytes + kBBytes;
   // ring depth: as many stages as fit the 160 KiB LDS when one workgroup owns the CU (NT >= 5)
   // NT <= 4 needs at most 128 accumulator registers: two workgroups share a CU (3 buffers each) and hide each other's waits.
-  // Half-tile workgroups move half the packed bytes per stage: five buffers (40 KiB, four workgroups per CU) keep as many bytes in flight.
-  static constexpr int kBufs = ROWS < kTileRows ? 5 : NT <= 4 ? 3 : 163840 / kBufBytes;
+  static constexpr int kBufs = NT <= 4 ? 3 : 163840 / kBufBytes;
   static constexpr int kLds = kBufs * kBufBytes;
   static constexpr int kAUnits = kABytes / 1024;
   static constexpr int kUnits = kAUnits + 4 * NT;       // 1 KiB DMA units per stage
@@ -355,10 +305,6 @@ struct SchedIter {
 // columns with MT * (4/WC) = 8 so that a workgroup covers one 256-row tile of the packed layout.
 //   <NT, 2, 1>: every wave reads all NT B fragments per K-step (LDS read traffic 4 x NT KiB per K-step of 512 MFMA cycles)
 //   <NT, 4, 2>: wave tile 128 x (NT/2 x 32): half the B-fragment LDS traffic, twice the unpack VALU (28 per 16 MFMAs)
-//   <1, 1, 1>:  HALF-TILE workgroup (round 4): 128 rows (rows 128 h .. of a packed tile are 4 KiB in a row), wave tile 32 rows.  For an n <= 2 product with
-//               few row tiles (the 'N' product of a CG step: 391 tiles on 1024 slots) twice the workgroups fill the chip WITHOUT K splits, so the product
-//               finishes inside the kernel (no partial sums through HBM, no finish launch) at the price of the digit slabs crossing L2 -> LDS twice as often.
-//               That price is too high (1.36 ms against 0.965): experiment only, MXA_I8_HALF_TILE=1.
 // Direct finish (n <= 2, ONE K split, round 3): the workgroup holds the complete integer sums of its 256 rows, so it scales them, adds the digits
 // of a column across the lanes in a fixed butterfly, applies the centring term and stores C itself -- no partial sums through HBM, no finish launch
 // (the 'T' product of a CG step: 128 MB of int32 partials and ~25 us).  Same arithmetic as k_finish_i8_small up to the (fixed) order of the additions.
@@ -369,23 +315,26 @@ struct I8Direct {
   const double *sumB, *sumfB, *f;
 };
 
-template <int NT, int MT, int WC, bool DIAG, bool SWAP1 = false>
+// (The unused pointer argument is the place of a diagnostic buffer that no launch ever passed.  It stays as padding: without it every argument behind it moves
+// by 8 bytes, and on the one shape where the parent's five runs agreed to 0.15 % -- n = 1 'T', 250 000 x 100 000: 931.0-932.4 us -- the median came out at 934.7 us;
+// with it the nine instantiations are the parent's machine code.  profiles/i8_fossils_refactor.txt)
+template <int NT, int MT, int WC, bool SWAP1 = false>
 __global__ void __launch_bounds__(256, 1)
 k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict__ Bs, long T_total, int *__restrict__ P, long m_pad, int e_pad,
-          int rowblocks, int nchunks, int stages_total, SplitTab tab, unsigned long long *__restrict__ diag, const int *__restrict__ skip_if_set,
+          int rowblocks, int nchunks, int stages_total, SplitTab tab, unsigned long long *__restrict__ /* unused */, const int *__restrict__ skip_if_set,
           I8Direct dir) {
-  constexpr int ROWS = MT * (4 / WC) * 32;             // rows of the packed tile this workgroup multiplies: the whole tile, or one half
-  using Cfg = I8Cfg<NT, ROWS>;
+  constexpr int ROWS = MT * (4 / WC) * 32;             // rows this workgroup multiplies: one tile of the packed layout
+  using Cfg = I8Cfg<NT>;
   if (skip_if_set && *skip_if_set) return;
   constexpr int NTW = NT / WC;
-  static_assert(NT % WC == 0 && (ROWS == kTileRows || (ROWS == kTileRows / 2 && NT == 1)) && MT * NTW <= 16, "wave tiling");
+  static_assert(NT % WC == 0 && ROWS == kTileRows && MT * NTW <= 16, "wave tiling");
   // Operand roles (round 3).  The matrix cores draw less power when the FULL-entropy operand (the radix-256 digits) is the instruction's A and the
   // low-entropy one (genotype bytes 0..2) its B: a bare MFMA loop runs 4.17 Pop/s at 2.11 GHz that way round against 3.60 at 1.84 GHz the other
   // (tools/mfma_i8_probe3.hip), and from two tiles on this kernel is power-bound.  The fragments are symmetric (a lane holds 16 consecutive k of one
   // row / column), so swapping them just transposes the accumulator tile: lane & 31 = genotype row, registers = expanded column; the partial sums
   // then go to P TRANSPOSED, P[split][e][row] (rows along the lanes: 128-byte runs), and k_finish_i8_t reads them that way.
   // (SWAP1: the one-tile launch of a product with three or more columns -- no in-kernel finish, no k_finish_i8_small -- stores transposed like the wider ones,
-  // so that k_finish_i8_t finishes it: 36 us where k_finish_i8's row-major pass took 77 behind a 500k-row product)
+  // so that k_finish_i8_t finishes it: 36 us where a row-major general finish, since removed, took 77 behind a 500k-row product)
   constexpr bool kSwap = NT >= 2 || SWAP1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -404,7 +353,7 @@ k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict_
   const int stages = st1 - st0;
   const uint32_t lds0 = (uint32_t)(size_t)(lptr_t)smem;
   const uint32_t v_lane = lane * 16;
-  const char *A_u = reinterpret_cast<const char *>(G) + (size_t)(ROWS == kTileRows ? rb : rb >> 1) * (pitch / kSlabBytes) * kTileBytes + (ROWS == kTileRows ? 0 : (rb & 1) * Cfg::kABytes);
+  const char *A_u = reinterpret_cast<const char *>(G) + (size_t)rb * (pitch / kSlabBytes) * kTileBytes;
   const char *B_u = reinterpret_cast<const char *>(Bs) + (size_t)nc * ((size_t)T_total * NT * 1024);
 
   // (with several column chunks -- the opt-in engines at wide n -- a packed tile is an operand of every chunk; choosing the policy per launch with a
@@ -417,8 +366,8 @@ k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict_
     for (int i = 0; i < (Cfg::kUnits + kI8Waves - 1) / kI8Waves; i++) {
       const int u = wave + i * kI8Waves;
       if (Cfg::kUnits % kI8Waves == 0 || u < Cfg::kUnits) {
-        if (u < Cfg::kAUnits) idma16_stream(asrc + u * 1024, v_lane, base + u * 1024);
-        else idma16_s(bsrc + (u - Cfg::kAUnits) * 1024, v_lane, base + Cfg::kABytes + (u - Cfg::kAUnits) * 1024);
+        if (u < Cfg::kAUnits) dma16_p<MXA_NT_STREAM != 0>(asrc + u * 1024, v_lane, base + u * 1024);
+        else dma16_s(bsrc + (u - Cfg::kAUnits) * 1024, v_lane, base + Cfg::kABytes + (u - Cfg::kAUnits) * 1024);
       }
     }
   };
@@ -446,14 +395,12 @@ k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict_
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  unsigned long long t0 = 0, r0 = 0;   // DIAG instantiation only: shader-clock / 100 MHz stamps around the K loop
-  if (DIAG) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
   uint4 aw[MT], awn[MT];
 #pragma unroll
   for (int a = 0; a < MT; a++) { aw[a] = *reinterpret_cast<const uint4 *>(smem + a_off + a * 32 * kSlabBytes); awn[a] = aw[a]; }
   int buf = 0;
   auto comp = [](const uint4 &w, int c) -> uint32_t { return c == 0 ? w.x : c == 1 ? w.y : c == 2 ? w.z : w.w; };
-  v4i af_cur = iunpack16(aw[0].x);
+  v4i af_cur = unpack16(aw[0].x);
   v4i bf_cur[NTW], bf_nxt[NTW];
 #pragma unroll
   for (int b = 0; b < NTW; b++) { bf_cur[b] = *reinterpret_cast<const v4i *>(smem + b_off + b * 1024); bf_nxt[b] = bf_cur[b]; }
@@ -479,7 +426,7 @@ k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict_
 #pragma unroll
       for (int a = 0; a < MT; a++) {
         const uint32_t wa = a < MT - 1 ? comp(aw[a + 1], ks) : (ks < 3 ? comp(aw[0], ks + 1) : awn[0].x);
-        const v4i af_nxt = iunpack16(wa);
+        const v4i af_nxt = unpack16(wa);
         const int lo = a * NTW / MT, hi = (a + 1) * NTW / MT;
 #pragma unroll
         for (int b = 0; b < NTW; b++)
@@ -500,10 +447,6 @@ k_gemm_i8(const uint8_t *__restrict__ G, size_t pitch, const int8_t *__restrict_
     for (int a = 0; a < MT; a++) aw[a] = awn[a];
   }
 
-  if (DIAG) {
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0 && diag) { diag[2 * (size_t)blockIdx.x] = t1 - t0; diag[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
-  }
   // epilogue: P[split][row][e] int32, e contiguous: lanes (col) write 128-byte runs.  C/D map: col = lane&31,
   // row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
   const int col = lane & 31, rq = 4 * (lane >> 5);
@@ -648,7 +591,7 @@ k_gemm_i8_tn(const uint8_t *__restrict__ G, long nslabs_all, const int8_t *__res
       const int u = kWaveLocal ? (i >> 1) * 8 + 2 * wave + (i & 1) : wave + i * Cfg::kWaves;       // slab j = u >> 3, K-step u & 7
       long sl = (long)strip * kTnSlabs + (u >> 3);
       if (sl >= nslabs_all) sl = nslabs_all - 1;             // individuals beyond the matrix: rows of P nobody reads
-      idma16_stream(reinterpret_cast<const char *>(G) + (rb * (size_t)nslabs_all + (size_t)sl) * kTileBytes + (u & 7) * 1024, v_pack, base + (u >> 3) * kTnSlabStride + (u & 7) * 1024);
+      dma16_p<MXA_NT_STREAM != 0>(reinterpret_cast<const char *>(G) + (rb * (size_t)nslabs_all + (size_t)sl) * kTileBytes + (u & 7) * 1024, v_pack, base + (u >> 3) * kTnSlabStride + (u & 7) * 1024);
     }
   };
   auto issue_digits = [&](int stage, v4i (&d)[2][TT]) {       // the tiles of a K-step are 1 KiB apart, the K-steps digit_tiles KiB
@@ -792,100 +735,9 @@ k_gemm_i8_tn(const uint8_t *__restrict__ G, long nslabs_all, const int8_t *__res
 }
 
 // ---- finish: sum the splits exactly (int64), combine the slices smallest scale first, centring, ldc store.
-// Block = 32 rows x one chunk of columns; P is read with the expanded column running along the lanes (one lane per integer sum),
-// the result is transposed through LDS so that C is written with the row running along the lanes.
-__global__ void __launch_bounds__(256) k_finish_i8(const int *__restrict__ P, long m_pad, int e_pad, int splits, long m, int n, int S, int nc, int NT,
-                                                   const int *__restrict__ E, const double *__restrict__ colmax_part, double *__restrict__ Cout, long ldc,
-                                                   long fill_rows, int mode_trans, int centered, const double *__restrict__ sumB, const double *__restrict__ sumfB,
-                                                   const double *__restrict__ f, const int *__restrict__ skip_if_set) {
-  __shared__ double sh[32][33];
-  if (skip_if_set && *skip_if_set) return;
-  __shared__ double contrib[8][8 * 32 + 1];        // scaled terms of 8 rows x all expanded columns of the chunk
-  __shared__ int bad[32];                           // column holds an inf or a NaN: the result column is NaN, like 0 * inf in fp64
-  const int chunk = blockIdx.y;
-  const long r0 = (long)blockIdx.x * 32;
-  if (threadIdx.x < 32) {
-    const int j = chunk * nc + threadIdx.x;
-    double cm = 0.0;
-    if ((int)threadIdx.x < nc && j < n)
-      for (int c = 0; c < 64; c++) cm = fmax(cm, colmax_part[(size_t)j * 64 + c]);
-    bad[threadIdx.x] = !(cm <= 1.7976931348623157e308);
-  }
-  __syncthreads();
-  if (nc >= 16) {
-    // wide chunks: lane jj walks its column's slices itself (the lanes of a row already cover a 64..128-byte run of P)
-    const int jj = threadIdx.x & 31, j = chunk * nc + jj;
-    for (int rr = threadIdx.x >> 5; rr < 32; rr += 8) {
-      const long r = r0 + rr;
-      double v = 0.0;
-      if (r < m && jj < nc && j < n) {
-        const int Ej = E[j];
-        if (bad[jj]) v = __longlong_as_double(0x7ff8000000000000ll);
-        else
-          for (int s = S - 1; s >= 0; s--) {
-            long long t = 0;
-            for (int sp = 0; sp < splits; sp++) t += P[((size_t)sp * m_pad + r) * e_pad + chunk * (NT * 32) + s * nc + jj];
-            v += ldexp((double)t, Ej - 8 * (s + 1));
-          }
-        if (centered) {
-          if (mode_trans) v = fma(-2.0 * sumB[j], f[r], v);
-          else v += -2.0 * sumfB[j];
-        }
-      }
-      sh[rr][jj] = v;
-    }
-    __syncthreads();
-  } else {
-    // 8 rows per pass: lanes run along the expanded column e = s * nc + jj (128-byte runs of P), each lane turns its integer sum into
-    // the scaled fp64 term of (slice s, column jj); then lane jj adds its column's terms, smallest scale first
-    for (int pass = 0; pass < 4; pass++) {
-      const int rr = pass * 8 + (threadIdx.x >> 5);
-      const long r = r0 + rr;
-      for (int nt = 0; nt < NT; nt++) {
-        const int e = nt * 32 + (threadIdx.x & 31);
-        double c = 0.0;
-        if (r < m && e < nc * S) {
-          const int s = e / nc, jj = e - s * nc, j = chunk * nc + jj;
-          if (j < n) {
-            long long t = 0;
-            for (int sp = 0; sp < splits; sp++) t += P[((size_t)sp * m_pad + r) * e_pad + chunk * (NT * 32) + e];
-            c = ldexp((double)t, E[j] - 8 * (s + 1));
-          }
-        }
-        contrib[threadIdx.x >> 5][e] = c;
-      }
-      __syncthreads();
-      {
-        const int jj = threadIdx.x & 31, j = chunk * nc + jj;
-        double v = 0.0;
-        if (r < m && jj < nc && j < n) {
-          if (bad[jj]) v = __longlong_as_double(0x7ff8000000000000ll);
-          else
-            for (int s = S - 1; s >= 0; s--) v += contrib[threadIdx.x >> 5][s * nc + jj];
-          if (centered) {
-            if (mode_trans) v = fma(-2.0 * sumB[j], f[r], v);
-            else v += -2.0 * sumfB[j];
-          }
-        }
-        sh[rr][jj] = v;
-      }
-      __syncthreads();
-    }
-  }
-  {
-    const int rr = threadIdx.x & 31;
-    const long r = r0 + rr;
-    for (int jj = threadIdx.x >> 5; jj < nc; jj += 8) {
-      const int j = chunk * nc + jj;
-      if (r < fill_rows && j < n) Cout[r + (long)j * ldc] = sh[rr][jj];
-    }
-  }
-}
-
-
 // finish for the TRANSPOSED partial sums of the operand-swapped instantiations (NT >= 2): P[split][e][row], e = chunk * NT * 32 + s * nc + jj.
-// One thread per (row, column): every load is a 1 KiB run along the rows, C is written along the rows.  Same arithmetic, in the same order, as
-// k_finish_i8: exact int64 sums over the splits, digits added smallest scale first.
+// One thread per (row, column): every load is a 1 KiB run along the rows, C is written along the rows: exact int64 sums over the splits, digits added
+// smallest scale first.
 // Block = 256 rows x 4 digit groups (round 4; was one thread per row walking all S digits and K splits in a chain of dependent loads: 100-170 us behind a
 // 1 ms product).  Thread (lane, g) owns the digits s in [g Sg, (g + 1) Sg), Sg = ceil(S / 4) <= 8, of FOUR rows (lane, lane + 64, ...): all their partial
 // sums over the K splits are loaded before the first use (rows along the lanes: 256-byte runs; one row per thread left the launch bound by the life
@@ -1029,84 +881,15 @@ __global__ void __launch_bounds__(256) k_finish_i8_small(const int *__restrict__
   }
 }
 
-struct I8Plan { int S, nc, nchunks, NT, e_pad, rowblocks, stages_total, stages_per_split, splits, rows_wg; long m_pad, T_total; };
-
-static I8Plan plan_i8(long m, long k_pad, int n, int S_override) {
-  I8Plan p{};
-  const int S_env = S_override > 0 ? std::min(32, std::max(3, S_override)) : 0;
-  int S = S_env ? S_env : 7;                                     // 8 bits per digit: 7 digits = 56 bits below 2^E_j
-  // a tile of 32 expanded columns is the unit of work: for n <= 4 the kernel is HBM-bound with one tile, so the digits that fit the
-  // tile are free -- n = 1: 32 digits (256 bits: any entry down to 2^-200 of the column maximum keeps its whole mantissa), n = 2: 16
-  if (!S_env && n * S <= 32) S = std::min(32, 32 / n);
-  if (!S_override && n * S > 32 && S > 8) S = 8;
-  p.S = S;
-  const int max_nc = std::min(32, 256 / S);                     // <= 8 tiles of 32 expanded columns per pass; k_finish_i8 handles <= 32 columns per chunk
-  p.nchunks = (n + max_nc - 1) / max_nc;
-  p.nc = (n + p.nchunks - 1) / p.nchunks;
-  p.NT = (p.nc * S + 31) / 32;
-  p.e_pad = p.nchunks * p.NT * 32;
-  p.stages_total = (int)(k_pad / kI8StageK);
-  p.T_total = k_pad / 32;
-  // K splits.  The kernel runs one workgroup per piece and the hardware keeps as many resident as the LDS allows (NT = 1: four per CU; the
-  // launch is HBM-bound there and more workgroups mean more bytes in flight).  Measured on the config-5 shard (n = 1): what matters is that the
-  // workgroup total fills whole rounds of the resident slots -- 391 row tiles x 5 splits = 1.91 rounds of 1024: 1.08 ms, x 6 = 2.29 rounds:
-  // 1.19 ms -- and, at equal fill, FEWER splits (less partial-sum traffic, fewer prologues): 977 tiles x 3: 1.05 ms, x 7: 1.16 ms.
-  long max_splits = std::max<long>(1, p.stages_total / 32);
-  const bool direct_possible = p.nchunks == 1 && p.NT == 1 && p.nc <= 2;
-  // Cost model (round 3; replaces "fill the rounds to 3 %"): main kernel = the larger of the packed-matrix stream at ~6 TB/s and the int8
-  // work at the ~2.4 Pop/s the power limit allows, stretched by the unfilled part of the last round of resident slots and by a per-piece
-  // prologue worth ~6 stages; plus the partial sums, written once and read once by the finish (none when the single split of an n <= 2
-  // product finishes inside the kernel).  Fewest splits within 1 % of the best.  Evaluated for whole-tile workgroups (256 rows) and, under
-  // MXA_I8_HALF_TILE=1, for half-tile workgroups (128 rows, five-deep rings; the model for those is a guess that the measurement refuted).
-  auto evaluate = [&](int rows_wg, long *splits_out) {
-    const long rowblocks = (m + rows_wg - 1) / rows_wg, m_pad = rowblocks * rows_wg, units = rowblocks * p.nchunks;
-    const bool half = rows_wg < kTileRows;
-    const long lds_wg = half ? 5L * (rows_wg * kSlabBytes + 4L * p.NT * 1024) : 3L * (kI8ABytes + 4L * p.NT * 1024);
-    const long resident = 256L * (p.NT <= 4 ? std::max<long>(1, std::min<long>(4, 163840 / lds_wg)) : 1);
-    const double t_main = std::max((double)m_pad * (double)k_pad / 4.0 * p.nchunks / 6.0e12, 2.0 * (double)m_pad * (double)k_pad * p.e_pad / 2.4e15) * (half ? 1.015 : 1.0);
-    const double prologue = half ? 12.0 : 6.0;
-    double best = 1e300;
-    long splits = 1;
-    for (long cand = 1; cand <= std::min<long>(max_splits, 64); cand++) {
-      const long per = (p.stages_total + cand - 1) / cand, actual = (p.stages_total + per - 1) / per;
-      if (actual != cand) continue;
-      // Whole rounds of the resident slots.  Exception (round 4): ONE split of a product with at least two full rounds of row tiles -- its thinly
-      // filled last round costs max(its workgroups, 0.6 slots), not a whole round: 500k x 50k, n = 4 .. 6, 'T' (1954 tiles on 768 slots) runs 2-10 % faster
-      // uncut than in the three splits the whole-round rule chose (round 4, docs/HISTORY.md).  Products with few row tiles ('N') keep the
-      // whole-round rule: there the sweeps want MORE workgroups than the soft rule would ask for (config-5 shard 'N' 2 / 5 splits 1.04 / 0.96 ms).
-      const long wgs = units * actual, rounds = (wgs + resident - 1) / resident, full = wgs / resident, last = wgs - full * resident;
-      double quant = (double)(rounds * resident) / (double)wgs;
-      if (actual == 1 && full >= 2) quant = ((double)full * (double)resident + (last ? std::max((double)last, 0.6 * (double)resident) : 0.0)) / (double)wgs;
-      if (half && rounds == 1) quant = std::max(1.0, 0.65 * (double)resident / (double)wgs);
-      const double t_p = (actual == 1 && direct_possible) ? 0.0 : 2.0 * (double)actual * (double)m_pad * p.e_pad * 4.0 / 5.0e12 + 5.0e-6;
-      const double t = t_main * quant * ((double)per + prologue) / (double)per + t_p;
-      if (t < best * 0.99) { best = t; splits = cand; }
-    }
-    *splits_out = splits;
-    return best;
-  };
-  long splits = 1;
-  (void)evaluate(kTileRows, &splits);
-  p.rows_wg = kTileRows;
-  // (half-tile workgroups -- 128 rows, no K splits, the product finished inside the kernel -- were built in round 4 and removed in round 5: config-5 shard 'N'
-  // 1.36 ms against 0.965 with five splits: the digit slabs then cross L2 -> LDS as 2x the packed bytes and the DMA path sets the pace;
-  // profiles/r04_i8_half_tile_ab.txt)
-  p.rowblocks = (int)((m + p.rows_wg - 1) / p.rows_wg);
-  p.m_pad = (long)p.rowblocks * p.rows_wg;
-  splits = std::max<long>(splits, (p.stages_total + 32767) / 32768);   // int32 accumulators: 2 * 128 * (K per split) < 2^31
-  p.stages_per_split = (int)((p.stages_total + splits - 1) / splits);
-  p.splits = (p.stages_total + p.stages_per_split - 1) / p.stages_per_split;
-  return p;
-}
-
+// (the plan of a product -- I8Plan, plan_i8, the split table, the choice of finish: mxa_plan.h, host-only code swept on the CPU)
 template <int NT, int MT, int WC, bool SWAP1 = false>
 static int launch_i8_t(const PackedMatrix &G, const int8_t *dBs, int *dP, const I8Plan &p, hipStream_t s, const int *skip_if_set, const I8Direct &dir) {
-  using Cfg = I8Cfg<NT, MT * (4 / WC) * 32>;
+  using Cfg = I8Cfg<NT>;
   static unsigned long long attr_a = 0;   // function attributes are per device
-  if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_gemm_i8<NT, MT, WC, false, SWAP1>), Cfg::kLds, &attr_a)) return 1;
+  if (ensure_dyn_lds(reinterpret_cast<const void *>(&k_gemm_i8<NT, MT, WC, SWAP1>), Cfg::kLds, &attr_a)) return 1;
   const long grid = (long)p.rowblocks * p.nchunks * p.splits;
-  hipLaunchKernelGGL((k_gemm_i8<NT, MT, WC, false, SWAP1>), dim3((unsigned)grid), dim3(256), Cfg::kLds, s, G.d, G.pitch, dBs, p.T_total, dP, p.m_pad, p.e_pad,
-                     p.rowblocks, p.nchunks, p.stages_total, make_split_tab(p.stages_total, p.splits, 32767), (unsigned long long *)nullptr, skip_if_set, dir);
+  hipLaunchKernelGGL((k_gemm_i8<NT, MT, WC, SWAP1>), dim3((unsigned)grid), dim3(256), Cfg::kLds, s, G.d, G.pitch, dBs, p.T_total, dP, p.m_pad, p.e_pad,
+                     p.rowblocks, p.nchunks, p.stages_total, make_split_tab(p.stages_total, p.splits, kPlanI8MaxSplitStages), (unsigned long long *)nullptr, skip_if_set, dir);
   MXA_HIP(hipGetLastError());
   return 0;
 }
@@ -1151,6 +934,7 @@ static int plan_i8_full(const PackedMatrix &G, int n, int S_override, const Pack
   f.p = plan_i8(m, G.k_pad, n, S_override);
   I8Plan &p = f.p;
   if (p.m_pad > G.rows_pad) { set_error(4, "internal: packed matrix smaller than the i8 plan"); return 1; }
+  if (p.splits > kMaxI8Splits) { set_error(4, "int8 engine: K of %ld genotypes needs more than %d K splits", G.k_pad, kMaxI8Splits); return 1; }   // beyond 64 x 32767 stages: the split table ends there
   // transposed-operand form (G_tn = the copy whose ROWS are the K index): same digits, same exactness guard, other main kernel and P layout
   // (several tiles of 32 expanded columns: one pass over the matrix per tile -- 3 <= n <= 6 and peeled columns of single-orientation objects; beyond what the
   // fp64 MFMA tile would take, or with several column chunks, the caller's fp64 path is the better choice: declined with 2 before anything is enqueued)
@@ -1196,14 +980,12 @@ int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_t
 int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, long ldb, double *dC, long ldc, long fill_rows, bool centered, double *d_sumB,
                    double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, const I8Opts &o) {
   hipEvent_t ev0 = o.ev0, ev1 = o.ev1;
-  int *splits_out = o.splits_out, guard = o.guard, S_override = o.S_override;
+  int *splits_out = o.splits_out, S_override = o.S_override;
   const int **flag_out = o.flag_out;
   double *colsum_scratch = o.colsum_scratch, *stats_part = o.stats_part;
   const PackedMatrix *G_tn = o.G_tn; const I8Chain *chain = o.chain;
   const long m = G.rows, k = G.k;
-  I8Chain ch1;
-  if (guard == 2) {   // device-side verdict: this launch sequence is the chain of one class
-    if (!chain) { ch1.S0 = plan_i8(m, G.k_pad, n, S_override).S; ch1.S1 = 0; ch1.my_class = 0; ch1.first = true; chain = &ch1; }
+  if (chain) {   // guarded product, device-side verdict: this launch sequence is the chain of one class
     if (n > kSmallNMaxCols || !colsum_scratch) { set_error(4, "internal: guarded int8 chain with %d columns", n); return 1; }
     S_override = chain->my_class ? chain->S1 : chain->S0;
   }
@@ -1219,16 +1001,15 @@ int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, l
   if (chain && !chain->first && w.cap_i8 < pf.need) { set_error(4, "internal: the second chain of a guarded product outgrows the workspace (gemm_i8_reserve)"); return 1; }
   if (i8_grow(w, pf.need, s)) return 1;
   char *base = static_cast<char *>(w.d_i8);
-  double *d_part = (stats_part && !guard) ? stats_part : reinterpret_cast<double *>(base);
+  double *d_part = (stats_part && !chain) ? stats_part : reinterpret_cast<double *>(base);
   int *d_E = reinterpret_cast<int *>(base + part_bytes);
   int8_t *d_Bs = reinterpret_cast<int8_t *>(base + part_bytes + e_bytes);
   int *d_P = reinterpret_cast<int *>(base + part_bytes + e_bytes + bs_bytes);
 
   // E_j = e + 2: |b| * 2^-E_j < 1/4, inside the remainder range of the balanced digits
-  const int *skip = nullptr;   // guard = 2: the kernels below test this device flag themselves
-  bool fused = false;
+  const int *skip = nullptr;   // a chain: the kernels below test this device flag themselves
   SliceFused fu{};
-  if (!guard) {
+  if (!chain) {
     if (stats_part) { if (launch_colexp_from_part(d_part, n, d_E, 2, s)) return 1; }
     else if (launch_colexp(dB, ldb, k, n, d_part, d_E, 2, s)) return 1;
   } else {
@@ -1237,41 +1018,30 @@ int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, l
     // i.e. the exponent span e_max - e_min <= 8S - 55; the recombination ldexp(t, E_j - 8(s+1)) stays normal iff e_max + 2 - 8S >= -1021.
     // the flag lives in the handle's small flag block (never reallocated while the handle lives: mxa_last_path() may read it later)
     if (!w.d_denflag) { set_error(4, "internal: flag block missing"); return 1; }
-    int *d_flag = w.d_denflag + 1, h_flag = 1;   // three words: (class == 2), (class != 0), (class != 1)   [SliceFused]
-    fused = guard == 2;
-    if (fused) {   // one statistics pass (the first chain's); exponents, verdict and column sums are finished inside k_slice_B
-      if (chain->first) hipLaunchKernelGGL(k_colstats_partial, dim3(64, n), dim3(256), 0, s, dB, ldb, k, n, trans ? nullptr : d_f, centered ? 1 : 0, d_part, colsum_scratch);
-      fu = SliceFused{d_part, colsum_scratch, d_E, d_flag, d_sumB, d_sumfB, 2, chain->S0, chain->S1, chain->my_class, chain->first ? 1 : 0, centered ? 1 : 0};
-      skip = d_flag + 1 + chain->my_class;     // (class != my_class)
-      if (flag_out) *flag_out = d_flag;        // (class == 2): the fp64 kernel behind runs iff it is set
-    } else {
-      if (launch_colexp(dB, ldb, k, n, d_part, d_E, 2, s, d_flag, 8 * p.S - 55, 8 * p.S - 1023)) return 1;
-      MXA_HIP(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
-      MXA_HIP(hipStreamSynchronize(s));
-      if (h_flag) return 2;
-    }
+    int *d_flag = w.d_denflag + 1;   // three words: (class == 2), (class != 0), (class != 1)   [SliceFused]
+    // one statistics pass (the first chain's); exponents, verdict and column sums are finished inside k_slice_B
+    if (chain->first) hipLaunchKernelGGL(k_colstats_partial, dim3(64, n), dim3(256), 0, s, dB, ldb, k, n, trans ? nullptr : d_f, centered ? 1 : 0, d_part, colsum_scratch);
+    fu = SliceFused{d_part, colsum_scratch, d_E, d_flag, d_sumB, d_sumfB, 2, chain->S0, chain->S1, chain->my_class, chain->first ? 1 : 0, centered ? 1 : 0};
+    skip = d_flag + 1 + chain->my_class;     // (class != my_class)
+    if (flag_out) *flag_out = d_flag;        // (class == 2): the fp64 kernel behind runs iff it is set
   }
   if (p.NT * 32 != p.nc * p.S) MXA_HIP(hipMemsetAsync(d_Bs, 0, bs_bytes, s));   // expanded columns beyond nc*S are never written
   {
     const int ncols = p.nchunks * p.nc;
     const long total = (long)p.T_total * 2 * ncols * 4;
     SmallNFallback fb{};
-    // threads sharing the slices of one (q, column, h, K-step).  Measured (profiles/r06_gram_step_kernel_timeline.txt): four threads per 32 slices take the 100k-row operand of a
-    // CG step from 11.5 to 10 us and the 250k-row one from 12 to 15 us (each group derives the digits of its four values again): one thread stays
-    const int SG = 1;
-    long blocks = (total * SG + 255) / 256;
-    if (fused && chain->first && chain->fp64_rows) {   // the fp64 rows of verdict class 2 ride in this launch: a thread per output row (n = 1; wider chains: gated fp64 launches of the caller)
+    long blocks = (total + 255) / 256;
+    if (chain && chain->first && chain->fp64_rows) {   // the fp64 rows of verdict class 2 ride in this launch: a thread per output row (n = 1; wider chains: gated fp64 launches of the caller)
       const PackedMatrix &GF = tn ? *G_tn : G;
       fb = SmallNFallback{GF.d, GF.nslabs, m, k, dC, ldc, fill_rows, tn ? 1 : 0, trans ? 1 : 0, centered ? 1 : 0, d_f};
       blocks = std::max(blocks, (fill_rows + 255) / 256);
     }
     hipLaunchKernelGGL(k_slice_B, dim3((unsigned)std::min<long>(blocks, 256L * 64)), dim3(256), 0, s, dB, ldb, k, n, d_E, p.S, p.nc, p.NT,
-                       p.T_total, ncols, reinterpret_cast<uint32_t *>(d_Bs), total, skip, fu, tn ? 1 : 0, fb, SG);
+                       p.T_total, ncols, reinterpret_cast<uint32_t *>(d_Bs), total, skip, fu, tn ? 1 : 0, fb);
   }
   MXA_HIP(hipGetLastError());
   if (ev0) MXA_HIP(hipEventRecord(ev0, s));
   int rc = 0;
-  const bool small_tile = p.nchunks == 1 && p.NT == 1 && p.nc * p.S <= 32 && (p.nc == 1 || p.nc == 2);   // n <= 2: one tile
   I8Direct dir{};
   if (tn) {
     if (p.NT >= 2 ? launch_i8_tn<6, 2>(*G_tn, d_Bs, d_P, p, pf.tn_sc, s, skip)
@@ -1282,14 +1052,14 @@ int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, l
     hipLaunchKernelGGL(k_finish_i8_t, grid, dim3(256), 0, s, d_P, p.m_pad, p.e_pad, p.splits, m, n, p.S, p.nc, p.NT, d_E, d_part, dC, ldc, fill_rows, trans ? 1 : 0,
                        centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip, 1, pf.tn_sc);
     MXA_HIP(hipGetLastError());
-    return guard == 2 ? 3 : 0;
+    return chain ? 3 : 0;
   }
-  if (small_tile && p.splits == 1)
+  const I8Finish finish = i8_finish_route(p);
+  if (finish == I8Finish::direct)
     dir = I8Direct{1, d_E, d_part, dC, ldc, m, fill_rows, n, p.S, p.nc, trans ? 1 : 0, centered ? 1 : 0, d_sumB, d_sumfB, d_f};
-  // one tile, three or more columns (n = 3; n = 4 with few digits), one chunk: transposed partial sums like the wider launches (k_finish_i8_t)
-  const bool swap1 = p.NT == 1 && !small_tile && p.nchunks == 1 && p.rows_wg == kTileRows;
   switch (p.NT) {
-    case 1: rc = swap1 ? launch_i8_t<1, 2, 1, true>(G, d_Bs, d_P, p, s, skip, dir) : launch_i8_t<1, 2, 1>(G, d_Bs, d_P, p, s, skip, dir); break;
+    // one tile, three or more columns (n = 3; n = 4 with few digits): transposed partial sums like the wider launches (k_finish_i8_t)
+    case 1: rc = finish == I8Finish::transposed ? launch_i8_t<1, 2, 1, true>(G, d_Bs, d_P, p, s, skip, dir) : launch_i8_t<1, 2, 1>(G, d_Bs, d_P, p, s, skip, dir); break;
     case 2: rc = launch_i8_t<2, 2, 1>(G, d_Bs, d_P, p, s, skip, dir); break;
     case 3: rc = launch_i8_t<3, 2, 1>(G, d_Bs, d_P, p, s, skip, dir); break;
     case 4: rc = launch_i8_t<4, 2, 1>(G, d_Bs, d_P, p, s, skip, dir); break;
@@ -1300,22 +1070,21 @@ int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, l
   }
   if (rc) return rc;
   if (ev1) MXA_HIP(hipEventRecord(ev1, s));
-  if (dir.on) {
-    // finished inside k_gemm_i8
-  } else if (small_tile) {   // n <= 2: one tile, the fast finish
-    hipLaunchKernelGGL(k_finish_i8_small, dim3((unsigned)((fill_rows + kFinSmallBlockRows - 1) / kFinSmallBlockRows)), dim3(256), 0, s, d_P, p.m_pad, p.splits, m, n, p.S, p.nc, d_E, d_part, dC, ldc, fill_rows,
-                       trans ? 1 : 0, centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip);
-  } else if (p.NT >= 2 || swap1) {   // operand-swapped instantiations: transposed partial sums
-    dim3 grid((unsigned)((fill_rows + kFinTBlockRows - 1) / kFinTBlockRows), (unsigned)n);
-    hipLaunchKernelGGL(k_finish_i8_t, grid, dim3(256), 0, s, d_P, p.m_pad, p.e_pad, p.splits, m, n, p.S, p.nc, p.NT, d_E, d_part, dC, ldc, fill_rows, trans ? 1 : 0,
-                       centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip, 0, TnSched{});
-  } else {
-    dim3 grid((unsigned)((fill_rows + 31) / 32), p.nchunks);
-    hipLaunchKernelGGL(k_finish_i8, grid, dim3(256), 0, s, d_P, p.m_pad, p.e_pad, p.splits, m, n, p.S, p.nc, p.NT, d_E, d_part, dC, ldc, fill_rows, trans ? 1 : 0,
-                       centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip);
+  switch (finish) {
+    case I8Finish::direct: break;   // finished inside k_gemm_i8
+    case I8Finish::small:           // n <= 2: one tile, the fast finish
+      hipLaunchKernelGGL(k_finish_i8_small, dim3((unsigned)((fill_rows + kFinSmallBlockRows - 1) / kFinSmallBlockRows)), dim3(256), 0, s, d_P, p.m_pad, p.splits, m, n, p.S, p.nc, d_E, d_part, dC, ldc, fill_rows,
+                         trans ? 1 : 0, centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip);
+      break;
+    case I8Finish::transposed: {    // operand-swapped instantiations: transposed partial sums
+      dim3 grid((unsigned)((fill_rows + kFinTBlockRows - 1) / kFinTBlockRows), (unsigned)n);
+      hipLaunchKernelGGL(k_finish_i8_t, grid, dim3(256), 0, s, d_P, p.m_pad, p.e_pad, p.splits, m, n, p.S, p.nc, p.NT, d_E, d_part, dC, ldc, fill_rows, trans ? 1 : 0,
+                         centered ? 1 : 0, d_sumB, d_sumfB, d_f, skip, 0, TnSched{});
+      break;
+    }
   }
   MXA_HIP(hipGetLastError());
-  return guard == 2 ? 3 : 0;
+  return chain ? 3 : 0;
 }
 
 }  // namespace mxa

@@ -288,22 +288,21 @@ int launch_sparse_times_plink(const uint8_t *dP, size_t pitch, long entries, int
                               double *dC_slab, long ldc, long e_base, long e_count, hipStream_t s);
 // opt-in engine (mxa_set_engine(1) / MXA_ENGINE=i8, mxa_gemm_i8.hip): whole product by exact int8 slicing of B.
 // Asynchronous on s; ev0/ev1 (optional) are recorded around the dominant kernel.
-// guard: check on the device that every column of B is represented EXACTLY by the slicing (finite, dynamic range inside the digits, no
-// underflow in the recombination).  guard = 1: the host reads the verdict (one 4-byte copy + sync); if it is negative nothing is computed
-// and 2 is returned (the caller takes the fp64 path).  guard = 2: no host round trip -- the three kernels of the chain test the device
-// flag themselves and do nothing when it is set; 3 is returned with *flag_out = the device flag, and the caller enqueues the fp64
-// fallback with run_if_set = that flag.
-// S_override > 0 (engine 4): that many digits per column for every n (the caller has already proved them sufficient: guard = 0).
-// colsum_scratch (guard = 2, n <= 2 only; 128 n doubles): the column sums of the centring term are computed HERE, in the same pass over B as
-// the exponents and the guard (k_colstats_partial; finished inside k_slice_B) -- the caller must not have launched launch_colsums for them
-// chain (guard = 2, round 5): the verdict is a CLASS decided on the device (mxa_gemm_i8.hip: SliceFused) -- class 0 / 1: B is represented exactly by S0 / S1
-// digits per column (S1 = 0: no second class), class 2: neither.  One call enqueues the chain of ONE class (my_class; its kernels do nothing unless the
-// verdict is that class); `first`: this call also launches the statistics pass, publishes E, the column sums and the three flag words, and carries the fp64
-// chains of class 2 inside its k_slice_B launch.  The caller enqueues the chains of all classes back to back; nothing waits for the host.
+// chain != nullptr (the guarded route; n <= 6): the device checks that every column of B is represented EXACTLY by the slicing (finite, dynamic range inside
+// the digits, no underflow in the recombination) -- no host round trip: the kernels of the chain test a device flag themselves and do nothing when it is
+// set; 3 is returned with *flag_out = the device flag (class == 2), and the caller enqueues the fp64 fallback with run_if_set = that flag.
+// The verdict is a CLASS decided on the device (mxa_gemm_i8.hip: SliceFused) -- class 0 / 1: B is represented exactly by S0 / S1 digits per column (S1 = 0:
+// no second class), class 2: neither.  One call enqueues the chain of ONE class (my_class; its kernels do nothing unless the verdict is that class);
+// `first`: this call also launches the statistics pass, publishes E, the column sums and the three flag words, and carries the fp64 chains of class 2 inside
+// its k_slice_B launch.  The caller enqueues the chains of all classes back to back; nothing waits for the host.
+// colsum_scratch (with a chain; 128 n doubles): the column sums of the centring term are computed HERE, in the same pass over B as the exponents and the
+// guard (k_colstats_partial; finished inside k_slice_B) -- the caller must not have launched launch_colsums for them.
+// S_override > 0 (engine 4, no chain): that many digits per column for every n (the caller has already proved them sufficient).
+// Returns 0 (enqueued, no chain), 3 (a chain is enqueued), 1 (error), 2 (the planner declines: nothing enqueued, see G_tn below).
 struct I8Chain { int S0 = 0, S1 = 0, my_class = 0; bool first = true; bool fp64_rows = true; };   // fp64_rows: verdict class 2 is served by the fp64 chains inside the first chain's k_slice_B launch (false: by gated launches of the caller)
 struct I8Opts {   // (the members are described above and below; splits_out: the K splits of the plan that ran)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int *splits_out = nullptr, guard = 0;
+  int *splits_out = nullptr;
   const int **flag_out = nullptr;
   double *colsum_scratch = nullptr;
   int S_override = 0;
@@ -315,7 +314,7 @@ int gemm_i8_device(const PackedMatrix &G, bool trans, int n, const double *dB, l
                    double *d_sumfB, const double *d_f, Workspace &w, hipStream_t s, const I8Opts &o = {});
 // workspace for a chain with S digits (0: the default of n), before anything is enqueued; 2: the transposed-operand form declines this tile count
 int gemm_i8_reserve(const PackedMatrix &G, int n, int S, const PackedMatrix *G_tn, Workspace &w, hipStream_t s);
-// stats_part (guard = 0): the column maxima / minima of B are already there (k_colmax_partial's layout, 128 n doubles; the caller's launch_colspan made them to
+// stats_part (no chain): the column maxima / minima of B are already there (k_colmax_partial's layout, 128 n doubles; the caller's launch_colspan made them to
 // choose S): only the exponents are derived, no second pass over B
 // G_tn: the OTHER stored orientation (rows = the K index); the main kernel then runs in the transposed-operand form k_gemm_i8_tn, one launch per tile of 32
 // expanded columns.  Returns 2 (nothing enqueued) when that would take more passes than the fp64 MFMA tile costs or the plan has several column chunks.

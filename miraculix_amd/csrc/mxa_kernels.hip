@@ -13,6 +13,7 @@
 //
 // gfx950 only; wave64; no CUDA compatibility layer.
 #include "mxa_internal.h"
+#include "mxa_lds.h"
 #include "mxa_queue.h"
 #include <algorithm>
 #include <cstdio>
@@ -294,32 +295,13 @@ int launch_colsums(const double *dB, long ldb, long k, int n, const double *d_f,
 // (32 B per row).  Two LDS buffers; one vmcnt(0)+barrier per slab.  In the compute phase a wave only issues
 // ds_read_b64, 4 integer VALU per genotype fragment (VALU time is NOT hidden beside the fp64 MFMA: the DP pipe is
 // shared) and MFMAs.
-using gptr_t = const __attribute__((address_space(1))) void *;
-using lptr_t = __attribute__((address_space(3))) void *;
-
-// LDS-DMA with a wave-uniform 64-bit base in SGPRs, a per-lane 32-bit byte offset and a wave-uniform LDS byte address
-// (M0).  Written as asm so that the per-slab address arithmetic stays on the scalar unit; hipcc does not count this
-// load: the kernel waits with its own s_waitcnt vmcnt(0) before the barrier that precedes the first ds_read of the data.
-__device__ __forceinline__ void dma16_s(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory", "m0");
-}
-// non-temporal variant for the packed genotype stream (read once per pass, far larger than every cache): see mxa_gemm_i8.hip, idma16_stream.
-// Measured on the config-5 shard (profiles/r03_nt_stream_ab.txt): k_gemm_i8 at n = 1 0.96-0.97 ms with the hint against 1.01-1.02 without; the lookup kernel
-// k_lut 1.66 against 1.63 (LDS-bound: no gain, MXA_NT_LUT stays 0).  k_gemm is MFMA-bound and its time does not move (C2: 43.89-43.99 ms with, 43.87-44.02
-// without), but its HBM traffic does: the packed stream no longer pushes the B-fragment slabs, which every row block re-reads, out of the L2s --
-// 15.0 GB per launch by the counters instead of 18.9 (12.8 algorithmic; FETCH_SIZE calibrated for the hinted stream too: factor 2.000,
-// profiles/r03_pmc_calibration_nt.json).  MXA_NT_GEMM = 1.
+// The DMA primitives (dma16_s, dma16_p<NT>) and what the non-temporal hint measured: mxa_lds.h.
 #ifndef MXA_NT_LUT
 #define MXA_NT_LUT 0
 #endif
 #ifndef MXA_NT_GEMM
 #define MXA_NT_GEMM 1
 #endif
-template <bool NT>
-__device__ __forceinline__ void dma16_p(const void *sbase, uint32_t voff, uint32_t lds_addr) {
-  if (NT) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0 nt" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory", "m0");
-  else dma16_s(sbase, voff, lds_addr);
-}
 
 template <int A, int C>
 struct GemmCfg {

@@ -1,5 +1,5 @@
 // mxa_plan.h -- the HOST-ONLY planners of the library: how a product is cut into workgroup tiles, K splits (long pieces + tapered tail) and partial-sum
-// buffers (plan_gemm_host, plan_lut_host), and how the SNPs of a multi-device object are cut into shards (shard_blocks).  Plain C++ without any HIP
+// buffers (plan_gemm_host, plan_lut_host), the plans of the int8 kernels (plan_i8 with its split table and choice of finish, plan_i8_tn_host), and how the SNPs of a multi-device object are cut into shards (shard_blocks).  Plain C++ without any HIP
 // dependency, so that exactly this code is compiled by g++ with -fsanitize=address,undefined and swept over shapes on the CPU
 // (tests/host/plan_sweep.cpp, `make -C tests/host san`; reference practice: src/miraculix/makefile.c.mk:47-50).  The kernels' geometry constants
 // live here for the same reason.
@@ -263,6 +263,111 @@ inline TnSched plan_i8_tn_host(long indiv_slabs, long snp_rows, long slots, int 
     if (valid && (force_mode == 1 || (liked && (tiles_per_pass >= 2 || cost < best)))) s = t;
   }
   return s;
+}
+
+// ---- plan of the plain int8 kernel (k_gemm_i8, mxa_gemm_i8.hip): digits per column, column chunks, tiles of 32 expanded columns, K splits, and which
+// finish follows.  One workgroup multiplies one 256-row tile of the packed matrix by NT tiles over one K split.
+constexpr int kPlanTileRows = 256;                 // rows per tile of the packed layout
+constexpr int kPlanI8ABytes = kPlanTileRows * kPlanSlabK / 4;   // packed bytes of a stage (one slab of a tile): 8 KiB
+constexpr int kPlanI8MaxSplitStages = 32767;       // stages per K split at most.  int32 accumulators: 2 * 128 * (K per split) < 2^31
+// K splits at most: the cost model tries up to 64, the accumulators ask for ceil(stages / 32767), which stays within 64 up to 64 * 32767 stages
+// (268 M genotypes per row; the sweep shows the bound over its whole range and at that edge; beyond it the product is refused: plan_i8_full)
+constexpr int kMaxI8Splits = 64;
+struct I8Plan { int S, nc, nchunks, NT, e_pad, rowblocks, stages_total, stages_per_split, splits; long m_pad, T_total; };
+
+inline I8Plan plan_i8(long m, long k_pad, int n, int S_override) {
+  I8Plan p{};
+  const int S_env = S_override > 0 ? std::min(32, std::max(3, S_override)) : 0;
+  int S = S_env ? S_env : 7;                                     // 8 bits per digit: 7 digits = 56 bits below 2^E_j
+  // a tile of 32 expanded columns is the unit of work: for n <= 4 the kernel is HBM-bound with one tile, so the digits that fit the
+  // tile are free -- n = 1: 32 digits (256 bits: any entry down to 2^-200 of the column maximum keeps its whole mantissa), n = 2: 16
+  if (!S_env && n * S <= 32) S = std::min(32, 32 / n);
+  if (!S_override && n * S > 32 && S > 8) S = 8;
+  p.S = S;
+  const int max_nc = std::min(32, 256 / S);                     // <= 8 tiles of 32 expanded columns per pass, <= 32 columns per chunk
+  p.nchunks = (n + max_nc - 1) / max_nc;
+  p.nc = (n + p.nchunks - 1) / p.nchunks;
+  p.NT = (p.nc * S + 31) / 32;
+  p.e_pad = p.nchunks * p.NT * 32;
+  p.stages_total = (int)(k_pad / kPlanSlabK);
+  p.T_total = k_pad / 32;
+  p.rowblocks = (int)((m + kPlanTileRows - 1) / kPlanTileRows);
+  p.m_pad = (long)p.rowblocks * kPlanTileRows;
+  // K splits.  The kernel runs one workgroup per piece and the hardware keeps as many resident as the LDS allows (NT = 1: four per CU; the
+  // launch is HBM-bound there and more workgroups mean more bytes in flight).  Measured on the config-5 shard (n = 1): what matters is that the
+  // workgroup total fills whole rounds of the resident slots -- 391 row tiles x 5 splits = 1.91 rounds of 1024: 1.08 ms, x 6 = 2.29 rounds:
+  // 1.19 ms -- and, at equal fill, FEWER splits (less partial-sum traffic, fewer prologues): 977 tiles x 3: 1.05 ms, x 7: 1.16 ms.
+  const long max_splits = std::max<long>(1, p.stages_total / 32);
+  const bool direct_possible = p.nchunks == 1 && p.NT == 1 && p.nc <= 2;
+  // Cost model (round 3; replaces "fill the rounds to 3 %"): main kernel = the larger of the packed-matrix stream at ~6 TB/s and the int8
+  // work at the ~2.4 Pop/s the power limit allows, stretched by the unfilled part of the last round of resident slots and by a per-piece
+  // prologue worth ~6 stages; plus the partial sums, written once and read once by the finish (none when the single split of an n <= 2
+  // product finishes inside the kernel).  Fewest splits within 1 % of the best.
+  // (half-tile workgroups -- 128 rows, no K splits, the product finished inside the kernel -- were built in round 4 and removed in round 5: config-5 shard 'N'
+  // 1.36 ms against 0.965 with five splits: the digit slabs then cross L2 -> LDS as 2x the packed bytes and the DMA path sets the pace;
+  // profiles/r04_i8_half_tile_ab.txt)
+  const long units = (long)p.rowblocks * p.nchunks;
+  const long lds_wg = 3L * (kPlanI8ABytes + 4L * p.NT * 1024);
+  const long resident = 256L * (p.NT <= 4 ? std::max<long>(1, std::min<long>(4, 163840 / lds_wg)) : 1);
+  const double t_main = std::max((double)p.m_pad * (double)k_pad / 4.0 * p.nchunks / 6.0e12, 2.0 * (double)p.m_pad * (double)k_pad * p.e_pad / 2.4e15);
+  const double prologue = 6.0;
+  double best = 1e300;
+  long splits = 1;
+  for (long cand = 1; cand <= std::min<long>(max_splits, kMaxI8Splits); cand++) {
+    const long per = (p.stages_total + cand - 1) / cand, actual = (p.stages_total + per - 1) / per;
+    if (actual != cand) continue;
+    // Whole rounds of the resident slots.  Exception (round 4): ONE split of a product with at least two full rounds of row tiles -- its thinly
+    // filled last round costs max(its workgroups, 0.6 slots), not a whole round: 500k x 50k, n = 4 .. 6, 'T' (1954 tiles on 768 slots) runs 2-10 % faster
+    // uncut than in the three splits the whole-round rule chose (round 4, docs/HISTORY.md).  Products with few row tiles ('N') keep the
+    // whole-round rule: there the sweeps want MORE workgroups than the soft rule would ask for (config-5 shard 'N' 2 / 5 splits 1.04 / 0.96 ms).
+    const long wgs = units * actual, rounds = (wgs + resident - 1) / resident, full = wgs / resident, last = wgs - full * resident;
+    double quant = (double)(rounds * resident) / (double)wgs;
+    if (actual == 1 && full >= 2) quant = ((double)full * (double)resident + (last ? std::max((double)last, 0.6 * (double)resident) : 0.0)) / (double)wgs;
+    const double t_p = (actual == 1 && direct_possible) ? 0.0 : 2.0 * (double)actual * (double)p.m_pad * p.e_pad * 4.0 / 5.0e12 + 5.0e-6;
+    const double t = t_main * quant * ((double)per + prologue) / (double)per + t_p;
+    if (t < best * 0.99) { best = t; splits = cand; }
+  }
+  // ... and no piece beyond the bound that make_split_tab is given.  (Until the planner was swept this line divided by 32768 while the table was cut with
+  // 32767: for stage counts in (32767 s, 32768 s] the last piece came out one or two stages over the table's own limit -- still inside the accumulators' range,
+  // so no sum was wrong, and the sums do not depend on the cuts; K of 4.2 M genotypes and more.)
+  splits = std::max<long>(splits, (p.stages_total + kPlanI8MaxSplitStages - 1) / kPlanI8MaxSplitStages);
+  p.stages_per_split = (int)((p.stages_total + splits - 1) / splits);
+  p.splits = (p.stages_total + p.stages_per_split - 1) / p.stages_per_split;
+  return p;
+}
+
+// K splits of a launch as a table of stage boundaries (round 5).  The integer partial sums are exact, so ANY partition of K gives the same result bit for
+// bit -- which frees the lengths.  They are uniform: a taper (lengths from 1.4x to 0.6x of the mean, longest dispatched first) was measured: no gain for the
+// transposed-operand kernel, a LOSS for k_gemm_i8, whose XCD-dealt groups want equal work (profiles/r05_i8_taper_ab.txt: config-5 shard 'N' 0.964 -> 0.999 ms).
+// The table form is kept.  No piece is longer than max_len.
+struct SplitTab { int begin[kMaxI8Splits + 1]; };
+inline SplitTab make_split_tab(int stages_total, int splits, int max_len) {
+  SplitTab t{};
+  const double mean = (double)stages_total / splits;
+  double acc = 0.0;
+  t.begin[0] = 0;
+  for (int i = 0; i < splits; i++) {
+    acc += mean;
+    int b = i + 1 == splits ? stages_total : (int)(acc + 0.5);
+    b = std::max(b, t.begin[i] + 1);
+    b = std::min(b, std::min(stages_total - (splits - 1 - i), t.begin[i] + max_len));
+    t.begin[i + 1] = b;
+  }
+  // (max_len clipped a piece: push the remainder onto the later ones; they are shorter than the mean, so there is room unless mean itself is at the bound)
+  for (int i = splits; i > 0 && t.begin[i] > t.begin[i - 1] + max_len; i--) t.begin[i - 1] = t.begin[i] - max_len;
+  t.begin[splits] = stages_total;
+  return t;
+}
+
+// Which finish follows k_gemm_i8.  direct: one tile of at most two columns in ONE K split -- the workgroup holds the complete sums and stores C itself, no
+// launch; small: that tile in several splits, row-major partial sums, k_finish_i8_small; transposed: everything else -- the kernel stores P[split][e][row]
+// (the operand-swapped instantiations; the one-tile launch of three or more columns among them) and k_finish_i8_t reads it.  The planner never cuts a
+// one-tile product into column chunks (NT == 1 implies nchunks == 1: the sweep shows it), so these three are all there is.
+enum class I8Finish { direct, small, transposed };
+inline I8Finish i8_finish_route(const I8Plan &p) {
+  const bool small_tile = p.nchunks == 1 && p.NT == 1 && p.nc * p.S <= 32 && (p.nc == 1 || p.nc == 2);   // n <= 2: one tile
+  if (!small_tile) return I8Finish::transposed;
+  return p.splits == 1 ? I8Finish::direct : I8Finish::small;
 }
 
 inline void shard_blocks(long snps, int want, std::vector<long> &b, std::vector<long> &e) {

@@ -313,7 +313,7 @@ static int guarded_small(const Product &pr, int c0, int nc, const PackedMatrix *
   for (int cls = 0; cls < (ch.S1 ? 2 : 1); cls++) {
     ch.my_class = cls; ch.first = cls == 0;
     const bool lead = cls == 0;
-    const I8Opts o = {.ev0 = lead && timed ? pr.pe0 : nullptr, .ev1 = lead && timed ? pr.pe1 : nullptr, .splits_out = lead ? splits_out : nullptr, .guard = 2, .flag_out = &d_flag, .colsum_scratch = w.d_colpart, .G_tn = G_tn, .chain = &ch};
+    const I8Opts o = {.ev0 = lead && timed ? pr.pe0 : nullptr, .ev1 = lead && timed ? pr.pe1 : nullptr, .splits_out = lead ? splits_out : nullptr, .flag_out = &d_flag, .colsum_scratch = w.d_colpart, .G_tn = G_tn, .chain = &ch};
     const int rc = gemm_i8_device(G, pr.trans, nc, dBc, pr.ldb, dCc, pr.ldc, pr.fill_rows, pr.centered, d_sumB, d_sumfB, h->d_f, w, s, o);
     if (rc != 3) return 1;
   }

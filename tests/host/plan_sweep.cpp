@@ -2,7 +2,8 @@
 // shapes under AddressSanitizer / UndefinedBehaviorSanitizer on the CPU.  Reference practice: an -fsanitize=address build profile
 // (src/miraculix/makefile.c.mk:47-50) and valgrind targets for its test drivers (tests/dgemm_compressed/Makefile:80-85).  Never built for the GPU.
 // Invariants checked: every K split is non-empty and the splits cover the K slabs exactly once, in order; the padded extents hold the problem;
-// the piece count stays below the kernels' 2^30 limit; the partial-sum sizes do not overflow; the SNP shards are contiguous, aligned and complete.
+// the piece count stays below the kernels' 2^30 limit; the partial-sum sizes do not overflow; the SNP shards are contiguous, aligned and complete; the int8 plan's digits, tiles and chunks fit
+// the kernels' instantiations, its K splits fit the split table and the int32 accumulators, and its finish is one of the three that exist.
 #include "../../miraculix_amd/csrc/mxa_plan.h"
 #include <cstdio>
 #include <cstdlib>
@@ -78,7 +79,41 @@ static void check_tn(long indiv, long snps, long slots, int tiles, int force) {
   CHECK(bad_slots == 0, "indiv %ld snps %ld slots %ld tiles %d mode %d: %ld slot mismatches", indiv, snps, slots, tiles, s.mode, bad_slots);
 }
 
+// plan of k_gemm_i8 (plan_i8), its split table and the finish that follows
+static void check_i8(long m, long k_pad, int n, int S_override) {
+  const I8Plan p = plan_i8(m, k_pad, n, S_override);
+#define I8_AT "m %ld k_pad %ld n %d S_override %d: S %d nc %d nchunks %d NT %d splits %d", m, k_pad, n, S_override, p.S, p.nc, p.nchunks, p.NT, p.splits
+  CHECK(p.S >= 3 && p.S <= 32 && p.nc >= 1 && p.nc <= 32 && p.nc * p.S <= 32 * p.NT && p.NT >= 1 && p.NT <= 8, I8_AT);
+  CHECK((S_override <= 0 || p.S == std::min(32, std::max(3, S_override))) && (long)p.nchunks * p.nc >= n && p.e_pad == p.nchunks * p.NT * 32, I8_AT);
+  CHECK(p.m_pad % 256 == 0 && p.m_pad >= m && p.m_pad - m < 256 && (long)p.rowblocks * 256 == p.m_pad, I8_AT);
+  CHECK((long)p.stages_total * 128 == k_pad && p.T_total * 32 == k_pad, I8_AT);
+  CHECK(p.splits >= 1 && p.splits <= kMaxI8Splits && p.splits <= p.stages_total, I8_AT);
+  CHECK(p.NT > 1 || p.nchunks == 1, I8_AT);   // a one-tile product is never cut into column chunks: the row-major general finish had no other caller
+  if (p.splits >= 1 && p.splits <= kMaxI8Splits) {
+    const SplitTab t = make_split_tab(p.stages_total, p.splits, kPlanI8MaxSplitStages);
+    bool ok = t.begin[0] == 0 && t.begin[p.splits] == p.stages_total;
+    for (int i = 0; i < p.splits; i++) ok = ok && t.begin[i + 1] > t.begin[i] && t.begin[i + 1] - t.begin[i] <= kPlanI8MaxSplitStages;
+    CHECK(ok, I8_AT);
+  }
+  const I8Finish f = i8_finish_route(p);
+  const bool one_small_tile = p.nchunks == 1 && p.NT == 1 && p.nc <= 2;
+  CHECK(f == I8Finish::direct || f == I8Finish::small || f == I8Finish::transposed, I8_AT);
+  CHECK(f != I8Finish::direct || (p.splits == 1 && one_small_tile), I8_AT);
+  CHECK(f != I8Finish::small || (p.splits > 1 && one_small_tile), I8_AT);
+  CHECK(f != I8Finish::transposed || !one_small_tile, I8_AT);
+#undef I8_AT
+}
+
 int main() {
+  {   // int8 planner: every n and digit count; row counts around the 256-row tile edges; K from one stage to beyond two pieces of the int32 bound, and
+      // the K at which the accumulators alone ask for kMaxI8Splits pieces
+    const long i8_ms[] = {1, 255, 256, 257, 511, 512, 513, 100000, 250000, 1000001};
+    const long i8_stages[] = {1, 2, 31, 32, 33, 64, 100, 391, 782, 1954, 7813, 32767, 32768, 32769, 65534, 65535, 65536, 65537, 100000, 64L * 32767};
+    for (long m : i8_ms)
+      for (long st : i8_stages)
+        for (int n = 1; n <= 1024; n++)
+          for (int S = 0; S <= 40; S++) check_i8(m, st * 128, n, S);
+  }
   const long ms[] = {1, 3, 127, 128, 129, 500, 1000, 1003, 4096, 50000, 100000, 200000, 625000, 1000000, 2000000, 5000000, 33554432, 40000001};
   const long ks[] = {1, 100, 128, 129, 500, 1000, 12800, 25000, 50000, 100000, 200000, 1000000, 5000000, 40000000};
   const int ns[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 16, 17, 20, 31, 32, 33, 40, 64, 100, 127, 128, 129, 255, 256, 1000, 65535};

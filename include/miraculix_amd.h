@@ -87,9 +87,22 @@ void get_compressed_freq(void *compressed, double *f);
  * of the packed matrix and the result runs over the 2-bit entries of that row --
  *   transcompressed in {N,n}: C (nIdx x indiv, ld Ldc) = S (nIdx x snps)  * Z^T, packed matrix = plink;
  *   transcompressed in {T,t,Y,y}: C (nIdx x snps, ld Ldc) = S (nIdx x indiv) * Z, packed matrix = plink_transposed.
- * rowIdxB (nIdx + 1 entries) / colIdxB / B are ZERO-based CSR; C is zero-filled over Ldc x columns.  transsparse must be N
- * (the reference aborts otherwise; so does this).  Only the packed matrix that is used needs to be non-NULL.  Pointers may be
- * host or device.  Padding bits of the packed rows: IGNORED.  Errors: message on stderr, C unwritten, mxa_last_error() != 0. */
+ * rowIdxB (nIdx + 1 entries) / colIdxB / B are ZERO-based CSR; C is zero-filled over Ldc x columns, also when nIdx == 0 (as the
+ * reference, which clears C before it looks at nIdx).  The columns of a sparse row need not be sorted or distinct: a column stored
+ * twice is added twice.  nIdx is bounded by int alone.  transsparse must be N (the reference aborts otherwise; so does this).  Only
+ * the packed matrix that is used needs to be non-NULL.  Each of the packed matrix, rowIdxB, colIdxB, B and C may be a host or a
+ * device pointer, independently.  Padding bits of the packed rows: IGNORED.
+ * Summation order: CSR order, one fused multiply-add per stored entry --
+ *     acc = 0;  for t = rowIdxB[j] .. rowIdxB[j+1]-1 ascending:  acc = fma(B[t], z(colIdxB[t], e), acc);  C[j + e*Ldc] = acc
+ * with z in {0, 1, 2} (00 -> 0, 01 = missing -> 0, 10 -> 1, 11 -> 2).  B[t] * z is exact, so every element is the plain
+ * left-to-right fp64 sum of its row's terms: the same bits from run to run, for every pointer kind and for every piece size of the
+ * host staging.  A host packed matrix is uploaded as the rows S refers to, through a bounce buffer of 256 MiB or
+ * MXA_SPARSE_CHUNK_BYTES bytes (at least one row); a host C leaves through a device buffer of 1 GiB or MXA_SPARSE_SLAB_BYTES
+ * bytes, in slabs of a multiple of 512 columns (at least 512).  Both variables are read per call; under PRINT_LEVEL > 0 the call
+ * prints how many chunks and slabs it ran in.
+ * Errors (message on stderr, C unwritten, mxa_last_error() != 0): a NULL packed matrix, rowIdxB or C, snps or indiv < 1,
+ * nIdx < 0, rowIdxB[0] != 0, rowIdxB decreasing, NULL colIdxB or B with stored entries, a column outside [0, rows): 1;
+ * Ldc < nIdx: 7. */
 void sparse_times_plink(char *transsparse, char *transcompressed, char *plink, char *plink_transposed, int snps, int indiv,
                         int nIdx, int *rowIdxB, int *colIdxB, double *B, double *C, int Ldc);
 

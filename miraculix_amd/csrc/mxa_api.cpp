@@ -86,6 +86,7 @@ void debug_info(const char *fmt, ...) {
   vprintf(fmt, ap);
   printf("\n");
   va_end(ap);
+  fflush(stdout);   // (a caller that reads the line from a pipe or a file sees it when the call returns)
 }
 
 thread_local CallClock *tl_call_clock = nullptr;
@@ -291,6 +292,12 @@ struct DevBuf {   // frees on scope exit
   ~DevBuf() { if (p) (void)hipFree(p); }
   int alloc(size_t bytes) { MXA_HIP(hipMalloc(&p, bytes ? bytes : 1)); return 0; }
 };
+// size of one piece of the host staging, read per call: MXA_SPARSE_CHUNK_BYTES (the bounce buffer of the gathered packed rows, default 256 MiB) and
+// MXA_SPARSE_SLAB_BYTES (the device buffer a host C leaves through, default 1 GiB).  A piece size changes how often the loops run, never a result.
+size_t sparse_piece_bytes(const char *name, size_t dflt) {
+  const char *e = getenv(name);
+  return e && atoll(e) > 0 ? (size_t)atoll(e) : dflt;
+}
 }  // namespace
 
 static int sparse_times_plink_impl(bool tcompressed, const uint8_t *plink, const uint8_t *plink_transposed, int snps, int indiv, int nIdx,
@@ -303,10 +310,19 @@ static int sparse_times_plink_impl(bool tcompressed, const uint8_t *plink, const
   const uint8_t *P = tcompressed ? plink_transposed : plink;
   const long rows = tcompressed ? indiv : snps, entries = tcompressed ? snps : indiv;
   if (!P || !rowIdxB || !C || snps <= 0 || indiv <= 0 || nIdx < 0) { set_error(1, "sparse_times_plink: invalid argument"); return 1; }
-  if (nIdx == 0) return 0;
   if (ldc < nIdx) { set_error(7, "sparse_times_plink: Ldc %ld < nIdx %d", ldc, nIdx); return 1; }
   const int dev = select_device();
   if (dev < 0) return 1;
+  if (nIdx == 0) {   // no sparse row: the zero-fill of Ldc x entries is all there is (the reference memsets before it looks at nIdx)
+    const size_t bytes = sizeof(double) * (size_t)ldc * (size_t)entries;
+    if (bytes && is_device_ptr(C)) {
+      MXA_HIP(hipMemsetAsync(C, 0, bytes, nullptr));
+      MXA_HIP(hipStreamSynchronize(nullptr));
+    } else if (bytes) {
+      memset(C, 0, bytes);
+    }
+    return 0;
+  }
   const size_t pitch = ((size_t)entries + 3) / 4;
   // CSR arrays on the host for validation
   std::vector<int> h_row((size_t)nIdx + 1);
@@ -330,7 +346,9 @@ static int sparse_times_plink_impl(bool tcompressed, const uint8_t *plink, const
     for (size_t u = 0; u < used.size(); u++) remap[used[u]] = (int)u;
     for (long t = 0; t < nnz; t++) h_col[t] = remap[h_col[t]];
     if (dP.alloc(used.size() * pitch)) return 1;
-    const size_t rows_per_chunk = std::max<size_t>(1, ((size_t)256 << 20) / pitch);
+    const size_t rows_per_chunk = std::max<size_t>(1, sparse_piece_bytes("MXA_SPARSE_CHUNK_BYTES", (size_t)256 << 20) / pitch);
+    debug_info("sparse_times_plink: %zu of %ld packed rows uploaded in %zu chunk(s) of at most %zu rows", used.size(), rows,
+               (used.size() + rows_per_chunk - 1) / rows_per_chunk, rows_per_chunk);
     std::vector<uint8_t> bounce(std::min(rows_per_chunk, std::max<size_t>(1, used.size())) * pitch);
     for (size_t u0 = 0; u0 < used.size(); u0 += rows_per_chunk) {
       const size_t cnt = std::min(rows_per_chunk, used.size() - u0);
@@ -352,11 +370,12 @@ static int sparse_times_plink_impl(bool tcompressed, const uint8_t *plink, const
     MXA_HIP(hipStreamSynchronize(s));
     return 0;
   }
-  // host C: slabs of columns through a device buffer of at most 1 GiB
-  long e_slab = std::max<long>(512, (((long)1 << 30) / (8 * ldc)) / 512 * 512);
+  // host C: slabs of columns (multiples of 512, at least 512) through a device buffer of at most 1 GiB or MXA_SPARSE_SLAB_BYTES
+  long e_slab = std::max<long>(512, ((long)sparse_piece_bytes("MXA_SPARSE_SLAB_BYTES", (size_t)1 << 30) / (8 * ldc)) / 512 * 512);
   e_slab = std::min(e_slab, (entries + 511) / 512 * 512);
+  debug_info("sparse_times_plink: host C in %ld slab(s) of at most %ld columns", (entries + e_slab - 1) / e_slab, e_slab);
   DevBuf dC;
-  if (dC.alloc(sizeof(double) * (size_t)ldc * (size_t)e_slab)) return 1;
+  if (dC.alloc(sizeof(double) * (size_t)ldc * (size_t)std::min(e_slab, entries))) return 1;   // (the kernel stores no column at or beyond `entries`)
   for (long e0 = 0; e0 < entries; e0 += e_slab) {
     const long cnt = std::min(e_slab, entries - e0);
     if (launch_sparse_times_plink(d_packed, pitch, entries, nIdx, (const int *)dRow.p, (const int *)dCol.p, (const double *)dVal.p, (double *)dC.p, ldc, e0, cnt, s)) return 1;

@@ -5,7 +5,9 @@
 // Workgroup = 16 sparse rows x 512 entries (128 packed bytes).  Wave w takes sparse rows w, w+4, ...; a lane takes 2 packed bytes
 // (8 entries), so one wave-load is a 128-byte run of the packed row; the CSR entries of a row are wave-uniform (scalar loads).
 // Sums are accumulated in CSR order -- the order of the reference's loop over the stored entries -- and transposed through LDS so
-// that the store to the column-major C runs along the sparse-row index (128-byte runs).
+// that the store to the column-major C runs along the sparse-row index (128-byte runs).  gridDim.y holds at most 65535 row blocks: a launch takes its first
+// row block (jblk0), as launch_in_block_chunks hands other kernels their first workgroup, and more sparse rows than 65535 x 16 run in consecutive pieces.
+#include <algorithm>
 #include "mxa_internal.h"
 
 namespace mxa {
@@ -13,18 +15,19 @@ namespace mxa {
 constexpr int kSpJ = 16;      // sparse rows per workgroup
 constexpr int kSpE = 512;     // entries per workgroup
 constexpr int kSpPitch = kSpE + 1;
+constexpr long kSpMaxGridY = 65535;   // row blocks of one launch (gridDim.y)
 
 __global__ void __launch_bounds__(256) k_sparse_times_plink(const uint8_t *__restrict__ P, size_t pitch, long entries, int nIdx, const int *__restrict__ rowIdx,
                                                             const int *__restrict__ colIdx, const double *__restrict__ val, double *__restrict__ C,
-                                                            long ldc, long e_base) {
+                                                            long ldc, long e_base, long jblk0) {
   __shared__ double tile[kSpJ * kSpPitch];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long e0 = (long)blockIdx.x * kSpE;            // first entry of this block (relative to the slab's e_base)
-  const int j0 = blockIdx.y * kSpJ;
+  const long j0 = (jblk0 + blockIdx.y) * kSpJ;
   const long byte0 = (e_base + e0) / 4 + 2 * lane;    // e_base and e0 are multiples of 4
   const long nbytes = (entries + 3) / 4;
   for (int jj = wave; jj < kSpJ; jj += 4) {
-    const int j = j0 + jj;
+    const long j = j0 + jj;
     double acc[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) acc[i] = 0.0;
@@ -69,9 +72,11 @@ __global__ void k_zero_ld_rows(double *__restrict__ C, long ldc, int nIdx, long 
 int launch_sparse_times_plink(const uint8_t *dP, size_t pitch, long entries, int nIdx, const int *d_rowIdx, const int *d_colIdx, const double *d_val,
                               double *dC_slab, long ldc, long e_base, long e_count, hipStream_t s) {
   if (e_count <= 0 || nIdx <= 0) return 0;
-  dim3 grid((unsigned)((e_count + kSpE - 1) / kSpE), (unsigned)((nIdx + kSpJ - 1) / kSpJ));
-  if (grid.y > 65535) { set_error(8, "sparse_times_plink: more than %d sparse rows are not supported", 65535 * kSpJ); return 1; }
-  hipLaunchKernelGGL(k_sparse_times_plink, grid, dim3(256), 0, s, dP, pitch, entries, nIdx, d_rowIdx, d_colIdx, d_val, dC_slab, ldc, e_base);
+  const long jblocks = ((long)nIdx + kSpJ - 1) / kSpJ;
+  for (long jb0 = 0; jb0 < jblocks; jb0 += kSpMaxGridY) {
+    dim3 grid((unsigned)((e_count + kSpE - 1) / kSpE), (unsigned)std::min<long>(kSpMaxGridY, jblocks - jb0));
+    hipLaunchKernelGGL(k_sparse_times_plink, grid, dim3(256), 0, s, dP, pitch, entries, nIdx, d_rowIdx, d_colIdx, d_val, dC_slab, ldc, e_base, jb0);
+  }
   if (ldc > nIdx) {
     const long tot = (ldc - nIdx) * e_count;
     hipLaunchKernelGGL(k_zero_ld_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, dC_slab, ldc, nIdx, e_count);

@@ -576,6 +576,48 @@ int mxa_assoc_basis(int indiv, const double *W, long ldw, int q, double *Q, long
 int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta, double *se,
                      double *tstat, long ldo, int *nobs, int *dof);
 
+/* Association scan for binary traits: the score test of a generalized linear null model on packed genotypes.  The null model is fitted ONCE per trait
+ * (mxa_assoc_logistic_null for logistic regression; any other GLM null may be supplied by the caller); the scan then needs per SNP only inner products of the
+ * genotype with fixed columns.  plink, the PLINK coding, the padding fields and x_s (missing calls replaced by mu = Sz / N) are those of mxa_assoc_linear.
+ * Per trait c = 0 .. n-1 the caller supplies: the null residual r_c = column c of R (indiv x n, ldr >= indiv); the working weight w_c = column c of Wt
+ * (indiv x n, ldw >= indiv); kh >= 0 projection columns h_{c,0..kh-1} = the columns c kh .. c kh + kh - 1 of H (indiv x n kh, ldh >= indiv; NULL iff kh == 0),
+ * built so that sum_j (h_{c,j}^T x)^2 = x^T W C (C^T W C)^-1 C^T W x for the null design C and W = diag(w_c).  All column-major.
+ * Per SNP, exact integers from popcounts of the raw row: N, c1, c2, Sz = c1 + 2 c2.  Per SNP and column b of B = [R | Wt | H] (n (kh + 2) columns):
+ * D_b = sum_i z_i b_i (z = the allele count, missing as 0: the library's uncentred 'T' product on a one-shot packed object, whatever setOptions_compressed
+ * said) and M_b = sum over the SNP's missing individuals of b_i.  Per SNP and weight column c: E_c = sum over the individuals with code 11 of w_{c,i}.  E_c and
+ * M_b are summed in an order fixed by indiv (and kh, n) alone, no atomics.  Then, every operation rounded once, in this order:
+ *     mu  = Sz / N
+ *     U   = fma(mu, M_r, D_r)
+ *     s2  = fma(2.0, E_c, D_w)                 (sum w z^2 = sum w z + 2 sum_{z = 2} w)
+ *     m2  = mu * mu
+ *     sxx = fma(m2, M_w, s2)
+ *     for j = 0 .. kh-1 ascending:  a = fma(mu, M_hj, D_hj);  sxx = fma(-a, a, sxx)
+ *     V   = sxx
+ *     z   = U / sqrt(V)
+ * score = U, var = V, zstat = z.  There is no special case: N == 0, V <= 0 and monomorphic SNPs give what the arithmetic gives; callers filter such SNPs.
+ * p-values and Firth / saddle-point corrections are a wrapper's business (-|z| orders a clump).  Results are identical from run to run, between host and
+ * device pointers and for every row-chunk size of the staging (MXA_ASSOC_CHUNK_ROWS applies as for mxa_assoc_linear); they are NOT promised bit-identical
+ * between different column counts n (kh + 2).
+ * mxa_assoc_score: score, var, zstat: snps x n column-major, ldo >= snps; each optional, at least one required, those given all host or all device pointers;
+ *   nothing is written beyond row snps - 1 of a column or beyond column n - 1.  nobs (optional, snps ints, host or device) receives N.  plink, R, Wt and H are
+ *   host or device pointers, each independently.  Errors (return 1, mxa_last_error() == 1, outputs untouched, all decided before a device is selected): NULL
+ *   plink, R or Wt; snps, indiv or n below 1; kh < 0; H == NULL with kh > 0; n (kh + 2) > 65535; a leading dimension below its extent; indiv > 47 453 132; all
+ *   three result pointers NULL; mixed host and device result pointers.  12: not enough device memory (what mxa_assoc_linear lists, and the snps x n array E).
+ *   Runs on the selected device.
+ * mxa_assoc_logistic_null (host only, no device needed): fits logit P(y_i = 1) = (C gamma)_i, C = [1 | W], W indiv x q (ldw >= indiv; NULL iff q == 0), y
+ *   exactly 0 or 1, by Newton / IRLS: start at the intercept logit(ybar) and zeros; each step solves C^T W C delta = C^T (y - p) by Cholesky and is halved while
+ *   the deviance rises (by more than 2^-50 of itself, the rounding of the sum; at most 20 halvings); stop when max_j |delta_j| <= tol max(1, max_j |gamma_j|).
+ *   Sums are carried in long double.  Outputs: gamma (q + 1), r = y - p^, w = p^ (1 - p^) (indiv each), H (indiv x (q + 1), ldh >= indiv) = diag(w) C L^-T with L
+ *   the lower Cholesky factor of C^T diag(w) C -- so kh = q + 1, H^T x = L^-1 C^T W x, and C^T H = L; iters (optional) = the Newton steps taken.  Errors (return
+ *   1, mxa_last_error() == 1, outputs untouched, the message names the cause and the column): NULL pointers; indiv < 1, q < 0, indiv <= q + 1; a leading dimension
+ *   below indiv; a y that is not exactly 0 or 1; all y equal; a non-finite covariate; C^T diag(w) C not positive definite (a pivot at most indiv 2^-52 times its
+ *   diagonal entry: a constant or dependent column); no convergence within max_iter steps (separation).  12: not enough host memory for the work arrays (outputs
+ *   untouched). */
+int mxa_assoc_score(const unsigned char *plink, int snps, int indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
+                    double *score, double *var, double *zstat, long ldo, int *nobs);
+int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ldw, int q, double tol, int max_iter, double *gamma, double *r, double *w, double *H,
+                            long ldh, int *iters);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -1,5 +1,6 @@
 """Association scan (C entries mxa_assoc_basis, mxa_assoc_linear): per-SNP linear regression y ~ 1 + covariates + x_s on packed genotypes, missing calls
-imputed by the SNP's mean.  The definition, the operation order and what is exact: include/miraculix_amd.h."""
+imputed by the SNP's mean; and, for binary traits, the score test of a logistic null model fitted once per trait (mxa_assoc_logistic_null, mxa_assoc_score).
+The definitions, the operation orders and what is exact: include/miraculix_amd.h."""
 import ctypes
 from collections import namedtuple
 
@@ -114,3 +115,112 @@ def assoc_linear(plink, snps, indiv, Y, covariates=None, Q=None, out=None):
         r = res[key].t() if _lib.is_torch_tensor(res[key]) else res[key].T
         return r.reshape(snps) if one_dim else r
     return AssocResult(shaped("beta"), shaped("se"), shaped("t"), nobs, int(dof.value))
+
+
+# ---- binary traits: the score test (C entries mxa_assoc_logistic_null, mxa_assoc_score)
+LogisticNull = namedtuple("LogisticNull", "gamma r w H iters")
+AssocScoreResult = namedtuple("AssocScoreResult", "score var z nobs")
+
+
+def assoc_logistic_null(y, covariates=None, tol=1e-10, max_iter=50):
+    """The null model of the score test, on the host: logit P(y = 1) = [1 | covariates] gamma by Newton / IRLS.  y: (indiv,) of exactly 0 and 1; covariates:
+    (indiv, q) or (indiv,) or None.  Returns (gamma (q + 1,), r = y - p (indiv,), w = p (1 - p) (indiv,), H (indiv, q + 1) Fortran-ordered, iters): r, w and H
+    are what assoc_score takes for this trait.  Separation, a constant or dependent covariate and a y that is not 0 / 1 are errors."""
+    yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+    if yv.ndim != 1 or yv.shape[0] < 1:
+        raise ValueError(f"y needs to be (indiv,): {yv.shape}")
+    indiv = yv.shape[0]
+    Wf, q = None, 0
+    if covariates is not None:
+        W = np.asarray(covariates, dtype=np.float64)
+        if W.ndim == 1:
+            W = W.reshape(-1, 1)
+        if W.ndim != 2 or W.shape[0] != indiv:
+            raise ValueError(f"covariates need to be ({indiv}, q) or ({indiv},): {W.shape}")
+        q = int(W.shape[1])
+        Wf = np.asfortranarray(W) if q else None
+    if indiv <= q + 1:
+        raise ValueError(f"indiv needs to exceed q + 1: indiv {indiv}, q {q}")
+    gamma, r, w = np.zeros(q + 1), np.zeros(indiv), np.zeros(indiv)
+    H = np.zeros((indiv, q + 1), dtype=np.float64, order="F")
+    iters = ctypes.c_int(0)
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_logistic_null(indiv, _lib.ptr(yv), _lib.ptr(Wf), indiv, q, float(tol), int(max_iter), _lib.ptr(gamma), _lib.ptr(r), _lib.ptr(w), _lib.ptr(H),
+                                     indiv, ctypes.byref(iters)), "mxa_assoc_logistic_null")
+    return LogisticNull(gamma, r, w, H, int(iters.value))
+
+
+def assoc_score(plink, snps, indiv, R, Wt, H=None, out=None):
+    """score U, var V, z = U / sqrt(V) (each (snps, n), or (snps,) for a one-dimensional R) and nobs (snps,) int32 of the score test of every SNP against the
+    null models of n traits.  plink: as for assoc_linear.  R, Wt: (indiv, n) or (indiv,) float64 null residuals and working weights; H: (indiv, n kh) projection
+    columns, trait c owning the columns c kh .. c kh + kh - 1 (None: kh = 0); numpy or torch, host or device, each independently.  The results are numpy
+    arrays, or torch tensors on R's device when R is a device tensor.  out: a dict with any of the keys "score", "var", "z", as for assoc_linear."""
+    snps, indiv = int(snps), int(indiv)
+    if snps < 1 or indiv < 1:
+        raise ValueError(f"snps and indiv need to be positive: {snps}, {indiv}")
+    if indiv > ASSOC_MAX_INDIV:
+        raise ValueError(f"indiv needs to be at most {ASSOC_MAX_INDIV}: {indiv}")
+    if int(np.prod(plink.shape)) != snps * ((indiv + 3) // 4):
+        raise ValueError(f"Matrix has wrong dimensions: {tuple(plink.shape)}")
+    rc, n = _columns(R, indiv, "R")
+    wc, nw = _columns(Wt, indiv, "Wt")
+    if nw != n:
+        raise ValueError(f"Wt needs as many columns as R: {nw}, {n}")
+    kh, hc = 0, None
+    if H is not None and not (len(tuple(H.shape)) == 2 and H.shape[1] == 0):
+        hc, nh = _columns(H, indiv, "H")
+        if nh % n:
+            raise ValueError(f"H needs n kh columns: {nh} columns, n = {n}")
+        kh = nh // n
+    if n * (kh + 2) > 65535:
+        raise ValueError(f"n (kh + 2) needs to be at most 65535: n {n}, kh {kh}")
+    one_dim = len(tuple(R.shape)) == 1
+    on_device = _lib.is_torch_tensor(R) and R.is_cuda
+    res = {}
+    if out is not None:
+        if not out or any(key not in ("score", "var", "z") for key in out):
+            raise ValueError("out needs to hold at least one of the keys 'score', 'var', 'z'")
+        for key, o in out.items():
+            ot = o.t() if _lib.is_torch_tensor(o) else o.T
+            ok = tuple(o.shape) == (snps, n) and str(o.dtype).endswith("float64") and (ot.is_contiguous() if _lib.is_torch_tensor(o) else ot.flags.c_contiguous)
+            if not ok:
+                raise ValueError(f"out[{key!r}] needs to be a float64 ({snps}, {n}) result with contiguous columns")
+            res[key] = ot
+    else:
+        for key in ("score", "var", "z"):
+            if on_device:
+                import torch
+                res[key] = torch.zeros((n, snps), dtype=torch.float64, device=R.device)
+            else:
+                res[key] = np.zeros((n, snps), dtype=np.float64)
+    nobs = np.zeros(snps, dtype=np.int32)
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_score(_lib.ptr(plink), snps, indiv, _lib.ptr(rc), indiv, _lib.ptr(wc), indiv, _lib.ptr(hc), indiv, n, kh, _lib.ptr(res.get("score")),
+                             _lib.ptr(res.get("var")), _lib.ptr(res.get("z")), snps, _lib.ptr(nobs)), "mxa_assoc_score")
+
+    def shaped(key):
+        if key not in res:
+            return None
+        if out is not None:
+            return out[key]
+        r = res[key].t() if _lib.is_torch_tensor(res[key]) else res[key].T
+        return r.reshape(snps) if one_dim else r
+    return AssocScoreResult(shaped("score"), shaped("var"), shaped("z"), nobs)
+
+
+def assoc_logistic(plink, snps, indiv, Y, covariates=None):
+    """The logistic score test of every SNP for the 0 / 1 traits Y ((indiv, n) or (indiv,), numpy): the null model of each trait is fitted on the host
+    (assoc_logistic_null), R, Wt and H are stacked, and assoc_score scans.  Returns AssocScoreResult(score, var, z, nobs) as numpy arrays."""
+    Ya = np.asarray(Y, dtype=np.float64)
+    one_dim = Ya.ndim == 1
+    if Ya.ndim not in (1, 2) or Ya.shape[0] != int(indiv) or (Ya.ndim == 2 and Ya.shape[1] < 1):
+        raise ValueError(f"Y needs to be ({indiv},) or ({indiv}, n >= 1): {Ya.shape}")
+    Y2 = Ya.reshape(int(indiv), -1)
+    fits = [assoc_logistic_null(Y2[:, c], covariates) for c in range(Y2.shape[1])]
+    R = np.asfortranarray(np.stack([f.r for f in fits], axis=1))
+    Wt = np.asfortranarray(np.stack([f.w for f in fits], axis=1))
+    H = np.asfortranarray(np.concatenate([f.H for f in fits], axis=1))
+    res = assoc_score(plink, snps, indiv, R, Wt, H)
+    if one_dim:
+        return AssocScoreResult(res.score.reshape(-1), res.var.reshape(-1), res.z.reshape(-1), res.nobs)
+    return res

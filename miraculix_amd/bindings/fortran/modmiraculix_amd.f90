@@ -22,6 +22,7 @@ module modmiraculix_amd
  public :: mxa_ld_window_apply, mxa_ld_window_apply_pairwise
  public :: mxa_ld_op_bytes, mxa_ld_op_create, mxa_ld_op_create_pairwise, mxa_ld_op_from_rows, mxa_ld_op_rows, mxa_ld_op_apply, mxa_ld_op_solve, mxa_ld_op_free
  public :: mxa_assoc_basis, mxa_assoc_linear
+ public :: mxa_assoc_score, mxa_assoc_logistic_null
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -338,6 +339,25 @@ module modmiraculix_amd
    type(c_ptr), value, intent(in) :: plink, Y, Q, beta, se, tstat, nobs, dof
    integer(c_int), value, intent(in) :: snps, indiv, n, k
    integer(c_long), value, intent(in) :: ldy, ldq, ldo
+   integer(c_int) :: rc
+  end function
+  ! score test for binary traits: score, var, zstat (snps x n, ld ldo, each c_loc or c_null_ptr, one at least) from the null residuals R, the working weights
+  ! Wt (indiv x n each) and the projection columns H (indiv x n kh; c_null_ptr with kh = 0); nobs: snps ints or c_null_ptr
+  function mxa_assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs) bind(C, name='mxa_assoc_score') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, R, Wt, H, score, var, zstat, nobs
+   integer(c_int), value, intent(in) :: snps, indiv, n, kh
+   integer(c_long), value, intent(in) :: ldr, ldw, ldh, ldo
+   integer(c_int) :: rc
+  end function
+  ! the logistic null model (host only): gamma (ncov + 1), resid = y - p, wt = p (1 - p), Hmat (indiv x (ncov + 1), ld ldh) for mxa_assoc_score with kh = ncov + 1;
+  ! Wcov: indiv x ncov raw covariates or c_null_ptr with ncov = 0; iters: c_loc of one int or c_null_ptr.  (ncov, Wcov, resid, wt, Hmat: the header's q, W, r, w, H)
+  function mxa_assoc_logistic_null(indiv, y, Wcov, ldw, ncov, tol, max_iter, gamma, resid, wt, Hmat, ldh, iters) bind(C, name='mxa_assoc_logistic_null') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   integer(c_int), value, intent(in) :: indiv, ncov, max_iter
+   type(c_ptr), value, intent(in) :: y, Wcov, gamma, resid, wt, Hmat, iters
+   integer(c_long), value, intent(in) :: ldw, ldh
+   real(c_double), value, intent(in) :: tol
    integer(c_int) :: rc
   end function
 

@@ -2,12 +2,16 @@
 // 3.6e).  The fp64 product does the work: D = Z^T B for B = [Y~ | Q] is the library's own uncentred 'T' product on a one-shot object.  What the product cannot
 // know -- the missing calls -- comes from ONE streaming pass over the raw PLINK rows (k_assoc_scan): the exact counts N, c1, c2 of every SNP by popcount, and
 // M_b = the sum of b over the SNP's missing individuals.  k_assoc_finish turns D, M and the counts into beta, se and t in the documented operation order.
+// The score test for binary traits (mxa_assoc_score) is the same scan with B = [R | Wt | H] and one more sum per weight column, E = the weights
+// summed over the SNP's 11 fields (k_assoc_weights, dense); k_assoc_score_finish is its epilogue.  Its null model is host code: mxa_assoc_null_host.h.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include "../../include/miraculix_amd.h"
 #include "mxa_internal.h"
 #include "mxa_assoc_host.h"
+#include "mxa_assoc_null_host.h"
 #include "mxa_xprod.h"
 
 namespace mxa {
@@ -207,6 +211,110 @@ __global__ void __launch_bounds__(256) k_assoc_finish(long snps, int n, int k, c
   if (tstat) tstat[o] = __ddiv_rn(b, e);
 }
 
+// ---- the score test's one new sum: E[r, c] = sum over the individuals with code 11 in row r of w_c.  Dense, not a gather (11 fields are 10-25 % of all
+// fields): a workgroup takes kScoreRows SNP rows and C = kScoreCols weight columns (further columns: further passes).  Thread t owns the individuals of the
+// logical words t, t + 256, ... (the words of assoc_load_word, so every alignment gives the same sums; a wave's loads of one row are 1 KiB contiguous, 16 rows
+// in flight).  Of each row it keeps the 11 mask of its 64 individuals in two dwords: H & L of the lower 32 on the even bits, of the upper 32 on the odd bits.
+// Then, 16 individuals at a time in ascending order, it loads their C weights into registers once and adds them to the accumulators of all kScoreRows rows
+// under the mask (the weight's bits ANDed with 0 or -1).
+// Individuals at and beyond indiv carry the weight zero, whatever the padding fields hold.  Reduction: the wave's shuffles, then (w0 + w1) + (w2 + w3) through
+// the LDS; the order depends on indiv alone.  Rows [r0, r0 + kScoreRows) of the chunk's nrows; E is indexed by row0 + the row, as M is.
+constexpr int kScoreRows = 16, kScoreCols = 1;   // (two columns a pass need 256 VGPRs and more: one wave per SIMD)
+
+__global__ void __launch_bounds__(256) k_assoc_weights(const uint8_t *__restrict__ rows, long bps, long indiv, long row0, long nrows, const double *__restrict__ W,
+                                                        long ldw, double *__restrict__ E, long lde, long blk0) {
+  constexpr int C = kScoreCols;
+  __shared__ double red[4][kScoreRows * C];
+  const long r0 = (blk0 + blockIdx.x) * kScoreRows;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long nwords = (bps + 15) / 16;
+  double acc[kScoreRows][C];
+#pragma unroll
+  for (int r = 0; r < kScoreRows; r++)
+#pragma unroll
+    for (int c = 0; c < C; c++) acc[r][c] = 0.0;
+  for (long w = threadIdx.x; w < nwords; w += 256) {
+    unsigned p0[kScoreRows], p1[kScoreRows];      // individuals 0-15: even bits of p0, 16-31: even bits of p1, 32-47: odd bits of p0, 48-63: odd bits of p1
+#pragma unroll
+    for (int r = 0; r < kScoreRows; r++) {
+      p0[r] = 0u;
+      p1[r] = 0u;
+      if (r0 + r < nrows) {
+        const uint8_t *row = rows + (size_t)(r0 + r) * (size_t)bps;
+        const AssocWord a = assoc_load_word(row, w, bps, (int)(reinterpret_cast<uintptr_t>(row) & 15));
+        const unsigned long long lo = a.lo & (a.lo >> 1) & 0x5555555555555555ull, hi = a.hi & (a.hi >> 1) & 0x5555555555555555ull;
+        const unsigned long long p = lo | (hi << 1);
+        p0[r] = (unsigned)p;
+        p1[r] = (unsigned)(p >> 32);
+      }
+    }
+#pragma unroll 1
+    for (int step = 0; step < 4; step++) {          // 16 individuals a step: p0's even bits, then (p0, p1) <- (p1, p0 >> 1)
+      const long i0 = 64 * w + 16 * step, left = indiv - i0;
+      double wv[16][C];
+#pragma unroll
+      for (int k = 0; k < 16; k++)
+#pragma unroll
+        for (int c = 0; c < C; c++) wv[k][c] = k < left ? W[(size_t)c * (size_t)ldw + (size_t)(i0 + k)] : 0.0;
+#pragma unroll
+      for (int k = 0; k < 16; k++)                  // the rows innermost: consecutive adds go to different accumulators, none waits for the one before it
+#pragma unroll
+        for (int r = 0; r < kScoreRows; r++) {
+          const int m = -(int)((p0[r] >> (2 * k)) & 1u);
+#pragma unroll
+          for (int c = 0; c < C; c++) acc[r][c] += __hiloint2double(__double2hiint(wv[k][c]) & m, __double2loint(wv[k][c]) & m);
+        }
+#pragma unroll
+      for (int r = 0; r < kScoreRows; r++) {
+        const unsigned cur = p0[r];
+        p0[r] = p1[r];
+        p1[r] = cur >> 1;
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kScoreRows; r++)
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+      double v = acc[r][c];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+      if (lane == 0) red[wave][r * C + c] = v;
+    }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < kScoreRows * C && r0 + t / C < nrows)
+    E[(size_t)(t % C) * (size_t)lde + (size_t)(row0 + r0 + t / C)] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
+
+// ---- the score test's epilogue: one thread per (SNP, trait), every operation rounded once in the header's order.  Columns of D and M: c = R, n + c = Wt,
+// 2 n + c kh + j = H
+__global__ void __launch_bounds__(256) k_assoc_score_finish(long snps, int n, int kh, const int *__restrict__ nobs, const int *__restrict__ c1,
+                                                             const int *__restrict__ c2, const double *__restrict__ D, const double *__restrict__ M,
+                                                             const double *__restrict__ E, long ld, double *__restrict__ score, double *__restrict__ var,
+                                                             double *__restrict__ zstat, long ldo, long blk0) {
+  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
+  if (idx >= snps * (long)n) return;
+  const long s = idx % snps;
+  const int c = (int)(idx / snps);
+  const long N = nobs[s], Sz = (long)c1[s] + 2 * (long)c2[s];
+  const double mu = __ddiv_rn((double)Sz, (double)N);
+  const size_t ar = (size_t)s + (size_t)c * (size_t)ld, aw = (size_t)s + (size_t)(n + c) * (size_t)ld;
+  const double U = __fma_rn(mu, M[ar], D[ar]);
+  const double s2 = __fma_rn(2.0, E[ar], D[aw]);
+  const double m2 = __dmul_rn(mu, mu);
+  double sxx = __fma_rn(m2, M[aw], s2);
+  for (int j = 0; j < kh; j++) {
+    const size_t ah = (size_t)s + ((size_t)2 * (size_t)n + (size_t)c * (size_t)kh + (size_t)j) * (size_t)ld;
+    const double a = __fma_rn(mu, M[ah], D[ah]);
+    sxx = __fma_rn(-a, a, sxx);
+  }
+  const size_t o = (size_t)s + (size_t)c * (size_t)ldo;
+  if (score) score[o] = U;
+  if (var) var[o] = sxx;
+  if (zstat) zstat[o] = __ddiv_rn(U, __dsqrt_rn(sxx));
+}
+
 // ---- host side
 struct HandleHolder {                // the one-shot object is released on every exit path
   Handle *h = nullptr;
@@ -247,43 +355,127 @@ int scan_rows(const uint8_t *d_rows, long bps, long indiv, long row0, long nrows
   return 0;
 }
 
-int assoc_linear(const unsigned char *plink, long snps, long indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta, double *se,
-                 double *tstat, long ldo, int *nobs, int *dof, bool out_dev) {
-  const char *who = "mxa_assoc_linear";
-  const int dev = select_device();
-  if (dev < 0) return 1;
-  const int ncols = n + k, ncc = (ncols + kAssocCols - 1) / kAssocCols, max_n = std::min(ncols, 32);
-  const long bps = (indiv + 3) / 4;
-  int p_dev = -1;
-  const bool in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;   // rows in this device's memory are scanned where they lie
-  const long chunk_rows = in_place ? snps : assoc_chunk_rows(snps, bps);
-  // ---- memory pre-flight: the packed object, the staging chunk, B and its row-packed copy, D and M, the counts, the device copies of host results
-  const size_t b_bytes = sizeof(double) * (size_t)indiv * (size_t)ncols, bp_bytes = sizeof(AssocRow) * (size_t)indiv * (size_t)ncc;
-  const size_t dm_bytes = sizeof(double) * (size_t)snps * (size_t)ncols, cnt_bytes = sizeof(int) * 3 * (size_t)snps;
-  const size_t out_bytes = sizeof(double) * (size_t)snps * (size_t)n, bounce_bytes = in_place ? 0 : (size_t)chunk_rows * (size_t)bps;
-  const int n_out = (beta != nullptr) + (se != nullptr) + (tstat != nullptr);
-  const size_t need = object_footprint(snps, indiv, max_n, true) + bounce_bytes + b_bytes + bp_bytes + 2 * dm_bytes + cnt_bytes + (out_dev ? 0 : n_out * out_bytes);
-  size_t free_b = 0, total_b = 0;
-  MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu MB, free %zu MB", who, need >> 20, free_b >> 20); return 1; }
-
+// ---- what mxa_assoc_linear and mxa_assoc_score share: the device and the memory pre-flight, the one-shot object and the buffers of B (ncols columns), its
+// row-packed copy, D, M, the counts and the device copies of host results (n columns each); the scan and the staging chunk by chunk; the product; the way out
+struct AssocDriver {
+  const char *who;
+  long snps, indiv;
+  int ncols, n;
+  bool out_dev;
+  int dev = -1, ncc = 0, max_n = 0;
+  long bps = 0, chunk_rows = 0;
+  bool in_place = false;
+  size_t b_bytes = 0, bp_bytes = 0, dm_bytes = 0, cnt_bytes = 0, out_bytes = 0, bounce_bytes = 0;
   OneShotScope scope;
   HandleHolder obj;
-  { void *o = nullptr; if (begin_handle(snps, indiv, max_n, &o, dev)) return 1; obj.h = reinterpret_cast<Handle *>(o); }
-  Handle *h = obj.h;
-  hipStream_t s = h->stream;
-  XBuf bB, bBp, bD, bM, bCnt, bSmall, bFlag, bounce, bOut[3];
+  XBuf bB, bBp, bD, bM, bCnt, bFlag, bounce, bOut[3];
+  Handle *h = nullptr;
+  hipStream_t s = nullptr;
+  double *out_d[3] = {nullptr, nullptr, nullptr};
+  double *dB = nullptr, *dD = nullptr, *dM = nullptr;
+  int *dCnt = nullptr, *dFlag = nullptr;
+  AssocRow *dBp = nullptr;
+
+  AssocDriver(const char *who_, long snps_, long indiv_, int ncols_, int n_, bool out_dev_) : who(who_), snps(snps_), indiv(indiv_), ncols(ncols_), n(n_), out_dev(out_dev_) {}
+
+  // res: the caller's three results (nullable each); extra_bytes: device memory the caller allocates on top
+  int begin(const unsigned char *plink, double *const res[3], size_t extra_bytes) {
+    dev = select_device();
+    if (dev < 0) return 1;
+    ncc = (ncols + kAssocCols - 1) / kAssocCols;
+    max_n = std::min(ncols, 32);
+    bps = (indiv + 3) / 4;
+    int p_dev = -1;
+    in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;   // rows in this device's memory are scanned where they lie
+    chunk_rows = in_place ? snps : assoc_chunk_rows(snps, bps);
+    // ---- memory pre-flight: the packed object, the staging chunk, B and its row-packed copy, D and M, the counts, the device copies of host results
+    b_bytes = sizeof(double) * (size_t)indiv * (size_t)ncols;
+    bp_bytes = sizeof(AssocRow) * (size_t)indiv * (size_t)ncc;
+    dm_bytes = sizeof(double) * (size_t)snps * (size_t)ncols;
+    cnt_bytes = sizeof(int) * 3 * (size_t)snps;
+    out_bytes = sizeof(double) * (size_t)snps * (size_t)n;
+    bounce_bytes = in_place ? 0 : (size_t)chunk_rows * (size_t)bps;
+    const int n_out = (res[0] != nullptr) + (res[1] != nullptr) + (res[2] != nullptr);
+    const size_t need = object_footprint(snps, indiv, max_n, true) + bounce_bytes + b_bytes + bp_bytes + 2 * dm_bytes + cnt_bytes + (out_dev ? 0 : n_out * out_bytes) + extra_bytes;
+    size_t free_b = 0, total_b = 0;
+    MXA_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu MB, free %zu MB", who, need >> 20, free_b >> 20); return 1; }
+    { void *o = nullptr; if (begin_handle(snps, indiv, max_n, &o, dev)) return 1; obj.h = reinterpret_cast<Handle *>(o); }
+    h = obj.h;
+    s = h->stream;
+    if (bB.alloc(b_bytes) || bBp.alloc(bp_bytes) || bD.alloc(dm_bytes) || bM.alloc(dm_bytes) || bCnt.alloc(cnt_bytes) || bFlag.alloc(sizeof(int)) ||
+        (!in_place && bounce.alloc(bounce_bytes))) return 1;
+    for (int j = 0; j < 3; j++) {
+      out_d[j] = res[j];
+      if (!out_dev && res[j]) { if (bOut[j].alloc(out_bytes)) return 1; out_d[j] = (double *)bOut[j].p; }
+    }
+    dB = (double *)bB.p; dD = (double *)bD.p; dM = (double *)bM.p;
+    dCnt = (int *)bCnt.p; dFlag = (int *)bFlag.p;
+    dBp = (AssocRow *)bBp.p;
+    return 0;
+  }
+
+  // the row-packed copy of the finished B; M and the flag cleared
+  int pack_and_clear() {
+    k_assoc_pack<<<dim3((unsigned)((indiv + 255) / 256), ncc), 256, 0, s>>>(dB, indiv, ncols, indiv, dBp);
+    MXA_HIP(hipGetLastError());
+    MXA_HIP(hipMemsetAsync(dM, 0, dm_bytes, s));
+    MXA_HIP(hipMemsetAsync(dFlag, 0, sizeof(int), s));
+    return 0;
+  }
+
+  // ---- the scan and the staging of the product operand, chunk by chunk, then D = Z^T B.  The uncentred product needs no allele frequencies: the object is
+  // one without them (has_f cleared), which spares append_rows its own pass over the raw rows and makes a product that ignored tl_centered_override an error,
+  // not a result.  per_chunk(d_rows, r0, nr): the caller's own pass over the chunk's raw rows on the device (0, or 1 with the error set).
+  template <typename PerChunk>
+  int scan_and_multiply(const unsigned char *plink, PerChunk &&per_chunk) {
+    h->has_f = false;
+    bool seen_missing = false;
+    for (long r0 = 0; r0 < snps; r0 += chunk_rows) {
+      const long nr = std::min(chunk_rows, snps - r0);
+      const uint8_t *d_rows = plink + (size_t)r0 * (size_t)bps;
+      if (!in_place) {
+        MXA_HIP(hipMemcpyAsync(bounce.p, d_rows, (size_t)nr * (size_t)bps, hipMemcpyDefault, s));
+        d_rows = (const uint8_t *)bounce.p;
+      }
+      if (scan_rows(d_rows, bps, indiv, r0, nr, dBp, ncols, ncc, dM, snps, dCnt, dFlag, &seen_missing, s)) return 1;
+      if (per_chunk(d_rows, r0, nr)) return 1;
+      if (append_rows(h, d_rows, r0, nr, nullptr)) return 1;
+    }
+    if (end_handle(h)) return 1;
+    // in column chunks no wider than the object's max_n
+    for (int c0 = 0; c0 < ncols; c0 += max_n) {
+      const int w = std::min(max_n, ncols - c0);
+      if (gemm_any(h, true, w, dB + (size_t)c0 * (size_t)indiv, indiv, dD + (size_t)c0 * (size_t)snps, snps, snps, false, false)) return 1;
+    }
+    return 0;
+  }
+
+  // host results and nobs, then the end of the stream
+  int copy_out(double *const res[3], long ldo, int *nobs) {
+    if (!out_dev) {
+      const size_t ocol = sizeof(double) * (size_t)snps;
+      for (int j = 0; j < 3; j++)
+        if (res[j]) MXA_HIP(hipMemcpy2DAsync(res[j], sizeof(double) * (size_t)ldo, out_d[j], ocol, ocol, (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    if (nobs) MXA_HIP(hipMemcpyAsync(nobs, dCnt, sizeof(int) * (size_t)snps, hipMemcpyDefault, s));
+    MXA_HIP(hipStreamSynchronize(s));
+    return 0;
+  }
+};
+
+int assoc_linear(const unsigned char *plink, long snps, long indiv, const double *Y, long ldy, int n, const double *Q, long ldq, int k, double *beta, double *se,
+                 double *tstat, long ldo, int *nobs, int *dof, bool out_dev) {
+  AssocDriver d("mxa_assoc_linear", snps, indiv, n + k, n, out_dev);
+  double *const res[3] = {beta, se, tstat};
+  if (d.begin(plink, res, 0)) return 1;
+  const int ncols = n + k;
+  hipStream_t s = d.s;
+  XBuf bSmall;
   const size_t small_doubles = (size_t)ncols + (size_t)n + (size_t)n + (size_t)k * (size_t)n;   // T, syy, column sums, a = Q^T y
-  if (bB.alloc(b_bytes) || bBp.alloc(bp_bytes) || bD.alloc(dm_bytes) || bM.alloc(dm_bytes) || bCnt.alloc(cnt_bytes) || bSmall.alloc(sizeof(double) * small_doubles) ||
-      bFlag.alloc(sizeof(int)) || (!in_place && bounce.alloc(bounce_bytes))) return 1;
-  double *out_d[3] = {beta, se, tstat};
-  if (!out_dev)
-    for (int j = 0; j < 3; j++)
-      if (out_d[j]) { if (bOut[j].alloc(out_bytes)) return 1; out_d[j] = (double *)bOut[j].p; }
-  double *dB = (double *)bB.p, *dD = (double *)bD.p, *dM = (double *)bM.p;
+  if (bSmall.alloc(sizeof(double) * small_doubles)) return 1;
+  double *dB = d.dB;
   double *dT = (double *)bSmall.p, *dSyy = dT + ncols, *dSum = dSyy + n, *dA = dSum + n;
-  int *dCnt = (int *)bCnt.p, *dFlag = (int *)bFlag.p;
-  AssocRow *dBp = (AssocRow *)bBp.p;
 
   // ---- B = [Y~ | Q] on the device
   const size_t col = sizeof(double) * (size_t)indiv;
@@ -299,48 +491,59 @@ int assoc_linear(const unsigned char *plink, long snps, long indiv, const double
   }
   k_assoc_dots<<<dim3(1, n), 256, 0, s>>>(dB, indiv, dB, indiv, indiv, dSyy, 1, 1);
   k_assoc_dots<<<dim3(1, ncols), 256, 0, s>>>(nullptr, 0, dB, indiv, indiv, dT, 1, 0);
-  k_assoc_pack<<<dim3(iblocks, ncc), 256, 0, s>>>(dB, indiv, ncols, indiv, dBp);
-  MXA_HIP(hipGetLastError());
-  MXA_HIP(hipMemsetAsync(dM, 0, dm_bytes, s));
-  MXA_HIP(hipMemsetAsync(dFlag, 0, sizeof(int), s));
+  if (d.pack_and_clear()) return 1;
+  if (d.scan_and_multiply(plink, [](const uint8_t *, long, long) { return 0; })) return 1;
 
-  // ---- the scan and the staging of the product operand, chunk by chunk.  The uncentred product needs no allele frequencies: the object is one without them
-  // (has_f cleared), which spares append_rows its own pass over the raw rows and makes a product that ignored tl_centered_override an error, not a result.
-  h->has_f = false;
-  bool seen_missing = false;
-  for (long r0 = 0; r0 < snps; r0 += chunk_rows) {
-    const long nr = std::min(chunk_rows, snps - r0);
-    const uint8_t *d_rows = plink + (size_t)r0 * (size_t)bps;
-    if (!in_place) {
-      MXA_HIP(hipMemcpyAsync(bounce.p, d_rows, (size_t)nr * (size_t)bps, hipMemcpyDefault, s));
-      d_rows = (const uint8_t *)bounce.p;
-    }
-    if (scan_rows(d_rows, bps, indiv, r0, nr, dBp, ncols, ncc, dM, snps, dCnt, dFlag, &seen_missing, s)) return 1;
-    if (append_rows(h, d_rows, r0, nr, nullptr)) return 1;
-  }
-  if (end_handle(h)) return 1;
-
-  // ---- D = Z^T B, in column chunks no wider than the object's max_n
-  for (int c0 = 0; c0 < ncols; c0 += max_n) {
-    const int w = std::min(max_n, ncols - c0);
-    if (gemm_any(h, true, w, dB + (size_t)c0 * (size_t)indiv, indiv, dD + (size_t)c0 * (size_t)snps, snps, snps, false, false)) return 1;
-  }
   const long total = snps * (long)n;
   launch_in_block_chunks((total + 255) / 256, [&](unsigned nb, long b0) {
-    k_assoc_finish<<<nb, 256, 0, s>>>(snps, n, k, dCnt, dCnt + snps, dCnt + 2 * snps, dD, dM, snps, dT, dSyy, (double)(indiv - k - 2), out_d[0], out_d[1], out_d[2],
-                                      out_dev ? ldo : snps, b0);
+    k_assoc_finish<<<nb, 256, 0, s>>>(snps, n, k, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD, d.dM, snps, dT, dSyy, (double)(indiv - k - 2), d.out_d[0], d.out_d[1],
+                                      d.out_d[2], out_dev ? ldo : snps, b0);
   });
   MXA_HIP(hipGetLastError());
-  if (!out_dev) {
-    double *host[3] = {beta, se, tstat};
-    const size_t ocol = sizeof(double) * (size_t)snps;
-    for (int j = 0; j < 3; j++)
-      if (host[j]) MXA_HIP(hipMemcpy2DAsync(host[j], sizeof(double) * (size_t)ldo, out_d[j], ocol, ocol, (size_t)n, hipMemcpyDeviceToHost, s));
-  }
-  if (nobs) MXA_HIP(hipMemcpyAsync(nobs, dCnt, sizeof(int) * (size_t)snps, hipMemcpyDefault, s));
-  MXA_HIP(hipStreamSynchronize(s));
+  if (d.copy_out(res, ldo, nobs)) return 1;
   if (dof) *dof = (int)(indiv - k - 2);
   return 0;
+}
+
+// B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c
+int assoc_score(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
+                double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev) {
+  const int ncols = n * (kh + 2);
+  AssocDriver d("mxa_assoc_score", snps, indiv, ncols, n, out_dev);
+  double *const res[3] = {score, var, zstat};
+  const size_t e_bytes = sizeof(double) * (size_t)snps * (size_t)n;
+  if (d.begin(plink, res, e_bytes)) return 1;
+  hipStream_t s = d.s;
+  XBuf bE;
+  if (bE.alloc(e_bytes)) return 1;
+  double *dE = (double *)bE.p;
+  const size_t col = sizeof(double) * (size_t)indiv;
+  double *dW = d.dB + (size_t)n * (size_t)indiv;
+  MXA_HIP(hipMemcpy2DAsync(d.dB, col, R, sizeof(double) * (size_t)ldr, col, (size_t)n, hipMemcpyDefault, s));
+  MXA_HIP(hipMemcpy2DAsync(dW, col, Wt, sizeof(double) * (size_t)ldw, col, (size_t)n, hipMemcpyDefault, s));
+  if (kh > 0)
+    MXA_HIP(hipMemcpy2DAsync(d.dB + (size_t)2 * (size_t)n * (size_t)indiv, col, H, sizeof(double) * (size_t)ldh, col, (size_t)n * (size_t)kh, hipMemcpyDefault, s));
+  if (d.pack_and_clear()) return 1;
+  const long bps = d.bps;
+  auto weights = [&](const uint8_t *d_rows, long r0, long nr) -> int {          // E: kScoreCols weight columns a pass
+    for (int c0 = 0; c0 < n; c0 += kScoreCols) {
+      const double *w = dW + (size_t)c0 * (size_t)indiv;
+      double *e = dE + (size_t)c0 * (size_t)snps;
+      launch_in_block_chunks((nr + kScoreRows - 1) / kScoreRows, [&](unsigned nb, long b0) {
+        k_assoc_weights<<<nb, 256, 0, s>>>(d_rows, bps, indiv, r0, nr, w, indiv, e, snps, b0);
+      });
+      MXA_HIP(hipGetLastError());
+    }
+    return 0;
+  };
+  if (d.scan_and_multiply(plink, weights)) return 1;
+  const long total = snps * (long)n;
+  launch_in_block_chunks((total + 255) / 256, [&](unsigned nb, long b0) {
+    k_assoc_score_finish<<<nb, 256, 0, s>>>(snps, n, kh, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD, d.dM, dE, snps, d.out_d[0], d.out_d[1], d.out_d[2],
+                                            out_dev ? ldo : snps, b0);
+  });
+  MXA_HIP(hipGetLastError());
+  return d.copy_out(res, ldo, nobs);
 }
 
 }  // namespace
@@ -376,6 +579,51 @@ extern "C" int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv,
   int prev = -1;
   (void)hipGetDevice(&prev);
   const int rc = assoc_linear(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo, nobs, dof, on_dev != 0);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ldw, int q, double tol, int max_iter, double *gamma, double *r, double *w,
+                                       double *H, long ldh, int *iters) {
+  using namespace mxa;
+  clear_error();
+  const char *who = "mxa_assoc_logistic_null";
+  const char *wrong = assoc_logistic_null_args(indiv, y, W, ldw, q, gamma, r, w, H, ldh);
+  if (wrong) { set_error(1, "%s: %s", who, wrong); return 1; }
+  long bad = -1;
+  int rc = 0;
+  try {
+    rc = assoc_logistic_null_host(indiv, y, W, ldw, q, tol, max_iter, gamma, r, w, H, ldh, iters, &bad);
+  } catch (const std::bad_alloc &) {          // the work arrays (2 indiv long doubles) come before the first output is written
+    set_error(12, "%s: not enough host memory for the work arrays of %d individuals", who, indiv);
+    return 1;
+  }
+  if (rc == 2) { set_error(1, "%s: column %ld of W holds a non-finite entry", who, bad); return 1; }
+  if (rc == 3) { set_error(1, "%s: y[%ld] is not exactly 0 or 1", who, bad); return 1; }
+  if (rc == 4) { set_error(1, "%s: all entries of y are equal", who); return 1; }
+  if (rc == 5) {
+    if (bad == 0) set_error(1, "%s: C^T diag(w) C is not positive definite at the intercept", who);
+    else set_error(1, "%s: C^T diag(w) C is not positive definite: column %ld of W is constant or depends on the columns before it", who, bad - 1);
+    return 1;
+  }
+  if (rc == 6) { set_error(1, "%s: no convergence within %d iterations (separation?)", who, max_iter); return 1; }
+  return 0;
+}
+
+extern "C" int mxa_assoc_score(const unsigned char *plink, int snps, int indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n,
+                               int kh, double *score, double *var, double *zstat, long ldo, int *nobs) {
+  using namespace mxa;
+  clear_error();
+  const char *who = "mxa_assoc_score";
+  const char *bad = assoc_score_args(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo);
+  if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
+  int given = 0, on_dev = 0;
+  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat})
+    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
+  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var and zstat must be all host or all device pointers", who); return 1; }
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0);
   if (prev >= 0) (void)hipSetDevice(prev);
   return rc;
 }

@@ -1,6 +1,6 @@
 // mxa_assoc_host.h -- the host-only part of the association scan (mxa_assoc.hip): the covariate basis of mxa_assoc_basis and the argument rules of
-// mxa_assoc_linear.  Plain C++ without any HIP header, so that a stand-alone program can compile it for the CPU (tools/assoc_host_check.cpp, run under
-// -fsanitize=address,undefined).
+// mxa_assoc_linear and mxa_assoc_score (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
+// program can compile it for the CPU (tools/assoc_host_check.cpp, tools/assoc_score_host_check.cpp, run under -fsanitize=address,undefined).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -70,6 +70,21 @@ inline const char *assoc_linear_args(const void *plink, long snps, long indiv, c
   if (indiv - (long)k - 2 < 1) return "indiv - k - 2 degrees of freedom must be at least 1";
   if (indiv > kAssocMaxIndiv) return "indiv > 47 453 132 (4 indiv^2 >= 2^53)";
   if (!beta && !se && !tstat) return "beta, se and tstat are all NULL";
+  if (ldo < snps) return "ldo must be at least snps";
+  return nullptr;
+}
+
+// The same for mxa_assoc_score: B = [R | Wt | H] has n (kh + 2) columns.
+inline const char *assoc_score_args(const void *plink, long snps, long indiv, const void *R, long ldr, const void *Wt, long ldw, const void *H, long ldh, int n, int kh,
+                                    const void *score, const void *var, const void *zstat, long ldo) {
+  if (!plink || !R || !Wt) return "plink, R and Wt must not be NULL";
+  if (snps < 1 || indiv < 1 || n < 1) return "snps, indiv and n must be positive";
+  if (kh < 0) return "kh must not be negative";
+  if (kh > 0 && !H) return "H is NULL with kh > 0";
+  if ((long)n * ((long)kh + 2) > 65535) return "n (kh + 2) must be at most 65535";
+  if (ldr < indiv || ldw < indiv || (kh > 0 && ldh < indiv)) return "ldr, ldw and ldh must be at least indiv";
+  if (indiv > kAssocMaxIndiv) return "indiv > 47 453 132 (4 indiv^2 >= 2^53)";
+  if (!score && !var && !zstat) return "score, var and zstat are all NULL";
   if (ldo < snps) return "ldo must be at least snps";
   return nullptr;
 }

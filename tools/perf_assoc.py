@@ -8,7 +8,11 @@ Kernel times come from a run of its own under rocprofv3 --kernel-trace (tools/pr
 data set and shape and nothing else of the library; `perf_assoc.py summarize kernel_trace.csv` prints, for the second call of each, the time of every library
 kernel by name in dispatch order of first appearance (a call ends with k_assoc_finish).
 Model: the 'T' product of n + k columns + ceil((n + k) / 16) reads of the raw matrix at the 7.0 TB/s read ceiling + O(snps (n + k)) epilogue bytes.
-usage: perf_assoc.py snps indiv [reps | trace]   |   perf_assoc.py summarize kernel_trace.csv"""
+The score test (mxa_assoc_score) is the same script with `score` in front (tools/profile.sh assoc-score, assoc-score-kernels): shapes n = 1, q = 15
+and n = 4, q = 15 (kh = q + 1 projection columns per trait: 18 and 72 columns of B), beside mxa_assoc_linear at n = 1, k = 15 and the bare 'T' product of the same
+column counts, in column chunks of at most 32 as the entry itself multiplies.  Its summary puts the weight kernel (k_assoc_weights: E = the weights summed over
+the 11 fields) beside its model -- one read of the raw matrix at 7.0 TB/s plus snps x indiv masked adds per pass, one pass per trait -- and beside k_assoc_scan.
+usage: perf_assoc.py [score] snps indiv [reps | trace]   |   perf_assoc.py summarize kernel_trace.csv   |   perf_assoc.py summarize-score kernel_trace.csv"""
 import csv, ctypes, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,17 +23,20 @@ from bench import synth_plink_device
 
 
 
-def summarize(path):
+SCORE_SHAPES = ((1, 15), (4, 15))
+
+
+def summarize(path, last="k_assoc_finish", shapes=((1, 15), (16, 16)), second="k"):
     rows = [r for r in csv.DictReader(open(path)) if "mxa::" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     calls, cur = [], []
     for r in rows:
         name = re.sub(r"^.*?mxa::(\(anonymous namespace\)::)?", "", r["Kernel_Name"]).split("(")[0].split("<")[0]
         cur.append((name, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6))
-        if name == "k_assoc_finish":
+        if name == last:
             calls.append(cur)
             cur = []
-    labels = [f"{d}, n={n} k={k}" for d in ("no missing", "5 % missing") for n, k in ((1, 15), (16, 16))]
+    labels = [f"{d}, n={n} {second}={k}" for d in ("no missing", "5 % missing") for n, k in shapes]
     assert len(calls) == 2 * len(labels), (len(calls), "calls in the trace")
     for i, label in enumerate(labels):
         call, order, tot = calls[2 * i + 1], [], {}
@@ -46,6 +53,12 @@ def summarize(path):
 if sys.argv[1] == "summarize":
     summarize(sys.argv[2])
     sys.exit(0)
+if sys.argv[1] == "summarize-score":
+    summarize(sys.argv[2], "k_assoc_score_finish", SCORE_SHAPES, "q")
+    sys.exit(0)
+score = sys.argv[1] == "score"
+if score:
+    del sys.argv[1]
 snps, indiv = int(sys.argv[1]), int(sys.argv[2])
 trace = len(sys.argv) > 3 and sys.argv[3] == "trace"
 reps = int(sys.argv[3]) if len(sys.argv) > 3 and not trace else 5
@@ -111,6 +124,66 @@ Bd = torch.randn(nmax, indiv, dtype=torch.float64, device=dev)
 Cd = torch.empty(nmax, snps, dtype=torch.float64, device=dev)
 out = [torch.empty(16, snps, dtype=torch.float64, device=dev) for _ in range(3)]
 nobs = torch.empty(snps, dtype=torch.int32, device=dev)
+
+
+
+def score_legs():
+    """the score test: whole calls beside mxa_assoc_linear at n = 1, k = 15 and the bare 'T' products, alternating; or, for the trace, two calls per shape"""
+    nt = max(n for n, _ in SCORE_SHAPES)
+    kh = max(q for _, q in SCORE_SHAPES) + 1
+    Rd = torch.randn(nt, indiv, dtype=torch.float64, device=dev)
+    Wd = 0.25 * torch.rand(nt, indiv, dtype=torch.float64, device=dev)
+    Hd = torch.randn(nt * kh, indiv, dtype=torch.float64, device=dev) / indiv ** 0.5
+    Bs = torch.randn(32, indiv, dtype=torch.float64, device=dev)
+    Cs = torch.empty(32, snps, dtype=torch.float64, device=dev)
+
+    def scan(X, n, q):
+        assert L.mxa_assoc_score(P(X), snps, indiv, P(Rd), indiv, P(Wd), indiv, P(Hd), indiv, n, q + 1, P(out[0]), P(out[1]), P(out[2]), snps, P(nobs)) == 0, mx.lib.last_error()
+
+    for name, X in data.items():
+        if trace:
+            for n, q in SCORE_SHAPES:
+                for _ in range(2):
+                    scan(X, n, q)
+            torch.cuda.synchronize()
+            continue
+        obj = ctypes.c_void_p(None)
+        assert L.mxa_plink2compressed_begin(snps, indiv, 32, ctypes.byref(obj)) == 0, mx.lib.last_error()
+        assert L.mxa_plink2compressed_rows(obj, P(X), 0, snps, None) == 0 and L.mxa_plink2compressed_end(obj) == 0, mx.lib.last_error()
+
+        def linear():
+            assert L.mxa_assoc_linear(P(X), snps, indiv, P(Yd), indiv, 1, P(Qd), indiv, 15, P(out[0]), P(out[1]), P(out[2]), snps, P(nobs), None) == 0, mx.lib.last_error()
+
+        def product(cols):                                                  # in column chunks of at most 32, as the entries multiply
+            for c0 in range(0, cols, 32):
+                assert L.mxa_dgemm_compressed_device(b"T", obj, min(32, cols - c0), P(Bs), indiv, P(Cs), snps, None, 1) == 0, mx.lib.last_error()
+
+        legs = {"assoc_linear n=1 k=15": linear, "'T' product 16 columns": (lambda: product(16))}
+        for n, q in SCORE_SHAPES:
+            legs[f"score n={n} q={q}"] = (lambda n=n, q=q: scan(X, n, q))
+            legs[f"'T' product {n * (q + 3)} columns"] = (lambda c=n * (q + 3): product(c))
+        m = alternate(legs, reps)
+        lin, p16 = m["assoc_linear n=1 k=15"], m["'T' product 16 columns"]
+        print(f"{name}: assoc_linear n=1 k=15 whole call {lin[0]:.2f} ms median of {reps} (min {lin[1]:.2f}, max {lin[2]:.2f}); bare 'T' product of 16 columns "
+              f"{p16[0]:.2f} ms", flush=True)
+        for n, q in SCORE_SHAPES:
+            cols = n * (q + 3)
+            a, lo, hi = m[f"score n={n} q={q}"]
+            p, plo, phi = m[f"'T' product {cols} columns"]
+            passes, epasses = (cols + 15) // 16, n
+            adds = snps * indiv * epasses
+            print(f"{name}, n={n} q={q} ({cols} columns): score whole call {a:.2f} ms median of {reps} (min {lo:.2f}, max {hi:.2f}); bare 'T' product of {cols} columns on a "
+                  f"resident object {p:.2f} ms (min {plo:.2f}, max {phi:.2f}) = {2.0 * snps * indiv * cols / p / 1e9:.1f} TFLOP/s; ratio to the product {a / p:.2f}, to "
+                  f"assoc_linear n=1 k=15 {a / lin[0]:.2f}; model of the kernels: product + {passes} scan pass(es) + {epasses} weight pass(es) of "
+                  f"{snps * bps / READ_CEILING * 1e3:.2f} ms each + {adds:.3g} masked adds = {p + (passes + epasses) * snps * bps / READ_CEILING * 1e3:.2f} ms + the adds",
+                  flush=True)
+        freed = ctypes.c_void_p(obj.value)
+        L.free_compressed(ctypes.byref(freed))
+
+
+if score:
+    score_legs()
+    sys.exit(0)
 
 for name, X in data.items():
     if trace:                                                             # two calls per shape, nothing else: what the kernel trace is cut into

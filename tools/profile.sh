@@ -22,6 +22,8 @@
 #   ld-op [snps indiv window reps]   the LD operator object (mxa_ld_op_*): creation against mxa_ld_window_rows, apply at n in {1, 16, 64} against mxa_ld_window_apply with the byte model, a 50-iteration solve, one process
 #   assoc [snps indiv reps]   the association scan (mxa_assoc_linear) at n = 1, k = 15 and n = 16, k = 16, without and with 5 % missing calls, against the bare 'T' product of n + k columns on a resident object, one process
 #   assoc-kernels [snps indiv]   the library kernels inside mxa_assoc_linear, one by one: tools/perf_assoc.py ... trace under rocprofv3 --kernel-trace, in a run of its own
+#   assoc-score [snps indiv reps]   the score test (mxa_assoc_score) at n = 1, q = 15 and n = 4, q = 15, without and with 5 % missing calls, beside mxa_assoc_linear at n = 1, k = 15 and the bare 'T' products of the same column counts, one process, alternating calls
+#   assoc-score-kernels [snps indiv]   the library kernels inside mxa_assoc_score, one by one: tools/perf_assoc.py score ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -144,6 +146,16 @@ assoc-kernels)
   ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc.py" ${1:-1000000} ${2:-50000} trace > "$O/assoc_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_trace_run.log"; exit 1; }
   f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc.py summarize "$f" 2>&1 | tee "$O/assoc_kernels.txt" || exit 1
   rm -rf "$D"; cp -f "$O/assoc_kernels.txt" "$R/profiles/r15_assoc_kernels.txt" ;;
+assoc-score)
+  # whole-call time of the score test per shape and data set beside the linear entry and the bare 'T' products of the same run; the text is what profiles/r16_assoc_score.txt holds
+  timeout -k 10 900 python3 tools/perf_assoc.py score ${1:-1000000} ${2:-50000} ${3:-5} 2>&1 | tee "$O/assoc_score.txt" || exit 1
+  cp -f "$O/assoc_score.txt" "$R/profiles/r16_assoc_score.txt" ;;
+assoc-score-kernels)
+  # per-kernel times of the second call of each data set and shape; the text is what profiles/r16_assoc_score_kernels.txt holds
+  D="$O/assoc_score_trace"; rm -rf "$D"; mkdir -p "$D"
+  ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc.py" score ${1:-1000000} ${2:-50000} trace > "$O/assoc_score_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_score_trace_run.log"; exit 1; }
+  f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc.py summarize-score "$f" 2>&1 | tee "$O/assoc_score_kernels.txt" || exit 1
+  rm -rf "$D"; cp -f "$O/assoc_score_kernels.txt" "$R/profiles/r16_assoc_score_kernels.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

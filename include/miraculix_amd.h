@@ -618,6 +618,43 @@ int mxa_assoc_score(const unsigned char *plink, int snps, int indiv, const doubl
 int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ldw, int q, double tol, int max_iter, double *gamma, double *r, double *w, double *H,
                             long ldh, int *iters);
 
+/* The score test with saddlepoint p-values: mxa_assoc_score unchanged, then every (SNP s, trait c) with |z| >= z_cutoff is corrected on the device.  The
+ * normal p-value erfc(|z| / sqrt 2) of the score test is badly anti-conservative for rare cases and rare alleles; the saddlepoint one needs, per SNP and
+ * trait, a root solve over sums of a transcendental function of the covariate-adjusted genotype of all individuals, which no wrapper can form without the rows.
+ * plink, R, Wt, H, n, kh, score, var, zstat and nobs are those of mxa_assoc_score, and score, var, zstat and nobs receive bit for bit what mxa_assoc_score
+ * returns for the same operands.  P (indiv x n, ldp >= indiv, column-major): the null model's fitted probabilities p_{c,i}, expected in (0, 1) (for
+ * mxa_assoc_logistic_null: p = y - r); Wt is expected to be positive.  Per (s, c), with mu, U, V, z and a_j = fma(mu, M_hj, D_hj) of mxa_assoc_score's chain,
+ * x_i the allele count (missing calls: mu; padding fields are not individuals):
+ *   flag 3  z is not finite: pval = NaN.
+ *   flag 0  |z| < z_cutoff: pval = erfc(|z| sqrt(1/2)).
+ *   else    tau_ij = h_{c,j,i} / w_{c,i};  g_i = x_i, then for j ascending g_i = fma(-a_j, tau_ij, g_i)   (for mxa_assoc_logistic_null's H this is
+ *           x - C (C^T W C)^-1 C^T W x);  c0 = sum g_i p_i, A = sum |g_i|, G+ = sum max(g_i, 0), G- = sum min(g_i, 0).  The centred cumulant generating function
+ *           of sum g_i y_i, y_i ~ Bernoulli(p_i), in an overflow-free form: with x = t g_i, e = exp(-|x|), (al, be) = (p_i, 1 - p_i) if x >= 0 else
+ *           (1 - p_i, p_i), d = al + be e:
+ *               K(t) = sum [max(x, 0) + log d] - t c0,   K'(t) = sum g_i (x >= 0 ? p_i / d : p_i e / d) - c0,   K''(t) = sum g_i^2 al be e / d^2.
+ *           For each side sigma = +1, -1, with q = sigma |U| and b = (sigma > 0 ? G+ : G-) - c0: the side is outside the support iff
+ *           sigma (b - q) <= 2^-30 A.  Otherwise Newton from t = 0 with the bracket (lo, hi) = (-inf, +inf): evaluate f = K'(t) - q; f < 0: lo = t, else
+ *           hi = t; t' = t - f / K''(t); t' not finite: the side fails; |t' - t| <= tol |t'|: t^ = t' is accepted; else a t' not strictly inside (lo, hi)
+ *           is replaced by (lo + hi) / 2 (not finite: the side fails), and t = t'.  At most max_iter such evaluations, else the side fails (the one
+ *           evaluation of K and K'' at the accepted t^ is not counted).  At t^: w = sign(t^) sqrt(2 (t^ q - K(t^))), v = t^ sqrt(K''(t^)),
+ *           zeta = w + log(v / w) / w (not finite: the side fails), tail = erfc(sigma zeta sqrt(1/2)) / 2.
+ *           The observed side is sigma = +1 if U >= 0, else -1.
+ *   flag 2  the observed side is outside the support or fails, or the opposite side fails: pval = erfc(|z| sqrt(1/2)), the normal p-value.
+ *   flag 1  otherwise: pval = the observed side's tail + the opposite side's tail (0 where the opposite side is outside the support).
+ * Every sum over the individuals runs in an order fixed by indiv alone, no atomics; the list of items is compacted by prefix sums.  Results are identical from
+ * run to run, between host and device pointers, for every row-chunk size of the staging (MXA_ASSOC_CHUNK_ROWS) and every batch size of the correction
+ * (MXA_ASSOC_SPA_BATCH = marked SNPs per batch; default: what fits 4 GiB of g, and for a host matrix a bounce buffer of 256 MiB).  They carry the device's
+ * exp / log / erfc and its contraction of a * b + c, so they are NOT promised bit-equal to any host evaluation, and as before NOT bit-identical between
+ * column counts n (kh + 2).  One host wait (the number of items, with their list) lies between the scan and the correction.
+ * pval (required): snps x n doubles, ld ldo; flag (optional): snps x n ints, ld ldo.  score, var, zstat and pval are all host or all device pointers, flag is
+ *   on pval's side; plink, P, R, Wt and H are host or device pointers, each independently; nothing is written beyond row snps - 1 of a column.  Errors (return
+ *   1, mxa_last_error() == 1, outputs untouched, all decided before a device is selected): every error of mxa_assoc_score; NULL P or pval; ldp < indiv;
+ *   z_cutoff negative or NaN (+inf is legal: nothing is corrected); tol not in (0, 1); max_iter < 1; mixed host and device pointers among score, var, zstat,
+ *   pval and flag.  12: not enough device memory (what mxa_assoc_score lists; P, tau, the lists, and one batch of g at its largest). */
+int mxa_assoc_score_spa(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
+                        const double *H, long ldh, int n, int kh, double z_cutoff, double tol, int max_iter, double *score, double *var, double *zstat,
+                        double *pval, long ldo, int *flag, int *nobs);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

@@ -1,5 +1,6 @@
 """Association scan (C entries mxa_assoc_basis, mxa_assoc_linear): per-SNP linear regression y ~ 1 + covariates + x_s on packed genotypes, missing calls
-imputed by the SNP's mean; and, for binary traits, the score test of a logistic null model fitted once per trait (mxa_assoc_logistic_null, mxa_assoc_score).
+imputed by the SNP's mean; and, for binary traits, the score test of a logistic null model fitted once per trait (mxa_assoc_logistic_null, mxa_assoc_score),
+with saddlepoint p-values for unbalanced case-control data (mxa_assoc_score_spa).
 The definitions, the operation orders and what is exact: include/miraculix_amd.h."""
 import ctypes
 from collections import namedtuple
@@ -150,12 +151,8 @@ def assoc_logistic_null(y, covariates=None, tol=1e-10, max_iter=50):
     return LogisticNull(gamma, r, w, H, int(iters.value))
 
 
-def assoc_score(plink, snps, indiv, R, Wt, H=None, out=None):
-    """score U, var V, z = U / sqrt(V) (each (snps, n), or (snps,) for a one-dimensional R) and nobs (snps,) int32 of the score test of every SNP against the
-    null models of n traits.  plink: as for assoc_linear.  R, Wt: (indiv, n) or (indiv,) float64 null residuals and working weights; H: (indiv, n kh) projection
-    columns, trait c owning the columns c kh .. c kh + kh - 1 (None: kh = 0); numpy or torch, host or device, each independently.  The results are numpy
-    arrays, or torch tensors on R's device when R is a device tensor.  out: a dict with any of the keys "score", "var", "z", as for assoc_linear."""
-    snps, indiv = int(snps), int(indiv)
+def _score_operands(plink, snps, indiv, R, Wt, H):
+    """the checks and the column-major operands of assoc_score and assoc_score_spa: (R, Wt, H or None, n, kh)"""
     if snps < 1 or indiv < 1:
         raise ValueError(f"snps and indiv need to be positive: {snps}, {indiv}")
     if indiv > ASSOC_MAX_INDIV:
@@ -174,52 +171,116 @@ def assoc_score(plink, snps, indiv, R, Wt, H=None, out=None):
         kh = nh // n
     if n * (kh + 2) > 65535:
         raise ValueError(f"n (kh + 2) needs to be at most 65535: n {n}, kh {kh}")
-    one_dim = len(tuple(R.shape)) == 1
-    on_device = _lib.is_torch_tensor(R) and R.is_cuda
+    return rc, wc, hc, n, kh
+
+
+def _score_results(keys, required, out, snps, n, like):
+    """the (n, snps) C-contiguous result buffers by key: those of `out` (transposed views), else fresh ones of every key, torch tensors on `like`'s device when
+    it is a device tensor.  `required` keys must be in a given out."""
     res = {}
     if out is not None:
-        if not out or any(key not in ("score", "var", "z") for key in out):
-            raise ValueError("out needs to hold at least one of the keys 'score', 'var', 'z'")
+        names = ", ".join(repr(k) for k in keys)
+        if not out or any(key not in keys for key in out) or any(key not in out for key in required):
+            raise ValueError(f"out needs to hold at least one of the keys {names}" + (f" and every one of {required}" if required else ""))
         for key, o in out.items():
             ot = o.t() if _lib.is_torch_tensor(o) else o.T
             ok = tuple(o.shape) == (snps, n) and str(o.dtype).endswith("float64") and (ot.is_contiguous() if _lib.is_torch_tensor(o) else ot.flags.c_contiguous)
             if not ok:
                 raise ValueError(f"out[{key!r}] needs to be a float64 ({snps}, {n}) result with contiguous columns")
             res[key] = ot
-    else:
-        for key in ("score", "var", "z"):
-            if on_device:
-                import torch
-                res[key] = torch.zeros((n, snps), dtype=torch.float64, device=R.device)
-            else:
-                res[key] = np.zeros((n, snps), dtype=np.float64)
+        return res
+    on_device = _lib.is_torch_tensor(like) and like.is_cuda
+    for key in keys:
+        if on_device:
+            import torch
+            res[key] = torch.zeros((n, snps), dtype=torch.float64, device=like.device)
+        else:
+            res[key] = np.zeros((n, snps), dtype=np.float64)
+    return res
+
+
+def _shaped(res, out, key, snps, one_dim):
+    if key not in res:
+        return None
+    if out is not None:
+        return out[key]
+    r = res[key].t() if _lib.is_torch_tensor(res[key]) else res[key].T
+    return r.reshape(snps) if one_dim else r
+
+
+def assoc_score(plink, snps, indiv, R, Wt, H=None, out=None):
+    """score U, var V, z = U / sqrt(V) (each (snps, n), or (snps,) for a one-dimensional R) and nobs (snps,) int32 of the score test of every SNP against the
+    null models of n traits.  plink: as for assoc_linear.  R, Wt: (indiv, n) or (indiv,) float64 null residuals and working weights; H: (indiv, n kh) projection
+    columns, trait c owning the columns c kh .. c kh + kh - 1 (None: kh = 0); numpy or torch, host or device, each independently.  The results are numpy
+    arrays, or torch tensors on R's device when R is a device tensor.  out: a dict with any of the keys "score", "var", "z", as for assoc_linear."""
+    snps, indiv = int(snps), int(indiv)
+    rc, wc, hc, n, kh = _score_operands(plink, snps, indiv, R, Wt, H)
+    one_dim = len(tuple(R.shape)) == 1
+    res = _score_results(("score", "var", "z"), (), out, snps, n, R)
     nobs = np.zeros(snps, dtype=np.int32)
     L = _lib.check_library_handle()
     _check(L.mxa_assoc_score(_lib.ptr(plink), snps, indiv, _lib.ptr(rc), indiv, _lib.ptr(wc), indiv, _lib.ptr(hc), indiv, n, kh, _lib.ptr(res.get("score")),
                              _lib.ptr(res.get("var")), _lib.ptr(res.get("z")), snps, _lib.ptr(nobs)), "mxa_assoc_score")
-
-    def shaped(key):
-        if key not in res:
-            return None
-        if out is not None:
-            return out[key]
-        r = res[key].t() if _lib.is_torch_tensor(res[key]) else res[key].T
-        return r.reshape(snps) if one_dim else r
-    return AssocScoreResult(shaped("score"), shaped("var"), shaped("z"), nobs)
+    return AssocScoreResult(*(_shaped(res, out, key, snps, one_dim) for key in ("score", "var", "z")), nobs)
 
 
-def assoc_logistic(plink, snps, indiv, Y, covariates=None):
+AssocSpaResult = namedtuple("AssocSpaResult", "score var z pval flag nobs")
+
+
+def assoc_score_spa(plink, snps, indiv, P, R, Wt, H=None, z_cutoff=2.0, tol=2.0 ** -30, max_iter=50, out=None):
+    """assoc_score with saddlepoint p-values (C entry mxa_assoc_score_spa): score, var, z and nobs exactly as assoc_score returns them, pval (snps, n) and flag
+    (snps, n) int32 -- 0: |z| < z_cutoff, the normal p-value erfc(|z| / sqrt 2); 1: the saddlepoint p-value; 2: the saddlepoint solve did not apply (the
+    statistic lies on the edge of its support, or no convergence), the normal p-value; 3: z is not finite, NaN.  P: (indiv, n) or (indiv,) float64, the null
+    models' fitted probabilities in (0, 1) (y - r of assoc_logistic_null), numpy or torch like R, Wt and H.  The correction runs on the device for the (SNP,
+    trait) pairs with |z| >= z_cutoff only; z_cutoff = inf corrects nothing.  out: a dict with the key "pval" and at least one of "score", "var", "z"."""
+    snps, indiv = int(snps), int(indiv)
+    rc, wc, hc, n, kh = _score_operands(plink, snps, indiv, R, Wt, H)
+    pc, np_ = _columns(P, indiv, "P")
+    if np_ != n:
+        raise ValueError(f"P needs as many columns as R: {np_}, {n}")
+    z_cutoff, tol, max_iter = float(z_cutoff), float(tol), int(max_iter)
+    if not z_cutoff >= 0:
+        raise ValueError(f"z_cutoff must not be negative or NaN: {z_cutoff}")
+    if not 0 < tol < 1:
+        raise ValueError(f"tol needs to lie in (0, 1): {tol}")
+    if max_iter < 1:
+        raise ValueError(f"max_iter needs to be at least 1: {max_iter}")
+    one_dim = len(tuple(R.shape)) == 1
+    res = _score_results(("score", "var", "z", "pval"), ("pval",), out, snps, n, R)
+    if len(res) < 2:
+        raise ValueError("out needs to hold one of the keys 'score', 'var', 'z' beside 'pval'")
+    if _lib.is_torch_tensor(res["pval"]) and res["pval"].is_cuda:
+        import torch
+        flag = torch.zeros((n, snps), dtype=torch.int32, device=res["pval"].device)
+    else:
+        flag = np.zeros((n, snps), dtype=np.int32)
+    nobs = np.zeros(snps, dtype=np.int32)
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_score_spa(_lib.ptr(plink), snps, indiv, _lib.ptr(pc), indiv, _lib.ptr(rc), indiv, _lib.ptr(wc), indiv, _lib.ptr(hc), indiv, n, kh, z_cutoff, tol,
+                                 max_iter, _lib.ptr(res.get("score")), _lib.ptr(res.get("var")), _lib.ptr(res.get("z")), _lib.ptr(res["pval"]), snps, _lib.ptr(flag),
+                                 _lib.ptr(nobs)), "mxa_assoc_score_spa")
+    fl = flag.t() if _lib.is_torch_tensor(flag) else flag.T
+    return AssocSpaResult(*(_shaped(res, out, key, snps, one_dim) for key in ("score", "var", "z", "pval")), fl.reshape(snps) if one_dim else fl, nobs)
+
+
+def assoc_logistic(plink, snps, indiv, Y, covariates=None, spa=False, **spa_options):
     """The logistic score test of every SNP for the 0 / 1 traits Y ((indiv, n) or (indiv,), numpy): the null model of each trait is fitted on the host
-    (assoc_logistic_null), R, Wt and H are stacked, and assoc_score scans.  Returns AssocScoreResult(score, var, z, nobs) as numpy arrays."""
+    (assoc_logistic_null), R, Wt and H are stacked, and assoc_score scans.  Returns AssocScoreResult(score, var, z, nobs) as numpy arrays.  spa=True: the scan
+    is assoc_score_spa with P = y - r of every null (spa_options: its z_cutoff, tol, max_iter), and AssocSpaResult(score, var, z, pval, flag, nobs) returns."""
     Ya = np.asarray(Y, dtype=np.float64)
     one_dim = Ya.ndim == 1
     if Ya.ndim not in (1, 2) or Ya.shape[0] != int(indiv) or (Ya.ndim == 2 and Ya.shape[1] < 1):
         raise ValueError(f"Y needs to be ({indiv},) or ({indiv}, n >= 1): {Ya.shape}")
+    if spa_options and not spa:
+        raise ValueError(f"{sorted(spa_options)} need spa=True")
     Y2 = Ya.reshape(int(indiv), -1)
     fits = [assoc_logistic_null(Y2[:, c], covariates) for c in range(Y2.shape[1])]
     R = np.asfortranarray(np.stack([f.r for f in fits], axis=1))
     Wt = np.asfortranarray(np.stack([f.w for f in fits], axis=1))
     H = np.asfortranarray(np.concatenate([f.H for f in fits], axis=1))
+    if spa:
+        res = assoc_score_spa(plink, snps, indiv, np.asfortranarray(Y2 - R), R, Wt, H, **spa_options)
+        return AssocSpaResult(*(a.reshape(-1) for a in res[:5]), res.nobs) if one_dim else res
     res = assoc_score(plink, snps, indiv, R, Wt, H)
     if one_dim:
         return AssocScoreResult(res.score.reshape(-1), res.var.reshape(-1), res.z.reshape(-1), res.nobs)

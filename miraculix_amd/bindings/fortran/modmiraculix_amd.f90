@@ -23,6 +23,7 @@ module modmiraculix_amd
  public :: mxa_ld_op_bytes, mxa_ld_op_create, mxa_ld_op_create_pairwise, mxa_ld_op_from_rows, mxa_ld_op_rows, mxa_ld_op_apply, mxa_ld_op_solve, mxa_ld_op_free
  public :: mxa_assoc_basis, mxa_assoc_linear
  public :: mxa_assoc_score, mxa_assoc_logistic_null
+ public :: mxa_assoc_score_spa
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -358,6 +359,18 @@ module modmiraculix_amd
    type(c_ptr), value, intent(in) :: y, Wcov, gamma, resid, wt, Hmat, iters
    integer(c_long), value, intent(in) :: ldw, ldh
    real(c_double), value, intent(in) :: tol
+   integer(c_int) :: rc
+  end function
+
+  ! the score test with saddlepoint p-values: Pfit = the null's fitted probabilities (indiv x n, ld ldp); pval (required) and flag (c_loc of snps x n ints or
+  ! c_null_ptr) have the leading dimension ldo of score, var and zstat
+  function mxa_assoc_score_spa(plink, snps, indiv, Pfit, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, tol, max_iter, score, var, zstat, pval, ldo, flag, nobs) &
+           bind(C, name='mxa_assoc_score_spa') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, Pfit, R, Wt, H, score, var, zstat, pval, flag, nobs
+   integer(c_int), value, intent(in) :: snps, indiv, n, kh, max_iter
+   integer(c_long), value, intent(in) :: ldp, ldr, ldw, ldh, ldo
+   real(c_double), value, intent(in) :: z_cutoff, tol
    integer(c_int) :: rc
   end function
 

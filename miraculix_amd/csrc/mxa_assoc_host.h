@@ -1,5 +1,5 @@
 // mxa_assoc_host.h -- the host-only part of the association scan (mxa_assoc.hip): the covariate basis of mxa_assoc_basis and the argument rules of
-// mxa_assoc_linear and mxa_assoc_score (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
+// mxa_assoc_linear, mxa_assoc_score and mxa_assoc_score_spa (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
 // program can compile it for the CPU (tools/assoc_host_check.cpp, tools/assoc_score_host_check.cpp, run under -fsanitize=address,undefined).
 #pragma once
 #include <cmath>
@@ -86,6 +86,19 @@ inline const char *assoc_score_args(const void *plink, long snps, long indiv, co
   if (indiv > kAssocMaxIndiv) return "indiv > 47 453 132 (4 indiv^2 >= 2^53)";
   if (!score && !var && !zstat) return "score, var and zstat are all NULL";
   if (ldo < snps) return "ldo must be at least snps";
+  return nullptr;
+}
+
+// The same for mxa_assoc_score_spa: mxa_assoc_score's rules, then its own.  (flag and pval on different sides are the caller's check.)
+inline const char *assoc_score_spa_args(const void *plink, long snps, long indiv, const void *P, long ldp, const void *R, long ldr, const void *Wt, long ldw,
+                                        const void *H, long ldh, int n, int kh, double z_cutoff, double tol, int max_iter, const void *score, const void *var,
+                                        const void *zstat, const void *pval, long ldo) {
+  if (const char *bad = assoc_score_args(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo)) return bad;
+  if (!P || !pval) return "P and pval must not be NULL";
+  if (ldp < indiv) return "ldp must be at least indiv";
+  if (!(z_cutoff >= 0.0)) return "z_cutoff must not be negative or NaN";
+  if (!(tol > 0.0 && tol < 1.0)) return "tol must lie in (0, 1)";
+  if (max_iter < 1) return "max_iter must be at least 1";
   return nullptr;
 }
 

@@ -24,6 +24,8 @@
 #   assoc-kernels [snps indiv]   the library kernels inside mxa_assoc_linear, one by one: tools/perf_assoc.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   assoc-score [snps indiv reps]   the score test (mxa_assoc_score) at n = 1, q = 15 and n = 4, q = 15, without and with 5 % missing calls, beside mxa_assoc_linear at n = 1, k = 15 and the bare 'T' products of the same column counts, one process, alternating calls
 #   assoc-score-kernels [snps indiv]   the library kernels inside mxa_assoc_score, one by one: tools/perf_assoc.py score ... trace under rocprofv3 --kernel-trace, in a run of its own
+#   assoc-spa [snps indiv reps]   the score test with saddlepoint p-values (mxa_assoc_score_spa) at n = 1, q = 3, 5 % cases, z_cutoff = 1.96 and inf, beside mxa_assoc_score on the same operands, one process, alternating calls
+#   assoc-spa-kernels [snps indiv]   the library kernels inside mxa_assoc_score_spa, one by one: tools/perf_assoc_spa.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -156,6 +158,16 @@ assoc-score-kernels)
   ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc.py" score ${1:-1000000} ${2:-50000} trace > "$O/assoc_score_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_score_trace_run.log"; exit 1; }
   f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc.py summarize-score "$f" 2>&1 | tee "$O/assoc_score_kernels.txt" || exit 1
   rm -rf "$D"; cp -f "$O/assoc_score_kernels.txt" "$R/profiles/r16_assoc_score_kernels.txt" ;;
+assoc-spa)
+  # whole-call time of the entry beside mxa_assoc_score of the same run, alternating calls; the text is what profiles/r17_assoc_spa.txt holds
+  timeout -k 10 900 python3 tools/perf_assoc_spa.py ${1:-50000} ${2:-1000000} ${3:-5} 2>&1 | tee "$O/assoc_spa.txt" || exit 1
+  cp -f "$O/assoc_spa.txt" "$R/profiles/r17_assoc_spa.txt" ;;
+assoc-spa-kernels)
+  # per-kernel times of the second call; the text is what profiles/r17_assoc_spa_kernels.txt holds
+  D="$O/assoc_spa_trace"; rm -rf "$D"; mkdir -p "$D"
+  ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc_spa.py" ${1:-50000} ${2:-1000000} trace > "$O/assoc_spa_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_spa_trace_run.log"; exit 1; }
+  f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc_spa.py summarize "$f" 2>&1 | tee "$O/assoc_spa_kernels.txt" || exit 1
+  rm -rf "$D"; cp -f "$O/assoc_spa_kernels.txt" "$R/profiles/r17_assoc_spa_kernels.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

@@ -643,7 +643,8 @@ int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ld
  *   flag 1  otherwise: pval = the observed side's tail + the opposite side's tail (0 where the opposite side is outside the support).
  * Every sum over the individuals runs in an order fixed by indiv alone, no atomics; the list of items is compacted by prefix sums.  Results are identical from
  * run to run, between host and device pointers, for every row-chunk size of the staging (MXA_ASSOC_CHUNK_ROWS) and every batch size of the correction
- * (MXA_ASSOC_SPA_BATCH = marked SNPs per batch; default: what fits 4 GiB of g, and for a host matrix a bounce buffer of 256 MiB).  They carry the device's
+ * (MXA_ASSOC_SPA_BATCH = marked SNPs per batch, MXA_ASSOC_SPA_ITEMS = items per batch, never below the n items of one SNP; default: what fits 4 GiB of g,
+ * and for a host matrix a bounce buffer of 256 MiB).  They carry the device's
  * exp / log / erfc and its contraction of a * b + c, so they are NOT promised bit-equal to any host evaluation, and as before NOT bit-identical between
  * column counts n (kh + 2).  One host wait (the number of items, with their list) lies between the scan and the correction.
  * pval (required): snps x n doubles, ld ldo; flag (optional): snps x n ints, ld ldo.  score, var, zstat and pval are all host or all device pointers, flag is

@@ -773,8 +773,14 @@ struct SpaArgs {
   int *flag;
 };
 
-// the items one batch may hold: what fits 4 GiB of g (512 items, 1024 workgroups of k_assoc_spa, at a million individuals), at least the n items of one SNP
-long spa_batch_items(long indiv, int n) { return std::max<long>(n, (long)(((size_t)4 << 30) / (sizeof(double) * (size_t)indiv))); }
+// the items one batch may hold: MXA_ASSOC_SPA_ITEMS (read per call, for tests), else what fits 4 GiB of g (512 items, 1024 workgroups of k_assoc_spa, at a
+// million individuals); at least the n items of one SNP
+long spa_batch_items(long indiv, int n) {
+  long items = (long)(((size_t)4 << 30) / (sizeof(double) * (size_t)indiv));
+  const char *e = getenv("MXA_ASSOC_SPA_ITEMS");
+  if (e && atol(e) > 0) items = atol(e);
+  return std::max<long>(n, items);
+}
 // the marked SNPs of one batch: MXA_ASSOC_SPA_BATCH, else unlimited for rows read in place and what fits a bounce buffer of 256 MiB for a host matrix
 long spa_batch_rows(long snps, long bps, bool in_place) {
   long rows = in_place ? snps : std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)bps));

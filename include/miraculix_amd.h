@@ -595,7 +595,7 @@ int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv, const doub
  *     V   = sxx
  *     z   = U / sqrt(V)
  * score = U, var = V, zstat = z.  There is no special case: N == 0, V <= 0 and monomorphic SNPs give what the arithmetic gives; callers filter such SNPs.
- * p-values and Firth / saddle-point corrections are a wrapper's business (-|z| orders a clump).  Results are identical from run to run, between host and
+ * No p-values here (-|z| orders a clump): saddlepoint p-values are mxa_assoc_score_spa, effect sizes by Firth-penalised fits mxa_assoc_score_firth.  Results are identical from run to run, between host and
  * device pointers and for every row-chunk size of the staging (MXA_ASSOC_CHUNK_ROWS applies as for mxa_assoc_linear); they are NOT promised bit-identical
  * between different column counts n (kh + 2).
  * mxa_assoc_score: score, var, zstat: snps x n column-major, ldo >= snps; each optional, at least one required, those given all host or all device pointers;
@@ -655,6 +655,47 @@ int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ld
 int mxa_assoc_score_spa(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
                         const double *H, long ldh, int n, int kh, double z_cutoff, double tol, int max_iter, double *score, double *var, double *zstat,
                         double *pval, long ldo, int *flag, int *nobs);
+
+/* The score test with effect sizes: mxa_assoc_score unchanged, then every (SNP s, trait c) with |z| >= z_cutoff gets the log odds ratio of the SNP, its
+ * standard error and the likelihood-ratio statistic from a one-parameter logistic fit on the device, by maximum likelihood (penalty == 0) or with Firth's
+ * penalty (penalty == 1).  The one-step estimate U / V is badly biased for rare alleles and rare cases, and the maximum-likelihood estimate does not exist where
+ * carriers and cases separate; the penalised estimate always exists.  Like the saddlepoint p-value the fit sums transcendental functions of the
+ * covariate-adjusted genotype over all individuals, once per Newton step, which no wrapper can form without the rows.
+ * plink, P, R, Wt, H, n, kh, score, var, zstat and nobs are those of mxa_assoc_score_spa, and score, var, zstat and nobs receive bit for bit what
+ * mxa_assoc_score returns for the same operands.  The model: logit pi_i(beta) = logit p_i + beta g_i -- the null model's linear predictor is the offset, the
+ * adjusted genotype g the regressor.  With K the centred cumulant generating function of mxa_assoc_score_spa its log likelihood ratio against beta = 0 is
+ * beta U - K(beta), its score U - K'(beta), its information K''(beta): no y is needed.  Firth's penalty adds log(K''(beta)) / 2.
+ * Per (s, c), with mu, U, V, z and a_j of mxa_assoc_score's chain and g, c0, A, G+, G-, e, al, be, d, K, K', K'' exactly as defined for mxa_assoc_score_spa
+ * (t = beta: x = beta g_i, e = exp(-|x|)):
+ *   flag 3  z is not finite: beta = se = chisq = pval = NaN.
+ *   flag 0  |z| < z_cutoff: the one-step values beta = U / V, se = 1 / sqrt(V), chisq = z * z, pval = erfc(|z| sqrt(1/2)), each operation rounded once.
+ *   else    a fit.  Further sums: with pi_i = (x >= 0 ? p_i / d : p_i e / d) and omega_i = al be e / d^2:
+ *               K'''(beta) = sum g_i^3 omega_i (1 - 2 pi_i),   K''''(beta) = sum g_i^4 omega_i (1 - 6 omega_i).
+ *           The function to solve: penalty == 0: f = K'(beta) - U, f' = K''(beta); penalty == 1: f = K'(beta) - U - (K''' / K'') / 2,
+ *           f' = K'' - (K'''' / K'' - (K''' / K'')^2) / 2, and where this f' is not positive K'' stands in for it.
+ *           penalty == 0 only: the statistic is outside the support iff sigma (b - U) <= 2^-30 A with sigma = +1 if U >= 0 else -1 and
+ *           b = (sigma > 0 ? G+ : G-) - c0 (the observed side of mxa_assoc_score_spa): the likelihood has no maximum.  With the penalty there is no such
+ *           test: the penalised root exists on the edge of the support too.
+ *           Newton from beta = 0 with the bracket (lo, hi) = (-inf, +inf): evaluate f and f'; f < 0: lo = beta, else hi = beta; beta' = beta - f / f';
+ *           beta' not finite: the fit fails; |beta' - beta| <= tol |beta'|: beta^ = beta' is accepted; else a beta' not strictly inside (lo, hi) is
+ *           replaced by (lo + hi) / 2 (not finite: the fit fails), and beta = beta'.  At most max_iter such evaluations, else the fit fails.  The first
+ *           evaluation is at beta = 0 and yields K''(0); one evaluation of K and K'' at the accepted beta^ is not counted.
+ *   flag 2  the statistic is outside the support (penalty == 0), the fit fails, or se or chisq below is not finite: the one-step values of flag 0.
+ *   flag 1  otherwise: beta = beta^, se = 1 / sqrt(K''(beta^)), chisq = max(0, 2 (beta^ U - K(beta^)) + penalty log(K''(beta^) / K''(0))),
+ *           pval = erfc(sqrt(chisq / 2)).
+ * Every sum over the individuals runs in an order fixed by indiv alone, no atomics; list, items, batches and g are those of mxa_assoc_score_spa, and
+ * MXA_ASSOC_CHUNK_ROWS, MXA_ASSOC_SPA_BATCH and MXA_ASSOC_SPA_ITEMS apply as they do there (the default batch: what fits 8 GiB of g -- one workgroup an item --, beyond 1024 items cut down to a multiple of 1024).  Results are identical from run to run, between host and device
+ * pointers, for every row-chunk size of the staging and every batch size.  They carry the device's exp / log / erfc and its contraction of a * b + c, so they
+ * are NOT promised bit-equal to any host evaluation, and as before NOT bit-identical between column counts n (kh + 2).  One host wait (the number of items, with
+ * their list) lies between the scan and the fits.  Saddlepoint p-values and the fit in one call are not offered: call both entries.
+ * beta (required), se, chisq, pval (optional): snps x n doubles, ld ldo; flag (optional): snps x n ints, ld ldo.  score, var, zstat, beta, se, chisq and pval
+ *   are all host or all device pointers, flag is on beta's side; plink, P, R, Wt and H are host or device pointers, each independently; nothing is written
+ *   beyond row snps - 1 of a column.  Errors (return 1, mxa_last_error() == 1, outputs untouched, all decided before a device is selected): every error of
+ *   mxa_assoc_score_spa with beta in pval's place; penalty not 0 or 1.  12: not enough device memory (what mxa_assoc_score_spa lists, and the further snps x n
+ *   result arrays). */
+int mxa_assoc_score_firth(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
+                          const double *H, long ldh, int n, int kh, double z_cutoff, int penalty, double tol, int max_iter, double *score, double *var,
+                          double *zstat, double *beta, double *se, double *chisq, double *pval, long ldo, int *flag, int *nobs);
 
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *

@@ -1,6 +1,6 @@
 """Association scan (C entries mxa_assoc_basis, mxa_assoc_linear): per-SNP linear regression y ~ 1 + covariates + x_s on packed genotypes, missing calls
 imputed by the SNP's mean; and, for binary traits, the score test of a logistic null model fitted once per trait (mxa_assoc_logistic_null, mxa_assoc_score),
-with saddlepoint p-values for unbalanced case-control data (mxa_assoc_score_spa).
+with saddlepoint p-values for unbalanced case-control data (mxa_assoc_score_spa) and with effect sizes by Firth-penalised fits (mxa_assoc_score_firth).
 The definitions, the operation orders and what is exact: include/miraculix_amd.h."""
 import ctypes
 from collections import namedtuple
@@ -263,16 +263,62 @@ def assoc_score_spa(plink, snps, indiv, P, R, Wt, H=None, z_cutoff=2.0, tol=2.0 
     return AssocSpaResult(*(_shaped(res, out, key, snps, one_dim) for key in ("score", "var", "z", "pval")), fl.reshape(snps) if one_dim else fl, nobs)
 
 
-def assoc_logistic(plink, snps, indiv, Y, covariates=None, spa=False, **spa_options):
+AssocFirthResult = namedtuple("AssocFirthResult", "score var z beta se chisq pval flag nobs")
+
+
+def assoc_score_firth(plink, snps, indiv, P, R, Wt, H=None, z_cutoff=2.0, penalty=1, tol=2.0 ** -30, max_iter=50, out=None):
+    """assoc_score with effect sizes (C entry mxa_assoc_score_firth): score, var, z and nobs exactly as assoc_score returns them; beta (the SNP's log odds
+    ratio), se, chisq (the likelihood-ratio statistic), pval (each (snps, n)) and flag (snps, n) int32 -- 0: |z| < z_cutoff, the one-step values U / V,
+    1 / sqrt(V), z^2 and the normal p-value; 1: the fit of logit pi = logit p + beta g by Newton on the device, penalty=1: with Firth's penalty (finite where
+    carriers and cases separate), penalty=0: maximum likelihood; 2: no fit (penalty=0: the statistic lies on the edge of its support; no convergence), the
+    one-step values; 3: z is not finite, NaN.  P, R, Wt, H: as for assoc_score_spa.  z_cutoff = inf fits nothing.  out: a dict with the key "beta", at least
+    one of "score", "var", "z" and any of "se", "chisq", "pval"."""
+    snps, indiv = int(snps), int(indiv)
+    rc, wc, hc, n, kh = _score_operands(plink, snps, indiv, R, Wt, H)
+    pc, np_ = _columns(P, indiv, "P")
+    if np_ != n:
+        raise ValueError(f"P needs as many columns as R: {np_}, {n}")
+    z_cutoff, tol, max_iter = float(z_cutoff), float(tol), int(max_iter)
+    if not z_cutoff >= 0:
+        raise ValueError(f"z_cutoff must not be negative or NaN: {z_cutoff}")
+    if penalty not in (0, 1):
+        raise ValueError(f"penalty needs to be 0 or 1: {penalty}")
+    if not 0 < tol < 1:
+        raise ValueError(f"tol needs to lie in (0, 1): {tol}")
+    if max_iter < 1:
+        raise ValueError(f"max_iter needs to be at least 1: {max_iter}")
+    one_dim = len(tuple(R.shape)) == 1
+    keys = ("score", "var", "z", "beta", "se", "chisq", "pval")
+    res = _score_results(keys, ("beta",), out, snps, n, R)
+    if not any(key in res for key in ("score", "var", "z")):
+        raise ValueError("out needs to hold one of the keys 'score', 'var', 'z' beside 'beta'")
+    if _lib.is_torch_tensor(res["beta"]) and res["beta"].is_cuda:
+        import torch
+        flag = torch.zeros((n, snps), dtype=torch.int32, device=res["beta"].device)
+    else:
+        flag = np.zeros((n, snps), dtype=np.int32)
+    nobs = np.zeros(snps, dtype=np.int32)
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_score_firth(_lib.ptr(plink), snps, indiv, _lib.ptr(pc), indiv, _lib.ptr(rc), indiv, _lib.ptr(wc), indiv, _lib.ptr(hc), indiv, n, kh, z_cutoff,
+                                   int(penalty), tol, max_iter, *(_lib.ptr(res.get(key)) for key in keys), snps, _lib.ptr(flag), _lib.ptr(nobs)),
+           "mxa_assoc_score_firth")
+    fl = flag.t() if _lib.is_torch_tensor(flag) else flag.T
+    return AssocFirthResult(*(_shaped(res, out, key, snps, one_dim) for key in keys), fl.reshape(snps) if one_dim else fl, nobs)
+
+
+def assoc_logistic(plink, snps, indiv, Y, covariates=None, spa=False, firth=False, **spa_options):
     """The logistic score test of every SNP for the 0 / 1 traits Y ((indiv, n) or (indiv,), numpy): the null model of each trait is fitted on the host
     (assoc_logistic_null), R, Wt and H are stacked, and assoc_score scans.  Returns AssocScoreResult(score, var, z, nobs) as numpy arrays.  spa=True: the scan
-    is assoc_score_spa with P = y - r of every null (spa_options: its z_cutoff, tol, max_iter), and AssocSpaResult(score, var, z, pval, flag, nobs) returns."""
+    is assoc_score_spa with P = y - r of every null (spa_options: its z_cutoff, tol, max_iter), and AssocSpaResult(score, var, z, pval, flag, nobs) returns.
+    firth=True: the scan is assoc_score_firth (options: its z_cutoff, penalty, tol, max_iter), and AssocFirthResult returns.  Not both."""
+    if spa and firth:
+        raise ValueError("spa=True and firth=True exclude each other: call assoc_logistic twice")
     Ya = np.asarray(Y, dtype=np.float64)
     one_dim = Ya.ndim == 1
     if Ya.ndim not in (1, 2) or Ya.shape[0] != int(indiv) or (Ya.ndim == 2 and Ya.shape[1] < 1):
         raise ValueError(f"Y needs to be ({indiv},) or ({indiv}, n >= 1): {Ya.shape}")
-    if spa_options and not spa:
-        raise ValueError(f"{sorted(spa_options)} need spa=True")
+    if spa_options and not (spa or firth):
+        raise ValueError(f"{sorted(spa_options)} need spa=True or firth=True")
     Y2 = Ya.reshape(int(indiv), -1)
     fits = [assoc_logistic_null(Y2[:, c], covariates) for c in range(Y2.shape[1])]
     R = np.asfortranarray(np.stack([f.r for f in fits], axis=1))
@@ -281,6 +327,9 @@ def assoc_logistic(plink, snps, indiv, Y, covariates=None, spa=False, **spa_opti
     if spa:
         res = assoc_score_spa(plink, snps, indiv, np.asfortranarray(Y2 - R), R, Wt, H, **spa_options)
         return AssocSpaResult(*(a.reshape(-1) for a in res[:5]), res.nobs) if one_dim else res
+    if firth:
+        res = assoc_score_firth(plink, snps, indiv, np.asfortranarray(Y2 - R), R, Wt, H, **spa_options)
+        return AssocFirthResult(*(a.reshape(-1) for a in res[:8]), res.nobs) if one_dim else res
     res = assoc_score(plink, snps, indiv, R, Wt, H)
     if one_dim:
         return AssocScoreResult(res.score.reshape(-1), res.var.reshape(-1), res.z.reshape(-1), res.nobs)

@@ -24,6 +24,7 @@ module modmiraculix_amd
  public :: mxa_assoc_basis, mxa_assoc_linear
  public :: mxa_assoc_score, mxa_assoc_logistic_null
  public :: mxa_assoc_score_spa
+ public :: mxa_assoc_score_firth
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -369,6 +370,18 @@ module modmiraculix_amd
    import c_int, c_long, c_double, c_ptr
    type(c_ptr), value, intent(in) :: plink, Pfit, R, Wt, H, score, var, zstat, pval, flag, nobs
    integer(c_int), value, intent(in) :: snps, indiv, n, kh, max_iter
+   integer(c_long), value, intent(in) :: ldp, ldr, ldw, ldh, ldo
+   real(c_double), value, intent(in) :: z_cutoff, tol
+   integer(c_int) :: rc
+  end function
+
+  ! the score test with effect sizes: beta (required), se, chisq, pval (c_loc or c_null_ptr each) and flag (c_loc of snps x n ints or c_null_ptr) have the
+  ! leading dimension ldo of score, var and zstat; penalty 0: maximum likelihood, 1: Firth's penalty
+  function mxa_assoc_score_firth(plink, snps, indiv, Pfit, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, penalty, tol, max_iter, score, var, zstat, beta, se, &
+           chisq, pval, ldo, flag, nobs) bind(C, name='mxa_assoc_score_firth') result(rc)
+   import c_int, c_long, c_double, c_ptr
+   type(c_ptr), value, intent(in) :: plink, Pfit, R, Wt, H, score, var, zstat, beta, se, chisq, pval, flag, nobs
+   integer(c_int), value, intent(in) :: snps, indiv, n, kh, penalty, max_iter
    integer(c_long), value, intent(in) :: ldp, ldr, ldw, ldh, ldo
    real(c_double), value, intent(in) :: z_cutoff, tol
    integer(c_int) :: rc

@@ -5,6 +5,7 @@
 // The score test for binary traits (mxa_assoc_score) is the same scan with B = [R | Wt | H] and one more sum per weight column, E = the weights
 // summed over the SNP's 11 fields (k_assoc_weights, dense); k_assoc_score_finish is its epilogue.  Its null model is host code: mxa_assoc_null_host.h.
 // mxa_assoc_score_spa is that scan followed by the saddlepoint correction of the SNPs with |z| >= z_cutoff: the k_assoc_spa* kernels.
+// mxa_assoc_score_firth is the same scan and the same stage with another solve: the (Firth-penalised) fit of the SNP's effect, k_assoc_firth*.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -573,6 +574,160 @@ __global__ void __launch_bounds__(256) k_assoc_spa_combine(long nitems, long ite
   pval[o] = a.tail + (b.status == kSpaSolved ? b.tail : 0.0);
 }
 
+// ---- the effect sizes of the score test (mxa_assoc_score_firth): the stage of the saddlepoint correction with its own classify epilogue, solve
+// and combine.  k_assoc_firth_classify writes the one-step values and the flag 0 / 3 of every (SNP, trait) and marks with 1 what is to be fitted (the one-step
+// values stay where the fit ends with the flag 2); beta, se, chisq, pval and flag: snps x n, ld snps.
+struct FirthFit { double beta, K, k2, k20; int status, evals; };   // beta^, K(beta^), K''(beta^), K''(0)
+
+__global__ void __launch_bounds__(256) k_assoc_firth_classify(long snps, int n, const double *__restrict__ score, const double *__restrict__ var,
+                                                               const double *__restrict__ zstat, long ldu, double z_cutoff, double *__restrict__ beta,
+                                                               double *__restrict__ se, double *__restrict__ chisq, double *__restrict__ pval, int *__restrict__ flag,
+                                                               long blk0) {
+  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
+  if (idx >= snps * (long)n) return;
+  const size_t at = (size_t)(idx % snps) + (size_t)(idx / snps) * (size_t)ldu;
+  const double z = zstat[at];
+  if (!isfinite(z)) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    flag[idx] = 3; beta[idx] = nan; se[idx] = nan; chisq[idx] = nan; pval[idx] = nan;
+    return;
+  }
+  const double az = fabs(z), V = var[at];
+  flag[idx] = az < z_cutoff ? 0 : 1;
+  beta[idx] = __ddiv_rn(score[at], V);
+  se[idx] = __ddiv_rn(1.0, __dsqrt_rn(V));
+  chisq[idx] = __dmul_rn(z, z);
+  pval[idx] = erfc(__dmul_rn(az, 0.70710678118654752440));
+}
+
+// one workgroup per item: row `item` = blk0 + blockIdx.x of G, one solve.  Thread t takes the individuals t, t + 256, ... in ascending order; every sum ends in
+// spa_block_sums, so its order depends on indiv alone.  First c0, A, G+ and G- (penalty == 0: the support test of the observed side), then Newton from beta = 0
+// with its bracket, entirely in the kernel: an evaluation reads g and p once and sums K1, K2 and, with the penalty, K3 and K4 (the derivatives of K) -- one exp
+// and one division a term, the two further sums are FMA chains on g r and omega; the evaluation at the accepted beta^ sums K and K2.  Thread 0 updates beta, the
+// bracket and the state and broadcasts both through the LDS.  penalty is uniform over the launch.  The header of mxa_assoc_score_firth has the rules.
+__global__ void __launch_bounds__(256) k_assoc_firth(const double *__restrict__ G, long indiv, const double *__restrict__ P, const int *__restrict__ item_s,
+                                                      const int *__restrict__ item_c, long item_base, long nitems, const double *__restrict__ score, long ldu,
+                                                      int penalty, double tol, int max_iter, FirthFit *__restrict__ out, long blk0) {
+  __shared__ double red[4][4];
+  __shared__ double sh_b;
+  __shared__ int sh_state;                      // 0: a Newton evaluation is next, 1: the evaluation at the accepted beta^ is next, 2: done
+  const long item = blk0 + blockIdx.x;
+  if (item >= nitems) return;
+  const double *g = G + (size_t)item * (size_t)indiv;
+  const long s = item_s[item_base + item];
+  const int c = item_c[item_base + item];
+  const double *p = P + (size_t)c * (size_t)indiv;
+  double v4[4] = {0.0, 0.0, 0.0, 0.0};
+  for (long i = threadIdx.x; i < indiv; i += 256) {
+    const double gi = g[i];
+    v4[0] = __fma_rn(gi, p[i], v4[0]);
+    v4[1] += fabs(gi);
+    v4[2] += fmax(gi, 0.0);
+    v4[3] += fmin(gi, 0.0);
+  }
+  spa_block_sums<4>(v4, red);
+  const double c0 = v4[0], A = v4[1];
+  const double U = score[(size_t)s + (size_t)c * (size_t)ldu];
+  if (threadIdx.x == 0) {
+    sh_b = 0.0;
+    sh_state = 0;
+    const double margin = U >= 0.0 ? (v4[2] - c0) - U : -((v4[3] - c0) - U);
+    if (penalty == 0 && margin <= 0x1p-30 * A) {   // the statistic lies on the edge of its support: the unpenalised likelihood has no maximum
+      out[item].beta = 0.0; out[item].K = 0.0; out[item].k2 = 0.0; out[item].k20 = 0.0; out[item].status = kSpaOutside; out[item].evals = 0;
+      sh_state = 2;
+    }
+  }
+  __syncthreads();
+  int state = __builtin_amdgcn_readfirstlane(sh_state);
+  double b = sh_b, lo = -INFINITY, hi = INFINITY, k20 = 0.0;
+  int evals = 0;
+  while (state != 2) {
+    double v2[2] = {0.0, 0.0}, w2[2] = {0.0, 0.0};   // K (state 1) or K1 (state 0), K2; K3, K4 (state 0 with the penalty)
+    for (long i = threadIdx.x; i < indiv; i += 256) {
+      const double gi = g[i], pi = p[i];
+      const double x = b * gi;
+      const double e = exp(-fabs(x));
+      const bool pos = x >= 0.0;
+      const double al = pos ? pi : 1.0 - pi, be = pos ? 1.0 - pi : pi;
+      const double d = al + be * e, r = 1.0 / d;  // one division a term
+      const double gr = gi * r, abe = al * be * e, t2 = gr * gr * abe;   // t2 = g^2 omega
+      if (state == 1) v2[0] += fmax(x, 0.0) + log(d);
+      else {
+        const double pr = (pos ? pi : pi * e) * r;
+        v2[0] += gi * pr;
+        if (penalty) {
+          const double t3 = t2 * gi;
+          w2[0] = fma(t3, 1.0 - 2.0 * pr, w2[0]);
+          w2[1] = fma(t3 * gi, 1.0 - 6.0 * (abe * r * r), w2[1]);
+        }
+      }
+      v2[1] += t2;
+    }
+    spa_block_sums<2>(v2, red);
+    if (penalty && state == 0) spa_block_sums<2>(w2, red);
+    if (threadIdx.x == 0) {
+      int status = -1;                           // -1: go on
+      double K = 0.0;
+      if (state == 1) {
+        K = v2[0] - b * c0;
+        status = kSpaSolved;
+      } else {
+        evals++;
+        const double K2 = v2[1];
+        if (evals == 1) k20 = K2;
+        double f = (v2[0] - c0) - U, fp = K2;
+        if (penalty) {
+          const double r3 = w2[0] / K2;
+          f -= 0.5 * r3;
+          const double alt = K2 - 0.5 * (w2[1] / K2 - r3 * r3);
+          if (alt > 0.0) fp = alt;
+        }
+        if (f < 0.0) lo = b; else hi = b;
+        double bn = b - f / fp;
+        if (!isfinite(bn)) status = kSpaFailed;
+        else if (fabs(bn - b) <= tol * fabs(bn)) { sh_b = bn; sh_state = 1; }
+        else {
+          if (!(bn > lo && bn < hi)) bn = 0.5 * (lo + hi);
+          if (!isfinite(bn) || evals >= max_iter) status = kSpaFailed;
+          else sh_b = bn;
+        }
+      }
+      if (status >= 0) {
+        out[item].beta = b; out[item].K = K; out[item].k2 = v2[1]; out[item].k20 = k20; out[item].status = status; out[item].evals = evals;
+        sh_state = 2;
+      }
+    }
+    __syncthreads();
+    state = __builtin_amdgcn_readfirstlane(sh_state);
+    b = sh_b;
+  }
+}
+
+// one thread per item of the batch: the results of a converged fit.  The one-step values that k_assoc_firth_classify left stay with the flag 2.
+__global__ void __launch_bounds__(256) k_assoc_firth_combine(long nitems, long item_base, const int *__restrict__ item_s, const int *__restrict__ item_c,
+                                                              const double *__restrict__ score, long ldu, const FirthFit *__restrict__ fit, int penalty, long snps,
+                                                              double *__restrict__ beta, double *__restrict__ se, double *__restrict__ chisq,
+                                                              double *__restrict__ pval, int *__restrict__ flag, long blk0) {
+  const long item = (blk0 + blockIdx.x) * 256 + threadIdx.x;
+  if (item >= nitems) return;
+  const long s = item_s[item_base + item];
+  const int c = item_c[item_base + item];
+  const size_t o = (size_t)s + (size_t)c * (size_t)snps;
+  const FirthFit a = fit[item];
+  flag[o] = 2;
+  if (a.status != kSpaSolved) return;
+  const double e = __ddiv_rn(1.0, __dsqrt_rn(a.k2));
+  double x2 = 2.0 * (a.beta * score[(size_t)s + (size_t)c * (size_t)ldu] - a.K);
+  if (penalty) x2 += log(a.k2 / a.k20);
+  if (!isfinite(e) || !isfinite(x2)) return;
+  x2 = fmax(x2, 0.0);
+  flag[o] = 1;
+  beta[o] = a.beta;
+  se[o] = e;
+  chisq[o] = x2;
+  pval[o] = erfc(sqrt(0.5 * x2));
+}
+
 // ---- host side
 struct HandleHolder {                // the one-shot object is released on every exit path
   Handle *h = nullptr;
@@ -763,7 +918,8 @@ int assoc_linear(const unsigned char *plink, long snps, long indiv, const double
   return 0;
 }
 
-// ---- the saddlepoint stage of mxa_assoc_score_spa: what the entry takes beyond mxa_assoc_score's arguments
+// ---- the stage of mxa_assoc_score_spa and mxa_assoc_score_firth after the scan: what the entries take beyond mxa_assoc_score's arguments.  penalty < 0: the
+// saddlepoint correction (pval required); penalty 0 / 1: the fit (beta required; se, chisq and pval optional)
 struct SpaArgs {
   const double *P;
   long ldp;
@@ -771,12 +927,19 @@ struct SpaArgs {
   int max_iter;
   double *pval;
   int *flag;
+  int penalty = -1;
+  double *beta = nullptr, *se = nullptr, *chisq = nullptr;
+  bool firth() const { return penalty >= 0; }
 };
 
 // the items one batch may hold: MXA_ASSOC_SPA_ITEMS (read per call, for tests), else what fits 4 GiB of g (512 items, 1024 workgroups of k_assoc_spa, at a
-// million individuals); at least the n items of one SNP
-long spa_batch_items(long indiv, int n) {
-  long items = (long)(((size_t)4 << 30) / (sizeof(double) * (size_t)indiv));
+// million individuals) -- the fit: 8 GiB, since k_assoc_firth has one workgroup an item and 512 of them leave half of the device's workgroup slots empty, cut
+// down to a multiple of the kFirthResident workgroups the device holds at once, so that no launch ends in a second round of a few (measured);
+// at least the n items of one SNP
+constexpr long kFirthResident = 1024;   // 256 CUs x 4 workgroups of 4 waves at 114 VGPRs
+long spa_batch_items(long indiv, int n, bool firth) {
+  long items = (long)(((size_t)(firth ? 8 : 4) << 30) / (sizeof(double) * (size_t)indiv));
+  if (firth && items > kFirthResident) items -= items % kFirthResident;
   const char *e = getenv("MXA_ASSOC_SPA_ITEMS");
   if (e && atol(e) > 0) items = atol(e);
   return std::max<long>(n, items);
@@ -789,29 +952,33 @@ long spa_batch_rows(long snps, long bps, bool in_place) {
   return std::min(rows, snps);
 }
 // device memory of the stage at its largest (every trait of every SNP marked): the pre-flight's share
-size_t spa_bytes(long snps, long indiv, int n, int kh, long bps, bool in_place, bool own_u, bool own_z) {
+// (own: the snps x n arrays U, V, z that the stage allocates for itself; firth: beta, se and chisq beside pval, one FirthFit an item)
+size_t spa_bytes(long snps, long indiv, int n, int kh, long bps, bool in_place, int own, bool firth) {
   const size_t cells = (size_t)snps * (size_t)n;
-  const size_t items = (size_t)std::min<long>(spa_batch_items(indiv, n), (long)cells);
-  return cells * (sizeof(double) + sizeof(int)) + (size_t)snps * sizeof(int) + ((size_t)snps + 1) * sizeof(long) + cells * 2 * sizeof(int) +
-         sizeof(double) * (size_t)indiv * (size_t)n * ((size_t)kh + 1) + items * (sizeof(double) * (size_t)indiv + 2 * sizeof(SpaSide)) +
-         (in_place ? 0 : (size_t)spa_batch_rows(snps, bps, false) * (size_t)bps) + ((size_t)own_u + (size_t)own_z) * cells * sizeof(double);
+  const size_t items = (size_t)std::min<long>(spa_batch_items(indiv, n, firth), (long)cells);
+  return cells * ((firth ? 4 : 1) * sizeof(double) + sizeof(int)) + (size_t)snps * sizeof(int) + ((size_t)snps + 1) * sizeof(long) + cells * 2 * sizeof(int) +
+         sizeof(double) * (size_t)indiv * (size_t)n * ((size_t)kh + 1) + items * (sizeof(double) * (size_t)indiv + (firth ? sizeof(FirthFit) : 2 * sizeof(SpaSide))) +
+         (in_place ? 0 : (size_t)spa_batch_rows(snps, bps, false) * (size_t)bps) + (size_t)own * cells * sizeof(double);
 }
 
-// After k_assoc_score_finish on d's stream: dU and dZ are the scan's score and zstat on the device (ld ldu).  One host wait reads the number of marked SNPs
-// and items with the list and its offsets; where nothing is marked neither P nor H is touched and no further kernel is launched.
-int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int kh, const double *dU, const double *dZ, long ldu, long ldo) {
+// After k_assoc_score_finish on d's stream: dU, dV and dZ are the scan's score, var and zstat on the device (ld ldu; dV: the fit only).  One host wait reads the
+// number of marked SNPs and items with the list and its offsets; where nothing is marked neither P nor H is touched and no further kernel is launched.  The two
+// entries share everything but the classify epilogue, the solve and the combine: the list, the items, tau, the batches, the bounce rows and k_assoc_spa_form.
+int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int kh, const double *dU, const double *dV, const double *dZ, long ldu, long ldo) {
   const long snps = d.snps, indiv = d.indiv, bps = d.bps;
   const int n = d.n;
   hipStream_t s = d.s;
   const size_t cells = (size_t)snps * (size_t)n;
+  const bool firth = a.firth();
   XBuf bPv, bFl, bList, bOff, bCount;
-  if (bPv.alloc(sizeof(double) * cells) || bFl.alloc(sizeof(int) * cells) || bList.alloc(sizeof(int) * (size_t)snps) ||
+  if (bPv.alloc(sizeof(double) * cells * (firth ? 4 : 1)) || bFl.alloc(sizeof(int) * cells) || bList.alloc(sizeof(int) * (size_t)snps) ||
       bOff.alloc(sizeof(long) * ((size_t)snps + 1)) || bCount.alloc(2 * sizeof(long))) return 1;
-  double *dPv = (double *)bPv.p;
+  double *dPv = (double *)bPv.p, *dBeta = dPv + cells, *dSe = dBeta + cells, *dChi = dSe + cells;   // (the three of the fit)
   int *dFl = (int *)bFl.p, *dList = (int *)bList.p;
   long *dOff = (long *)bOff.p;
   launch_in_block_chunks(((long)cells + 255) / 256, [&](unsigned nb, long b0) {
-    k_assoc_spa_classify<<<nb, 256, 0, s>>>(snps, n, dZ, ldu, a.z_cutoff, dPv, dFl, b0);
+    if (firth) k_assoc_firth_classify<<<nb, 256, 0, s>>>(snps, n, dU, dV, dZ, ldu, a.z_cutoff, dBeta, dSe, dChi, dPv, dFl, b0);
+    else k_assoc_spa_classify<<<nb, 256, 0, s>>>(snps, n, dZ, ldu, a.z_cutoff, dPv, dFl, b0);
   });
   k_assoc_spa_list<<<1, 256, 0, s>>>(snps, n, dFl, dList, dOff, (long *)bCount.p);
   MXA_HIP(hipGetLastError());
@@ -837,8 +1004,8 @@ int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int 
       k_assoc_spa_items<<<nb, 256, 0, s>>>(nk, snps, n, dFl, dList, dOff, (int *)bItemS.p, (int *)bItemC.p, b0);
     });
     MXA_HIP(hipGetLastError());
-    const long max_items = std::min(spa_batch_items(indiv, n), nitems), max_rows = std::min(spa_batch_rows(snps, bps, d.in_place), nk);
-    if (bG.alloc(sizeof(double) * (size_t)max_items * (size_t)indiv) || bSide.alloc(sizeof(SpaSide) * 2 * (size_t)max_items) ||
+    const long max_items = std::min(spa_batch_items(indiv, n, firth), nitems), max_rows = std::min(spa_batch_rows(snps, bps, d.in_place), nk);
+    if (bG.alloc(sizeof(double) * (size_t)max_items * (size_t)indiv) || bSide.alloc((firth ? sizeof(FirthFit) : 2 * sizeof(SpaSide)) * (size_t)max_items) ||
         (!d.in_place && bRows.alloc((size_t)max_rows * (size_t)bps))) return 1;
     for (long k0 = 0; k0 < nk;) {
       long k1 = k0 + 1;                         // one SNP's items always fit; further SNPs while the rows and the items do
@@ -860,29 +1027,41 @@ int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int 
         k_assoc_spa_form<<<nb, 256, 0, s>>>(d_rows, bps, d.in_place ? 0 : 1, indiv, snps, n, kh, dList, dOff, k0, k1, dFl, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD,
                                             d.dM, (const double *)bHt.p, (double *)bG.p, (long)iblocks, b0);
       });
-      launch_in_block_chunks(2 * items, [&](unsigned nb, long b0) {
-        k_assoc_spa<<<nb, 256, 0, s>>>((const double *)bG.p, indiv, (const double *)bP.p, (const int *)bItemS.p, (const int *)bItemC.p, off[(size_t)k0], items, dU, ldu,
-                                       a.tol, a.max_iter, (SpaSide *)bSide.p, b0);
+      launch_in_block_chunks(firth ? items : 2 * items, [&](unsigned nb, long b0) {
+        if (firth)
+          k_assoc_firth<<<nb, 256, 0, s>>>((const double *)bG.p, indiv, (const double *)bP.p, (const int *)bItemS.p, (const int *)bItemC.p, off[(size_t)k0], items, dU,
+                                           ldu, a.penalty, a.tol, a.max_iter, (FirthFit *)bSide.p, b0);
+        else
+          k_assoc_spa<<<nb, 256, 0, s>>>((const double *)bG.p, indiv, (const double *)bP.p, (const int *)bItemS.p, (const int *)bItemC.p, off[(size_t)k0], items, dU,
+                                         ldu, a.tol, a.max_iter, (SpaSide *)bSide.p, b0);
       });
       launch_in_block_chunks((items + 255) / 256, [&](unsigned nb, long b0) {
-        k_assoc_spa_combine<<<nb, 256, 0, s>>>(items, off[(size_t)k0], (const int *)bItemS.p, (const int *)bItemC.p, dU, ldu, (const SpaSide *)bSide.p, snps, dPv, dFl, b0);
+        if (firth)
+          k_assoc_firth_combine<<<nb, 256, 0, s>>>(items, off[(size_t)k0], (const int *)bItemS.p, (const int *)bItemC.p, dU, ldu, (const FirthFit *)bSide.p, a.penalty,
+                                                   snps, dBeta, dSe, dChi, dPv, dFl, b0);
+        else
+          k_assoc_spa_combine<<<nb, 256, 0, s>>>(items, off[(size_t)k0], (const int *)bItemS.p, (const int *)bItemC.p, dU, ldu, (const SpaSide *)bSide.p, snps, dPv, dFl,
+                                                 b0);
       });
       MXA_HIP(hipGetLastError());
       k0 = k1;
     }
   }
   const size_t pcol = sizeof(double) * (size_t)snps, fcol = sizeof(int) * (size_t)snps;
-  MXA_HIP(hipMemcpy2DAsync(a.pval, sizeof(double) * (size_t)ldo, dPv, pcol, pcol, (size_t)n, hipMemcpyDefault, s));
+  const struct { double *to; const double *from; } results[4] = {{a.pval, dPv}, {a.beta, dBeta}, {a.se, dSe}, {a.chisq, dChi}};
+  for (int j = 0; j < (firth ? 4 : 1); j++)
+    if (results[j].to) MXA_HIP(hipMemcpy2DAsync(results[j].to, sizeof(double) * (size_t)ldo, results[j].from, pcol, pcol, (size_t)n, hipMemcpyDefault, s));
   if (a.flag) MXA_HIP(hipMemcpy2DAsync(a.flag, sizeof(int) * (size_t)ldo, dFl, fcol, fcol, (size_t)n, hipMemcpyDefault, s));
   MXA_HIP(hipStreamSynchronize(s));             // the buffers of the stage are released on return
   return 0;
 }
 
-// B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c.  spa: the saddlepoint stage follows the epilogue
+// B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c.  spa: the stage of the saddlepoint correction or of the
+// fit follows the epilogue
 int assoc_score(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
                 double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const SpaArgs *spa = nullptr) {
   const int ncols = n * (kh + 2);
-  AssocDriver d(spa ? "mxa_assoc_score_spa" : "mxa_assoc_score", snps, indiv, ncols, n, out_dev);
+  AssocDriver d(!spa ? "mxa_assoc_score" : spa->firth() ? "mxa_assoc_score_firth" : "mxa_assoc_score_spa", snps, indiv, ncols, n, out_dev);
   double *const res[3] = {score, var, zstat};
   const size_t e_bytes = sizeof(double) * (size_t)snps * (size_t)n;
   size_t extra = e_bytes;
@@ -891,15 +1070,16 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
     const int dev = select_device();
     if (dev < 0) return 1;
     const bool in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;
-    extra += spa_bytes(snps, indiv, n, kh, (indiv + 3) / 4, in_place, !score, !zstat);
+    extra += spa_bytes(snps, indiv, n, kh, (indiv + 3) / 4, in_place, !score + !zstat + (spa->firth() && !var), spa->firth());
   }
   if (d.begin(plink, res, extra)) return 1;
   hipStream_t s = d.s;
-  XBuf bE, bU, bZ;
+  XBuf bE, bU, bV, bZ;
   if (bE.alloc(e_bytes)) return 1;
   const long ldu = out_dev ? ldo : snps;
-  if (spa) {                                    // the stage reads U and z on the device, whether the caller asked for them or not
+  if (spa) {                                    // the stage reads U and z (the fit: and V) on the device, whether the caller asked for them or not
     if (!d.out_d[0]) { if (bU.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[0] = (double *)bU.p; }
+    if (spa->firth() && !d.out_d[1]) { if (bV.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[1] = (double *)bV.p; }
     if (!d.out_d[2]) { if (bZ.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[2] = (double *)bZ.p; }
   }
   double *dE = (double *)bE.p;
@@ -929,7 +1109,7 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
                                             ldu, b0);
   });
   MXA_HIP(hipGetLastError());
-  if (spa && spa_stage(d, plink, *spa, kh, d.out_d[0], d.out_d[2], ldu, ldo)) return 1;
+  if (spa && spa_stage(d, plink, *spa, kh, d.out_d[0], d.out_d[1], d.out_d[2], ldu, ldo)) return 1;
   return d.copy_out(res, ldo, nobs);
 }
 
@@ -1032,6 +1212,32 @@ extern "C" int mxa_assoc_score_spa(const unsigned char *plink, int snps, int ind
   (void)hipGetDevice(&prev);
   const SpaArgs spa = {P, ldp, z_cutoff, tol, max_iter, pval, flag};
   const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0, &spa);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  return rc;
+}
+
+extern "C" int mxa_assoc_score_firth(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
+                                     const double *H, long ldh, int n, int kh, double z_cutoff, int penalty, double tol, int max_iter, double *score, double *var,
+                                     double *zstat, double *beta, double *se, double *chisq, double *pval, long ldo, int *flag, int *nobs) {
+  using namespace mxa;
+  clear_error();
+  const char *who = "mxa_assoc_score_firth";
+  const char *bad = assoc_score_firth_args(plink, snps, indiv, P, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, penalty, tol, max_iter, score, var, zstat, beta, ldo);
+  if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
+  int given = 0, on_dev = 0;
+  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat, (const double *)beta, (const double *)se, (const double *)chisq,
+                          (const double *)pval})
+    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
+  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var, zstat, beta, se, chisq and pval must be all host or all device pointers", who); return 1; }
+  if (flag && (ptr_location(flag, nullptr) == 1) != (on_dev != 0)) { set_error(1, "%s: flag and beta must be both host or both device pointers", who); return 1; }
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  SpaArgs fit = {P, ldp, z_cutoff, tol, max_iter, pval, flag};
+  fit.penalty = penalty;
+  fit.beta = beta;
+  fit.se = se;
+  fit.chisq = chisq;
+  const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0, &fit);
   if (prev >= 0) (void)hipSetDevice(prev);
   return rc;
 }

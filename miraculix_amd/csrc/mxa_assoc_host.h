@@ -1,6 +1,7 @@
 // mxa_assoc_host.h -- the host-only part of the association scan (mxa_assoc.hip): the covariate basis of mxa_assoc_basis and the argument rules of
-// mxa_assoc_linear, mxa_assoc_score and mxa_assoc_score_spa (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
-// program can compile it for the CPU (tools/assoc_host_check.cpp, tools/assoc_score_host_check.cpp, run under -fsanitize=address,undefined).
+// mxa_assoc_linear, mxa_assoc_score, mxa_assoc_score_spa and mxa_assoc_score_firth (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
+// program can compile it for the CPU (tools/assoc_host_check.cpp, tools/assoc_score_host_check.cpp, tools/assoc_firth_host_check.cpp, run under
+// -fsanitize=address,undefined).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -99,6 +100,17 @@ inline const char *assoc_score_spa_args(const void *plink, long snps, long indiv
   if (!(z_cutoff >= 0.0)) return "z_cutoff must not be negative or NaN";
   if (!(tol > 0.0 && tol < 1.0)) return "tol must lie in (0, 1)";
   if (max_iter < 1) return "max_iter must be at least 1";
+  return nullptr;
+}
+
+// The same for mxa_assoc_score_firth: mxa_assoc_score_spa's rules with beta in pval's place, then its own.  (Mixed sides among the results are the caller's check.)
+inline const char *assoc_score_firth_args(const void *plink, long snps, long indiv, const void *P, long ldp, const void *R, long ldr, const void *Wt, long ldw,
+                                          const void *H, long ldh, int n, int kh, double z_cutoff, int penalty, double tol, int max_iter, const void *score,
+                                          const void *var, const void *zstat, const void *beta, long ldo) {
+  if (const char *bad = assoc_score_args(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo)) return bad;
+  if (!P || !beta) return "P and beta must not be NULL";
+  if (const char *bad = assoc_score_spa_args(plink, snps, indiv, P, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, tol, max_iter, score, var, zstat, beta, ldo)) return bad;
+  if (penalty != 0 && penalty != 1) return "penalty must be 0 or 1";
   return nullptr;
 }
 

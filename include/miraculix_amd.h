@@ -681,6 +681,9 @@ int mxa_assoc_score_spa(const unsigned char *plink, int snps, int indiv, const d
  *           replaced by (lo + hi) / 2 (not finite: the fit fails), and beta = beta'.  At most max_iter such evaluations, else the fit fails.  The first
  *           evaluation is at beta = 0 and yields K''(0); one evaluation of K and K'' at the accepted beta^ is not counted.
  *   flag 2  the statistic is outside the support (penalty == 0), the fit fails, or se or chisq below is not finite: the one-step values of flag 0.
+ *           A first step that saturates every exp (fitted probabilities of some 1e-5 and less at the carriers with kh = 0, so that exp(-|beta g_i|) = 0
+ *           and K'' = 0 at the second evaluation; or p_i in {0, 1} at the carriers, K''(0) = 0 at the first) makes beta' not finite: a failed fit
+ *           with the one-step values.
  *   flag 1  otherwise: beta = beta^, se = 1 / sqrt(K''(beta^)), chisq = max(0, 2 (beta^ U - K(beta^)) + penalty log(K''(beta^) / K''(0))),
  *           pval = erfc(sqrt(chisq / 2)).
  * Every sum over the individuals runs in an order fixed by indiv alone, no atomics; list, items, batches and g are those of mxa_assoc_score_spa, and

@@ -62,7 +62,9 @@ void setOptions_compressed(int use_gpu, int cores, int floatLoop, int meanSubstr
  * from two pointers.  On failure *compressed is left NULL and a message is printed (reference: print + handle unset).
  * Padding bits: IGNORED in both matrices (fields at and beyond indiv of a SNP-major row, at and beyond snps of an individual-major row), for every call
  * shape and for the other staging entries (mxa_plink2compressed_shard, _begin / _rows / _end, mxa_bed2compressed(_range)); so are they by every product of the
- * object and by get_compressed_freq. */
+ * object and by get_compressed_freq.
+ * A host matrix is uploaded in row chunks through a bounce buffer of 256 MB, or of MXA_STAGE_CHUNK_ROWS rows (a test knob, read per call; so do
+ * mxa_plink2compressed_shard, mxa_plink2compressed_rows and dgemm_plink): results are bit-identical for every chunk size. */
 void plink2compressed(char *plink, char *plink_transposed, int snps, int indiv, double *f, int max_n,
                       void **compressed);
 
@@ -125,6 +127,8 @@ void dgemm_plink(char *trans, char *plink, char *plink_transposed, int snps, int
  * missing 01 pair -> 0xFF).  Exact int32 accumulation.  snp_matrix and ans may be host or device pointers.
  * Padding bits: AS STORED.  The reference multiplies whole bytes (snp_multiply_cuda.h:121-210), and so does this: when snps is no multiple of 4, the fields
  * at and beyond snps of a row's last byte are multiplied like genotypes (and a 01 among them makes the byte 0xFF under the table).
+ * A host snp_matrix is uploaded in row chunks through a bounce buffer of 256 MiB, or of MXA_STAGE_CHUNK_ROWS rows (a test knob, read per call; so do
+ * mxa_snp_multiply_panel, mxa_grm, mxa_ld and every windowed-LD entry that takes the packed matrix): results are bit-identical for every chunk size.
  * Returns 0 on success, 1 on failure. */
 int snp_multiply_gpu(unsigned char *snp_matrix, int snps, int indiv, double *ans, bool is_plink_format);
 
@@ -215,7 +219,9 @@ int mxa_allele_freq(const unsigned char *plink, long snps, long indiv, double *f
  * individual-major copy with the on-device 2-bit transpose and the allele frequencies with the on-device popcount
  * (f_s = allele count / (2 indiv)), and returns the same kind of object as plink2compressed.  snps / indiv <= 0: taken
  * from the line counts of the .bim / .fam files next to the .bed.  f_out (optional, host, snps doubles) receives the
- * frequencies; snps_out / indiv_out (optional) the dimensions.  Returns 0 / 1; *compressed is NULL on failure. */
+ * frequencies; snps_out / indiv_out (optional) the dimensions.  Returns 0 / 1; *compressed is NULL on failure.
+ * The file is read in chunks of 64 MiB, or of MXA_STAGE_CHUNK_ROWS rows (a test knob, read per call, also by mxa_bed2compressed_range and the in-process
+ * sharder): results are bit-identical for every chunk size. */
 int mxa_bed2compressed(const char *bed_path, int snps, int indiv, int max_n, void **compressed, double *f_out, int *snps_out,
                        int *indiv_out);
 

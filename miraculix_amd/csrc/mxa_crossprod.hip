@@ -1011,8 +1011,7 @@ int stage_operand(const unsigned char *snp_matrix, bool in_dev, long row_bytes, 
     MXA_HIP(hipGetLastError());
     return 0;
   }
-  long chunk_rows = std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)row_bytes));
-  chunk_rows = std::min(chunk_rows, rows);
+  const long chunk_rows = stage_chunk_rows(rows, (size_t)row_bytes, (size_t)256 << 20);   // (MXA_STAGE_CHUNK_ROWS: tests)
   if (bounce.alloc((size_t)chunk_rows * row_bytes)) return 1;
   for (long r0 = 0; r0 < rows; r0 += chunk_rows) {
     const long nr = std::min(chunk_rows, rows - r0);
@@ -1094,7 +1093,7 @@ static int crossprod_any(const unsigned char *snp_matrix, long k, long rows, dou
   MXA_HIP(hipMemGetInfo(&free_b, &total_b));
   // a pipelined result can leave through the ring of three ~1 GiB slabs: the n x n device copy is then not needed
   const size_t out_need = out_dev ? 0 : (pipelined ? std::min<size_t>(abytes, (size_t)3400 << 20) : abytes);
-  const size_t need = xbytes + out_need + (in_dev ? 0 : std::min<size_t>((size_t)rows * row_bytes, (size_t)256 << 20));
+  const size_t need = xbytes + out_need + (in_dev ? 0 : (size_t)stage_chunk_rows(rows, (size_t)row_bytes, (size_t)256 << 20) * row_bytes);   // the bounce buffer stage_operand allocates
   if (need > free_b) { set_error(12, "snp_multiply_gpu: not enough device memory: required %zu GB, free %zu GB", need >> 30, free_b >> 30); return 1; }
   // a host result in fresh memory (crossproduct.jl:56 `M = zeros(...)`): its pages are populated in the background while the tiles are computed, so that
   // the copies do not pay the first-touch faults (mxa_hostmem.h).  Joined when this returns.

@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <mutex>
 #include <utility>
@@ -30,6 +31,16 @@ constexpr long kMaxBlocksPerLaunch = 1L << 23;
 template <typename Launch>
 inline void launch_in_block_chunks(long blocks, Launch &&launch) {
   for (long b0 = 0; b0 < blocks; b0 += kMaxBlocksPerLaunch) launch((unsigned)(blocks - b0 < kMaxBlocksPerLaunch ? blocks - b0 : kMaxBlocksPerLaunch), b0);
+}
+
+// Rows of one chunk where a host matrix or a .bed file is brought to the device in row chunks (recode_host_rows, stage_operand, bed_range_to_handle, and the
+// memory pre-flights that count their bounce buffer): what fits default_bytes, or MXA_STAGE_CHUNK_ROWS rows where that is a positive integer (tests: results
+// are bit-identical for every chunk size); clamped to [1, rows].  Read per call.
+inline long stage_chunk_rows(long rows, size_t row_bytes, size_t default_bytes) {
+  long chunk = (long)(default_bytes / (row_bytes ? row_bytes : 1));
+  const char *e = getenv("MXA_STAGE_CHUNK_ROWS");
+  if (e && atol(e) > 0) chunk = atol(e);
+  return chunk < 1 ? 1 : chunk > rows ? (rows < 1 ? 1 : rows) : chunk;
 }
 
 struct Options {

@@ -175,7 +175,7 @@ struct LdWindow {
     const size_t wbytes = sizeof(int) * (size_t)g.nb + (general() ? sizeof(int) * (size_t)snps + sizeof(long) * ((size_t)snps + 1) : 0);   // jmax, last, rowptr
     size_t free_b = 0, total_b = 0;
     MXA_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t need = planes * plane_bytes + pbytes + wbytes + extra_bytes() + (out_dev ? 0 : obytes) + (in_dev ? 0 : std::min<size_t>((size_t)snps * row_bytes, (size_t)256 << 20));
+    const size_t need = planes * plane_bytes + pbytes + wbytes + extra_bytes() + (out_dev ? 0 : obytes) + (in_dev ? 0 : (size_t)stage_chunk_rows(snps, (size_t)row_bytes, (size_t)256 << 20) * row_bytes);   // the bounce buffer stage_operand allocates
     if (need > free_b) { set_error(12, "%s: not enough device memory: required %zu GB, free %zu GB", who, need >> 30, free_b >> 30); return 1; }
     if (st.create(hipStreamDefault)) return 1;   // blocking: ordered against the caller's default-stream work
     s = st.s;

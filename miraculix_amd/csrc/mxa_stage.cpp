@@ -30,9 +30,7 @@ static void describe_matrix(PackedMatrix &M, long rows, long k) {
 // is waited for: the bounce buffer is reused, and on return the caller may reuse its rows.
 static int recode_host_rows(PackedMatrix &M, const uint8_t *src, size_t src_pitch, long row0, long nrows, long k, double *d_freq, hipStream_t s) {
   const long row_bytes = (k + 3) / 4;
-  const size_t chunk_bytes = (size_t)256 << 20;
-  long chunk_rows = std::max<long>(1, (long)(chunk_bytes / (size_t)std::max<long>(1, row_bytes)));
-  chunk_rows = std::min(chunk_rows, nrows);
+  const long chunk_rows = stage_chunk_rows(nrows, (size_t)row_bytes, (size_t)256 << 20);   // (MXA_STAGE_CHUNK_ROWS: tests)
   uint8_t *bounce = nullptr;
   MXA_HIP(hipMalloc(reinterpret_cast<void **>(&bounce), (size_t)chunk_rows * row_bytes));
   int rc = 0;
@@ -354,8 +352,8 @@ int bed_range_to_handle(const char *base_c, long snps_total, long indiv, long sn
   hipStream_t cs = nullptr;
   int rc = 0;
   auto bad = [&](hipError_t e, int line) { if (e != hipSuccess) { check_hip(e, "mxa_bed2compressed", line); rc = 1; } return rc; };
-  const size_t rows_per_chunk = std::max<size_t>(1, ((size_t)64 << 20) / bps);
-  const size_t chunk_bytes = std::min(rows_per_chunk, (size_t)rows) * bps;
+  const size_t rows_per_chunk = (size_t)stage_chunk_rows(rows, bps, (size_t)64 << 20);   // (MXA_STAGE_CHUNK_ROWS: tests)
+  const size_t chunk_bytes = rows_per_chunk * bps;
   // only the SNP-major copy will be kept (no transposed block is built): asked for, or the raw block + its transpose + the two packed copies do not fit
   bool single;
   {

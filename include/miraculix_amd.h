@@ -706,6 +706,51 @@ int mxa_assoc_score_firth(const unsigned char *plink, int snps, int indiv, const
                           const double *H, long ldh, int n, int kh, double z_cutoff, int penalty, double tol, int max_iter, double *score, double *var,
                           double *zstat, double *beta, double *se, double *chisq, double *pval, long ldo, int *flag, int *nobs);
 
+/* Set-based association: burden and SKAT statistics of SNP sets (genes, masks of rare variants, regions) under the null models of mxa_assoc_score.
+ * mxa_assoc_score runs unchanged; the set stage follows it on the device.  plink, R, Wt, H, n, kh, score, var, zstat, ldo and nobs are those of
+ * mxa_assoc_score; score, var, zstat and nobs are ALL optional here, and any of them that is given receives bit for bit what mxa_assoc_score returns for the
+ * same operands.  A linear model passes R = residual / sigma^2, Wt = 1 / sigma^2, H = W C L^-T.
+ * The sets are a CSR list on the HOST: set_ptr has nsets + 1 entries, non-decreasing, set_ptr[0] == 0; set_idx has set_ptr[nsets] SNP indices in [0, snps), in
+ * any order; sets may overlap and a SNP may repeat within a set (no special case); set_wt (nullable: all ones) is parallel to set_idx and holds the variant
+ * weights omega.  The size m_k = set_ptr[k + 1] - set_ptr[k] of a set satisfies 0 <= m_k <= 1024 (Phi of one (set, trait): at most 8 MiB).
+ * Per set k and trait c, for its entries j, j' with s = set_idx[j]; mu, U_j and a_jh the scan's own values of SNP s (mxa_assoc_score's chain), w_c,i the
+ * trait's working weights and x_j,i the allele count of individual i with missing calls replaced by mu (padding fields are not individuals):
+ *   S_jj'   = sum_i x_j,i (w_c,i x_j',i) for j <= j', on the fp64 matrix unit: the product w x rounded once, the sum over the individuals in pieces of 4096
+ *             (each piece: four interleaved runs of 64-genotype words, added as (r0 + r1) + (r2 + r3)), the pieces added in ascending order;
+ *   Phi_jj' = S_jj', then for h ascending Phi_jj' = fma(-a_jh, a_j'h, Phi_jj'); computed for j <= j' and mirrored: Phi_jj' == Phi_j'j bit for bit;
+ *   A_jj'   = (omega_j Phi_jj') omega_j', each product rounded once;
+ *   B = sum_j omega_j U_j,  Q = sum_j (omega_j U_j)^2,  c1 = sum_j A_jj  over ascending j;
+ *   varB = sum_jj' A_jj',  c2 = sum_jj' A_jj'^2,  c4 = sum_jj' ((A A)_jj')^2 with (A A)_jj' = the chain fma(A_jl, A_lj', .) over ascending l, never stored:
+ *             per tile of 16 rows j a fixed tree over the columns j', the tiles added in ascending order.
+ * The burden test is B / sqrt(varB) (p = erfc(|B| / sqrt(2 varB)), a wrapper's line), the SKAT statistic is Q, and mxa_assoc_skat_pvalue turns (Q, c1, c2, c4)
+ * into its p-value.  An empty set gives zeros.  A SNP without any called individual (N = 0) makes the results of the sets that contain it non-finite and touches
+ * no other set.
+ * stat (required): nsets x 6 n doubles, column-major, ld lds >= nsets: column 6 c + t holds for trait c B (t = 0), varB (1), Q (2), c1 (3), c2 (4), c4 (5);
+ *   nothing is written beyond row nsets - 1.  phi (optional): n sum_k m_k^2 doubles, the block of (k, c) is m_k x m_k column-major at the offset
+ *   n sum_{k' < k} m_k'^2 + c m_k^2 (for SKAT-O, Davies or Kuonen p-values from eigenvalues, which this library does not offer).
+ *   score, var, zstat, stat and phi are all host or all device pointers; plink, R, Wt and H are host or device pointers, each independently.
+ * Every sum over the individuals runs in an order fixed by indiv alone, every sum over a set in an order fixed by m_k alone, no atomics: results are identical
+ * from run to run, between host and device pointers, for every MXA_ASSOC_CHUNK_ROWS and for every batch size of the set stage, and a set's results do not
+ * depend on which other sets are in the call.  As before they are NOT bit-identical between column counts n (kh + 2).  The stage works in batches of consecutive
+ * sets: a batch is cut where its S / Phi blocks and partial sums would exceed 1 GiB, or its set entries MXA_ASSOC_SET_BATCH (environment, read per call, for
+ * tests; default: no limit on the entries); it never holds less than one whole set.  The rows of a batch's distinct SNPs of a host matrix are copied to a
+ * bounce buffer (runs of neighbouring rows in one copy); a device matrix is read in place.
+ * Errors (return 1, mxa_last_error() == 1, outputs untouched, all decided before a device is selected): every error of mxa_assoc_score except its "score, var
+ *   and zstat are all NULL"; nsets < 1; NULL set_ptr, set_idx or stat; set_ptr[0] != 0 or set_ptr decreasing; an index outside [0, snps) (the message names
+ *   the set and the entry); m_k > 1024; lds < nsets; mixed host and device pointers among the results.  12: not enough device memory (what mxa_assoc_score
+ *   lists, a score array where none is given, and of the stage: the bounce rows of its largest batch, one batch of S / Phi with its partial sums of 2 KiB per
+ *   (set, trait, tile pair, piece), the batch's lists, and the device copy of a host stat). */
+int mxa_assoc_set(const unsigned char *plink, int snps, int indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
+                  int nsets, const long *set_ptr, const int *set_idx, const double *set_wt, double *score, double *var, double *zstat, long ldo, int *nobs,
+                  double *stat, long lds, double *phi);
+/* The SKAT p-value of `count` items, on the host (no device is needed): Q = sum lambda_i chi^2_1 with the eigenvalues lambda of a positive semi-definite A is
+ * matched to a scaled central chi-square by c1 = tr A, c2 = tr A^2, c4 = tr A^4 (Liu's moment matching in its modified form; by Cauchy-Schwarz c3^2 <= c2 c4,
+ * so its non-central branch is never taken): l = c2^2 / c4, x = (Q - c1) sqrt(l / c2) + l, pval = the regularised upper incomplete gamma function
+ * Q(l / 2, x / 2), and exactly 1 where x <= 0.  Sums in long double on the log scale, the series for x / 2 < l / 2 + 1 and the continued fraction otherwise:
+ * tails down to the smallest doubles keep a relative error below 2^-40.  A non-finite Q, c1, c2 or c4, or c2 <= 0 or c4 <= 0, gives NaN (also in df).
+ * df (nullable) receives l.  Errors (return 1, error 1): count < 0; a NULL Q, c1, c2, c4 or pval with count > 0. */
+int mxa_assoc_skat_pvalue(long count, const double *Q, const double *c1, const double *c2, const double *c4, double *pval, double *df);
+
 /* multiply engine of dgemm_compressed (process-wide; MXA_ENGINE in the environment sets the initial one).  Details and error bounds: DESIGN.md 3.2 / 3.3.
  *
  *   id  MXA_ENGINE   arithmetic                                                                     host waits

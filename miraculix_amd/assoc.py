@@ -1,6 +1,7 @@
 """Association scan (C entries mxa_assoc_basis, mxa_assoc_linear): per-SNP linear regression y ~ 1 + covariates + x_s on packed genotypes, missing calls
 imputed by the SNP's mean; and, for binary traits, the score test of a logistic null model fitted once per trait (mxa_assoc_logistic_null, mxa_assoc_score),
-with saddlepoint p-values for unbalanced case-control data (mxa_assoc_score_spa) and with effect sizes by Firth-penalised fits (mxa_assoc_score_firth).
+with saddlepoint p-values for unbalanced case-control data (mxa_assoc_score_spa) and with effect sizes by Firth-penalised fits (mxa_assoc_score_firth);
+and the burden and SKAT tests of SNP sets under the same null models (mxa_assoc_set, mxa_assoc_skat_pvalue).
 The definitions, the operation orders and what is exact: include/miraculix_amd.h."""
 import ctypes
 from collections import namedtuple
@@ -333,4 +334,126 @@ def assoc_logistic(plink, snps, indiv, Y, covariates=None, spa=False, firth=Fals
     res = assoc_score(plink, snps, indiv, R, Wt, H)
     if one_dim:
         return AssocScoreResult(res.score.reshape(-1), res.var.reshape(-1), res.z.reshape(-1), res.nobs)
+    return res
+
+
+# ---- set tests: burden and SKAT (C entries mxa_assoc_set, mxa_assoc_skat_pvalue)
+AssocSetResult = namedtuple("AssocSetResult", "burden burden_var skat c1 c2 c4 burden_p skat_p skat_df phi")
+SET_MAX_SIZE = 1024
+
+
+def assoc_skat_pvalue(Q, c1, c2, c4):
+    """(pval, df) of the SKAT statistics Q with the moments c1 = tr A, c2 = tr A^2, c4 = tr A^4, arrays of one shape: Liu's moment matching in its modified form,
+    on the host (C entry mxa_assoc_skat_pvalue).  Non-finite or non-positive moments give NaN."""
+    q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64))
+    m = [np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (c1, c2, c4)]
+    if any(a.shape != q.shape for a in m):
+        raise ValueError("Q, c1, c2 and c4 need one shape")
+    pval, df = np.zeros(q.shape), np.zeros(q.shape)
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_skat_pvalue(int(q.size), _lib.ptr(q), _lib.ptr(m[0]), _lib.ptr(m[1]), _lib.ptr(m[2]), _lib.ptr(pval), _lib.ptr(df)), "mxa_assoc_skat_pvalue")
+    return pval, df
+
+
+def _set_csr(sets, weights):
+    """(set_ptr int64, set_idx int32, set_wt float64 or None).  sets: a LIST of index arrays, or a TUPLE (set_ptr, set_idx) -- the type decides, never the
+    contents, so that two index sets are not mistaken for a CSR pair; weights: a list parallel to sets, or flat"""
+    if isinstance(sets, tuple):
+        if len(sets) != 2 or np.ndim(sets[0]) != 1 or np.ndim(sets[1]) != 1 or len(sets[0]) < 1:
+            raise ValueError("a tuple for sets needs to be the CSR pair (set_ptr, set_idx); pass index arrays as a list")
+        ptr, idx = np.ascontiguousarray(sets[0], dtype=np.int64), np.ascontiguousarray(sets[1], dtype=np.int32)
+        if ptr[0] != 0 or np.any(np.diff(ptr) < 0) or int(ptr[-1]) != idx.size:
+            raise ValueError("set_ptr needs to start at 0, not to decrease and to end at len(set_idx)")
+    elif isinstance(sets, list):
+        arrays = [np.asarray(a, dtype=np.int32).reshape(-1) for a in sets]
+        ptr = np.zeros(len(arrays) + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum([a.size for a in arrays])
+        idx = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0, np.int32), dtype=np.int32)
+    else:
+        raise ValueError("sets needs to be a list of index arrays or the tuple (set_ptr, set_idx)")
+    if ptr.size < 2:
+        raise ValueError("sets needs to hold at least one set")
+    wt = None
+    if weights is not None:
+        if isinstance(weights, (list, tuple)) and len(weights) and np.ndim(weights[0]) > 0:
+            wt = np.concatenate([np.asarray(w, dtype=np.float64).reshape(-1) for w in weights])
+        else:
+            wt = np.asarray(weights, dtype=np.float64).reshape(-1)
+        wt = np.ascontiguousarray(wt, dtype=np.float64)
+        if wt.size != idx.size:
+            raise ValueError(f"weights need one entry per set entry: {wt.size}, {idx.size}")
+    return ptr, idx, wt
+
+
+def assoc_set(plink, snps, indiv, R, Wt, H, sets, weights=None, out=None, want_phi=False):
+    """Burden and SKAT tests of SNP sets under the null models of assoc_score (C entry mxa_assoc_set).  plink, R, Wt, H: as for assoc_score.  sets: a list of
+    arrays of SNP indices (any order, overlaps and repeats allowed, at most 1024 each), or the tuple (set_ptr, set_idx) of a CSR list (a list is always index
+    arrays, a tuple always the CSR pair); weights: the variant weights omega,
+    a list parallel to sets or one flat array parallel to set_idx (None: ones).  Returns AssocSetResult: burden B, burden_var, skat Q, c1, c2, c4, burden_p =
+    erfc(|B| / sqrt(2 burden_var)), skat_p and skat_df (assoc_skat_pvalue), each (nsets, n) numpy, or (nsets,) for a one-dimensional R; phi: None, or with
+    want_phi=True a list over the sets of (n, m, m) arrays, the null covariance of the set's scores for every trait.  out: an optional dict that receives the
+    scan's own "score", "var", "z" ((snps, n) Fortran-ordered numpy, as for assoc_score) and "nobs" ((snps,) int32)."""
+    from math import erfc, sqrt
+    snps, indiv = int(snps), int(indiv)
+    rc, wc, hc, n, kh = _score_operands(plink, snps, indiv, R, Wt, H)
+    ptr, idx, wt = _set_csr(sets, weights)
+    nsets = ptr.size - 1
+    sizes = np.diff(ptr)
+    if np.any(sizes < 0) or np.any(sizes > SET_MAX_SIZE) or ptr[0] != 0:
+        raise ValueError(f"set sizes need to lie in [0, {SET_MAX_SIZE}]")
+    if idx.size and (idx.min() < 0 or idx.max() >= snps):
+        raise ValueError(f"set indices need to lie in [0, {snps})")
+    one_dim = len(tuple(R.shape)) == 1
+    scan = {}
+    nobs = None
+    if out is not None:
+        if any(key not in ("score", "var", "z", "nobs") for key in out):
+            raise ValueError("out may hold the keys 'score', 'var', 'z', 'nobs'")
+        for key, o in out.items():
+            if key == "nobs":
+                if not (isinstance(o, np.ndarray) and o.dtype == np.int32 and o.shape == (snps,) and o.flags.c_contiguous):
+                    raise ValueError(f"out['nobs'] needs to be a contiguous int32 ({snps},) array")
+                nobs = o
+                continue
+            if not (isinstance(o, np.ndarray) and o.shape == (snps, n) and o.dtype == np.float64 and o.T.flags.c_contiguous):
+                raise ValueError(f"out[{key!r}] needs to be a float64 ({snps}, {n}) numpy result with contiguous columns")
+            scan[key] = o.T
+    stat = np.zeros((6 * n, nsets), dtype=np.float64)
+    phi = np.zeros(n * int(np.sum(sizes * sizes)), dtype=np.float64) if want_phi else None
+    L = _lib.check_library_handle()
+    _check(L.mxa_assoc_set(_lib.ptr(plink), snps, indiv, _lib.ptr(rc), indiv, _lib.ptr(wc), indiv, _lib.ptr(hc), indiv, n, kh, nsets, _lib.ptr(ptr), _lib.ptr(idx),
+                           _lib.ptr(wt), _lib.ptr(scan.get("score")), _lib.ptr(scan.get("var")), _lib.ptr(scan.get("z")), snps, _lib.ptr(nobs), _lib.ptr(stat), nsets,
+                           _lib.ptr(phi)), "mxa_assoc_set")
+    cols = [np.ascontiguousarray(stat[t::6].T) for t in range(6)]          # (nsets, n) each
+    with np.errstate(invalid="ignore", divide="ignore"):
+        zb = np.abs(cols[0]) / np.sqrt(2.0 * cols[1])
+    burden_p = np.array([erfc(v) if np.isfinite(v) else np.nan for v in zb.reshape(-1)]).reshape(zb.shape)
+    skat_p, skat_df = assoc_skat_pvalue(cols[2], cols[3], cols[4], cols[5])
+    blocks = None
+    if want_phi:
+        blocks, at = [], 0
+        for m in sizes:
+            m = int(m)
+            blocks.append(phi[at:at + n * m * m].reshape(n, m, m).transpose(0, 2, 1))
+            at += n * m * m
+    res = cols + [burden_p, skat_p, skat_df]
+    if one_dim:
+        res = [a.reshape(nsets) for a in res]
+    return AssocSetResult(*res, blocks)
+
+
+def assoc_logistic_sets(plink, snps, indiv, Y, covariates, sets, weights=None, want_phi=False):
+    """The set tests for the 0 / 1 traits Y ((indiv, n) or (indiv,), numpy): the null model of each trait is fitted on the host (assoc_logistic_null), R, Wt and H
+    are stacked, and assoc_set runs.  Returns AssocSetResult."""
+    Ya = np.asarray(Y, dtype=np.float64)
+    if Ya.ndim not in (1, 2) or Ya.shape[0] != int(indiv) or (Ya.ndim == 2 and Ya.shape[1] < 1):
+        raise ValueError(f"Y needs to be ({indiv},) or ({indiv}, n >= 1): {Ya.shape}")
+    Y2 = Ya.reshape(int(indiv), -1)
+    fits = [assoc_logistic_null(Y2[:, c], covariates) for c in range(Y2.shape[1])]
+    R = np.asfortranarray(np.stack([f.r for f in fits], axis=1))
+    Wt = np.asfortranarray(np.stack([f.w for f in fits], axis=1))
+    H = np.asfortranarray(np.concatenate([f.H for f in fits], axis=1))
+    res = assoc_set(plink, snps, indiv, R, Wt, H, sets, weights, want_phi=want_phi)
+    if Ya.ndim == 1:
+        return AssocSetResult(*(a.reshape(-1) for a in res[:9]), res.phi)
     return res

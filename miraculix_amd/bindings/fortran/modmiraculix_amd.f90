@@ -25,6 +25,7 @@ module modmiraculix_amd
  public :: mxa_assoc_score, mxa_assoc_logistic_null
  public :: mxa_assoc_score_spa
  public :: mxa_assoc_score_firth
+ public :: mxa_assoc_set, mxa_assoc_skat_pvalue
 
  interface
   subroutine c_setOptions_compressed(use_gpu, cores, floatLoop, meanSubstract, ignore_missings, do_not_center, do_normalize, use_miraculix_freq, variant, print_details) &
@@ -384,6 +385,26 @@ module modmiraculix_amd
    integer(c_int), value, intent(in) :: snps, indiv, n, kh, penalty, max_iter
    integer(c_long), value, intent(in) :: ldp, ldr, ldw, ldh, ldo
    real(c_double), value, intent(in) :: z_cutoff, tol
+   integer(c_int) :: rc
+  end function
+
+  ! set-based association (burden and SKAT): set_ptr (c_loc of nsets + 1 c_long), set_idx (c_loc of c_int, 0-based SNP indices) and set_wt (c_loc of doubles or
+  ! c_null_ptr) are a CSR list on the host; score, var, zstat and nobs are c_loc or c_null_ptr each; stat (required): nsets x 6 n doubles, ld lds; phi: c_loc
+  ! of n sum m_k^2 doubles or c_null_ptr
+  function mxa_assoc_set(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, nsets, set_ptr, set_idx, set_wt, score, var, zstat, ldo, nobs, stat, lds, phi) &
+           bind(C, name='mxa_assoc_set') result(rc)
+   import c_int, c_long, c_ptr
+   type(c_ptr), value, intent(in) :: plink, R, Wt, H, set_ptr, set_idx, set_wt, score, var, zstat, nobs, stat, phi
+   integer(c_int), value, intent(in) :: snps, indiv, n, kh, nsets
+   integer(c_long), value, intent(in) :: ldr, ldw, ldh, ldo, lds
+   integer(c_int) :: rc
+  end function
+
+  ! the SKAT p-values of count items from (Q, c1, c2, c4), on the host; df: c_loc of count doubles or c_null_ptr
+  function mxa_assoc_skat_pvalue(count, Q, c1, c2, c4, pval, df) bind(C, name='mxa_assoc_skat_pvalue') result(rc)
+   import c_int, c_long, c_ptr
+   integer(c_long), value, intent(in) :: count
+   type(c_ptr), value, intent(in) :: Q, c1, c2, c4, pval, df
    integer(c_int) :: rc
   end function
 

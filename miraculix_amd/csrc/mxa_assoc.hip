@@ -6,6 +6,7 @@
 // summed over the SNP's 11 fields (k_assoc_weights, dense); k_assoc_score_finish is its epilogue.  Its null model is host code: mxa_assoc_null_host.h.
 // mxa_assoc_score_spa is that scan followed by the saddlepoint correction of the SNPs with |z| >= z_cutoff: the k_assoc_spa* kernels.
 // mxa_assoc_score_firth is the same scan and the same stage with another solve: the (Firth-penalised) fit of the SNP's effect, k_assoc_firth*.
+// mxa_assoc_set is the same scan followed by the stage of another unit, mxa_assoc_set.hip, through assoc_score_then (mxa_assoc_stage.h).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "mxa_internal.h"
 #include "mxa_assoc_host.h"
 #include "mxa_assoc_null_host.h"
+#include "mxa_assoc_stage.h"
 #include "mxa_xprod.h"
 
 namespace mxa {
@@ -88,30 +90,7 @@ __global__ void __launch_bounds__(256) k_assoc_pack(const double *__restrict__ B
 // for every 01 field the individual's packed row of B is added to the thread's 16 accumulators, ascending individual.  Reduction: the wave's shuffles, then
 // (w0 + w1) + (w2 + w3) through the LDS: nothing in the order depends on the data or the launch.  A row without any 01 stores zeros without reducing (the
 // sum of zeros).  first != 0: this launch also stores the counts.  *flag is raised when a 01 was seen.
-struct AssocWord { unsigned long long lo, hi; };
-
-// Logical word w of a row: its bytes [16 w, 16 w + 16) below bps, the rest zero.  Only aligned 16-byte words that hold at least one byte of the row are
-// loaded: such a word lies in the page of that byte, so nothing unmapped is touched even where it reaches before the first row or behind the last one.
-__device__ __forceinline__ AssocWord assoc_load_word(const uint8_t *__restrict__ row, long w, long bps, int sh) {
-  const long b0 = 16 * w, nb = bps - b0;                          // nb >= 1 bytes of the row from b0 on
-  const uint4 *a = reinterpret_cast<const uint4 *>(row + b0 - sh);
-  const uint4 x = a[0];
-  uint4 y = make_uint4(0u, 0u, 0u, 0u);
-  if (sh && 16 - sh < nb) y = a[1];                               // the logical word reaches into the next aligned one
-  const unsigned long long q0 = (unsigned long long)x.x | ((unsigned long long)x.y << 32), q1 = (unsigned long long)x.z | ((unsigned long long)x.w << 32);
-  const unsigned long long q2 = (unsigned long long)y.x | ((unsigned long long)y.y << 32), q3 = (unsigned long long)y.z | ((unsigned long long)y.w << 32);
-  const bool big = sh >= 8;
-  const int s8 = 8 * (sh & 7);
-  const unsigned long long A = big ? q1 : q0, B = big ? q2 : q1, C = big ? q3 : q2;
-  AssocWord r;
-  r.lo = s8 ? (A >> s8) | (B << (64 - s8)) : A;
-  r.hi = s8 ? (B >> s8) | (C << (64 - s8)) : B;
-  if (nb < 16) {                                                  // the row ends inside this word: what follows belongs to the next row, or to nobody
-    if (nb <= 8) { r.hi = 0ull; if (nb < 8) r.lo &= (1ull << (8 * nb)) - 1ull; }
-    else r.hi &= (1ull << (8 * (nb - 8))) - 1ull;
-  }
-  return r;
-}
+// (AssocWord and assoc_load_word, the logical word of a row: mxa_assoc_stage.h)
 
 __device__ __forceinline__ void assoc_half(unsigned long long x, long fbase, long indiv, const AssocRow *__restrict__ bp, double (&acc)[kAssocCols], int &n01, int &n10,
                                            int &n11) {
@@ -1059,12 +1038,13 @@ int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int 
 // B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c.  spa: the stage of the saddlepoint correction or of the
 // fit follows the epilogue
 int assoc_score(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
-                double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const SpaArgs *spa = nullptr) {
+                double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const SpaArgs *spa = nullptr, const AssocAfterScan *after = nullptr) {
   const int ncols = n * (kh + 2);
-  AssocDriver d(!spa ? "mxa_assoc_score" : spa->firth() ? "mxa_assoc_score_firth" : "mxa_assoc_score_spa", snps, indiv, ncols, n, out_dev);
+  AssocDriver d(after ? after->who : !spa ? "mxa_assoc_score" : spa->firth() ? "mxa_assoc_score_firth" : "mxa_assoc_score_spa", snps, indiv, ncols, n, out_dev);
   double *const res[3] = {score, var, zstat};
   const size_t e_bytes = sizeof(double) * (size_t)snps * (size_t)n;
   size_t extra = e_bytes;
+  if (after) extra += after->extra_bytes + (score ? 0 : e_bytes);
   if (spa) {
     int p_dev = -1;
     const int dev = select_device();
@@ -1082,6 +1062,7 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
     if (spa->firth() && !d.out_d[1]) { if (bV.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[1] = (double *)bV.p; }
     if (!d.out_d[2]) { if (bZ.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[2] = (double *)bZ.p; }
   }
+  if (after && !d.out_d[0]) { if (bU.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[0] = (double *)bU.p; }   // a stage reads U on the device
   double *dE = (double *)bE.p;
   const size_t col = sizeof(double) * (size_t)indiv;
   double *dW = d.dB + (size_t)n * (size_t)indiv;
@@ -1110,10 +1091,19 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
   });
   MXA_HIP(hipGetLastError());
   if (spa && spa_stage(d, plink, *spa, kh, d.out_d[0], d.out_d[1], d.out_d[2], ldu, ldo)) return 1;
+  if (after) {
+    const AssocScanView v = {snps, indiv, bps, n, kh, d.in_place, out_dev, s, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD, d.dM, dW, d.out_d[0], ldu};
+    if (after->run(after->self, v, plink)) return 1;
+  }
   return d.copy_out(res, ldo, nobs);
 }
 
 }  // namespace
+
+int assoc_score_then(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
+                     double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const AssocAfterScan &after) {
+  return assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, out_dev, nullptr, &after);
+}
 
 }  // namespace mxa
 

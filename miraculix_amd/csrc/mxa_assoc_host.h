@@ -77,7 +77,7 @@ inline const char *assoc_linear_args(const void *plink, long snps, long indiv, c
 
 // The same for mxa_assoc_score: B = [R | Wt | H] has n (kh + 2) columns.
 inline const char *assoc_score_args(const void *plink, long snps, long indiv, const void *R, long ldr, const void *Wt, long ldw, const void *H, long ldh, int n, int kh,
-                                    const void *score, const void *var, const void *zstat, long ldo) {
+                                    const void *score, const void *var, const void *zstat, long ldo, bool need_result = true) {
   if (!plink || !R || !Wt) return "plink, R and Wt must not be NULL";
   if (snps < 1 || indiv < 1 || n < 1) return "snps, indiv and n must be positive";
   if (kh < 0) return "kh must not be negative";
@@ -85,7 +85,7 @@ inline const char *assoc_score_args(const void *plink, long snps, long indiv, co
   if ((long)n * ((long)kh + 2) > 65535) return "n (kh + 2) must be at most 65535";
   if (ldr < indiv || ldw < indiv || (kh > 0 && ldh < indiv)) return "ldr, ldw and ldh must be at least indiv";
   if (indiv > kAssocMaxIndiv) return "indiv > 47 453 132 (4 indiv^2 >= 2^53)";
-  if (!score && !var && !zstat) return "score, var and zstat are all NULL";
+  if (need_result && !score && !var && !zstat) return "score, var and zstat are all NULL";   // (mxa_assoc_set: its set results are the point)
   if (ldo < snps) return "ldo must be at least snps";
   return nullptr;
 }

@@ -163,6 +163,12 @@ def load_shared_library():
                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]
     L.mxa_assoc_score_firth.restype = ctypes.c_int
+    L.mxa_assoc_set.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
+    L.mxa_assoc_set.restype = ctypes.c_int
+    L.mxa_assoc_skat_pvalue.argtypes = [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.mxa_assoc_skat_pvalue.restype = ctypes.c_int
     L.mxa_last_error.restype = ctypes.c_int
     L.mxa_last_error_string.restype = ctypes.c_char_p
     L.mxa_device_count.restype = ctypes.c_int

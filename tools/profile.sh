@@ -28,6 +28,8 @@
 #   assoc-spa-kernels [snps indiv]   the library kernels inside mxa_assoc_score_spa, one by one: tools/perf_assoc_spa.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   assoc-firth [snps indiv reps]   the score test with effect sizes (mxa_assoc_score_firth, penalty 0 and 1) at n = 1, q = 3, 5.5 % cases, z_cutoff = 1.96, beside mxa_assoc_score and mxa_assoc_score_spa on the same operands, one process, alternating calls
 #   assoc-firth-kernels [snps indiv]   the library kernels inside mxa_assoc_score_spa and mxa_assoc_score_firth, one by one, with the time per item and per (item, evaluation) of k_assoc_spa and k_assoc_firth: tools/perf_assoc_firth.py ... trace under rocprofv3 --kernel-trace, in a run of its own
+#   assoc-set [snps indiv reps]   the set tests (mxa_assoc_set) with sets of 32, 8 and 256 neighbouring SNPs at n = 1, q = 3, beside mxa_assoc_score on the same operands and beside the torch route (decode to fp64 + bmm), one process, alternating calls
+#   assoc-set-kernels [snps indiv]   the library kernels inside mxa_assoc_set, one by one: tools/perf_assoc_set.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -180,6 +182,16 @@ assoc-firth-kernels)
   ( cd /tmp && timeout -k 10 800 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc_firth.py" ${1:-50000} ${2:-1000000} trace > "$O/assoc_firth_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_firth_trace_run.log"; exit 1; }
   f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc_firth.py summarize "$f" "$O/assoc_firth_trace_run.log" 2>&1 | tee "$O/assoc_firth_kernels.txt" || exit 1
   rm -rf "$D"; cp -f "$O/assoc_firth_kernels.txt" "$R/profiles/r18_assoc_firth_kernels.txt" ;;
+assoc-set)
+  # whole-call times of the entry beside mxa_assoc_score of the same run, alternating calls, and the torch route; the text is what profiles/r19_assoc_set.txt holds
+  timeout -k 10 900 python3 tools/perf_assoc_set.py ${1:-50000} ${2:-1000000} ${3:-7} 2>&1 | tee "$O/assoc_set.txt" || exit 1
+  cp -f "$O/assoc_set.txt" "$R/profiles/r19_assoc_set.txt" ;;
+assoc-set-kernels)
+  # per-kernel times of the second call at each set size; the text is what profiles/r19_assoc_set_kernels.txt holds
+  D="$O/assoc_set_trace"; rm -rf "$D"; mkdir -p "$D"
+  ( cd /tmp && timeout -k 10 800 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc_set.py" ${1:-50000} ${2:-1000000} trace > "$O/assoc_set_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_set_trace_run.log"; exit 1; }
+  f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc_set.py summarize "$f" 2>&1 | tee "$O/assoc_set_kernels.txt" || exit 1
+  rm -rf "$D"; cp -f "$O/assoc_set_kernels.txt" "$R/profiles/r19_assoc_set_kernels.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

@@ -4,9 +4,8 @@
 // M_b = the sum of b over the SNP's missing individuals.  k_assoc_finish turns D, M and the counts into beta, se and t in the documented operation order.
 // The score test for binary traits (mxa_assoc_score) is the same scan with B = [R | Wt | H] and one more sum per weight column, E = the weights
 // summed over the SNP's 11 fields (k_assoc_weights, dense); k_assoc_score_finish is its epilogue.  Its null model is host code: mxa_assoc_null_host.h.
-// mxa_assoc_score_spa is that scan followed by the saddlepoint correction of the SNPs with |z| >= z_cutoff: the k_assoc_spa* kernels.
-// mxa_assoc_score_firth is the same scan and the same stage with another solve: the (Firth-penalised) fit of the SNP's effect, k_assoc_firth*.
-// mxa_assoc_set is the same scan followed by the stage of another unit, mxa_assoc_set.hip, through assoc_score_then (mxa_assoc_stage.h).
+// A stage of another unit may follow that epilogue on the scan's stream and buffers, through assoc_score_then (mxa_assoc_stage.h): the saddlepoint correction
+// and the fit of the effect sizes in mxa_assoc_spa.hip, the set tests in mxa_assoc_set.hip.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -24,30 +23,19 @@ namespace {
 
 struct alignas(8 * kAssocCols) AssocRow { double v[kAssocCols]; };   // one individual's 16 columns of B: one aligned 128-byte run
 
-// ---- the sums of the phenotype preparation: 256 threads, thread t takes the individuals t, t + 256, ... in ascending order, then a fixed tree -- the wave's
-// shuffles (32, 16, ..., 1), then (w0 + w1) + (w2 + w3) through the LDS.  The order depends on indiv alone.
-__device__ __forceinline__ double assoc_block_sum(double v, double *red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  const double r = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return r;
-}
-
+// ---- the sums of the phenotype preparation: 256 threads, thread t takes the individuals t, t + 256, ... in ascending order, then the fixed tree of
+// assoc_block_sums (mxa_assoc_stage.h).  The order depends on indiv alone.
 // out[x + y ld_out] = sum_i A[i, a] B[i, y] with a = x (diag == 0) or a = y (diag != 0: the squared norms, launched with gridDim.x == 1); A == nullptr: the
 // column sums of B.  One workgroup per output.
 __global__ void __launch_bounds__(256) k_assoc_dots(const double *__restrict__ A, long lda, const double *__restrict__ B, long ldb, long indiv,
                                                      double *__restrict__ out, int ld_out, int diag) {
-  __shared__ double red[4];
+  __shared__ double red[1][4];
   const double *b = B + (size_t)blockIdx.y * (size_t)ldb;
   const double *a = A ? A + (size_t)(diag ? blockIdx.y : blockIdx.x) * (size_t)lda : nullptr;
-  double acc = 0.0;
-  for (long i = threadIdx.x; i < indiv; i += 256) acc = a ? __fma_rn(a[i], b[i], acc) : acc + b[i];
-  const double s = assoc_block_sum(acc, red);
-  if (threadIdx.x == 0) out[(size_t)blockIdx.x + (size_t)blockIdx.y * (size_t)ld_out] = s;
+  double acc[1] = {0.0};
+  for (long i = threadIdx.x; i < indiv; i += 256) acc[0] = a ? __fma_rn(a[i], b[i], acc[0]) : acc[0] + b[i];
+  assoc_block_sums<1>(acc, red);
+  if (threadIdx.x == 0) out[(size_t)blockIdx.x + (size_t)blockIdx.y * (size_t)ld_out] = acc[0];
 }
 
 // y[i, c] -= sum[c] / indiv
@@ -296,417 +284,6 @@ __global__ void __launch_bounds__(256) k_assoc_score_finish(long snps, int n, in
   if (zstat) zstat[o] = __ddiv_rn(U, __dsqrt_rn(sxx));
 }
 
-// ---- the saddlepoint correction of the score test (mxa_assoc_score_spa).  After k_assoc_score_finish: k_assoc_spa_classify writes the normal
-// p-value and the flag 0 / 3 of every (SNP, trait) and marks with 1 what is to be corrected; k_assoc_spa_list compacts the marked SNPs in ascending order (one
-// workgroup, prefix sums: no atomics, so the list is the same in every run) and k_assoc_spa_items names their (SNP, trait) items.  Then per batch of marked
-// SNPs: k_assoc_spa_form writes the adjusted genotype g of every item, k_assoc_spa solves both sides of every item, k_assoc_spa_combine writes p and the flag.
-constexpr int kSpaTile = 8;                                     // marked SNPs one workgroup of k_assoc_spa_form decodes for its 256 individuals
-constexpr int kSpaOutside = 0, kSpaFailed = 1, kSpaSolved = 2;  // what a side ends as
-struct SpaSide { double tail; int status; int evals; };
-
-// tau_{c,j,i} = h_{c,j,i} / w_{c,i}, once per call; blockIdx.y = c kh + j
-__global__ void __launch_bounds__(256) k_assoc_spa_tau(const double *__restrict__ H, const double *__restrict__ W, long indiv, int kh, double *__restrict__ Ht) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= indiv) return;
-  const size_t at = (size_t)blockIdx.y * (size_t)indiv + (size_t)i;
-  Ht[at] = __ddiv_rn(H[at], W[(size_t)(blockIdx.y / (unsigned)kh) * (size_t)indiv + (size_t)i]);
-}
-
-// one thread per (SNP, trait): flag 3 and NaN where z is not finite, else the normal p-value erfc(|z| sqrt(1/2)) and the flag 0, or the mark 1 where |z| >=
-// z_cutoff (the normal p-value stays where the correction ends with the flag 2).  pval and flag: snps x n, ld snps.
-__global__ void __launch_bounds__(256) k_assoc_spa_classify(long snps, int n, const double *__restrict__ zstat, long ldz, double z_cutoff, double *__restrict__ pval,
-                                                             int *__restrict__ flag, long blk0) {
-  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (idx >= snps * (long)n) return;
-  const long s = idx % snps;
-  const double z = zstat[(size_t)s + (size_t)(idx / snps) * (size_t)ldz];
-  if (!isfinite(z)) { flag[idx] = 3; pval[idx] = __longlong_as_double(0x7ff8000000000000ll); return; }
-  const double az = fabs(z);
-  flag[idx] = az < z_cutoff ? 0 : 1;
-  pval[idx] = erfc(__dmul_rn(az, 0.70710678118654752440));
-}
-
-// exclusive prefix sum over the workgroup's 256 threads through the LDS; *total = the sum of all
-__device__ __forceinline__ long spa_block_scan(long v, long *sh, long *total) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    const long add = t >= off ? sh[t - off] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  const long incl = sh[t];
-  *total = sh[255];
-  __syncthreads();
-  return incl - v;
-}
-
-// ONE workgroup: list[k] = the k-th SNP with a marked trait, ascending; off[k] = the index of its first item (its marked traits, ascending, follow one
-// another); off[count[0]] = count[1] = the number of items, count[0] = the number of marked SNPs
-__global__ void __launch_bounds__(256) k_assoc_spa_list(long snps, int n, const int *__restrict__ flag, int *__restrict__ list, long *__restrict__ off,
-                                                         long *__restrict__ count) {
-  __shared__ long sh[256];
-  long base_k = 0, base_item = 0;
-  for (long s0 = 0; s0 < snps; s0 += 256) {
-    const long s = s0 + threadIdx.x;
-    long cnt = 0;
-    if (s < snps)
-      for (int c = 0; c < n; c++) cnt += flag[(size_t)s + (size_t)c * (size_t)snps] == 1;
-    long tot_k = 0, tot_item = 0;
-    const long k = base_k + spa_block_scan(cnt > 0, sh, &tot_k);
-    const long item = base_item + spa_block_scan(cnt, sh, &tot_item);
-    if (cnt > 0) { list[k] = (int)s; off[k] = item; }
-    base_k += tot_k;
-    base_item += tot_item;
-  }
-  if (threadIdx.x == 0) { off[base_k] = base_item; count[0] = base_k; count[1] = base_item; }
-}
-
-// one thread per marked SNP: the SNP and the trait of each of its items
-__global__ void __launch_bounds__(256) k_assoc_spa_items(long nk, long snps, int n, const int *__restrict__ flag, const int *__restrict__ list, const long *__restrict__ off,
-                                                          int *__restrict__ item_s, int *__restrict__ item_c, long blk0) {
-  const long k = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (k >= nk) return;
-  const long s = list[k];
-  long at = off[k];
-  for (int c = 0; c < n; c++)
-    if (flag[(size_t)s + (size_t)c * (size_t)snps] == 1) { item_s[at] = (int)s; item_c[at] = c; at++; }
-}
-
-// (a) g of the items of the marked SNPs [k0, k1): workgroup (tile, ib) = divmod(blk0 + blockIdx.x, iblocks) takes the individuals 256 ib + t of the kSpaTile
-// marked SNPs from k0 + kSpaTile tile on.  Every thread decodes its field of each of these rows once (00 -> 0, 01 -> mu, 10 -> 1, 11 -> 2; mu = Sz / N as in
-// k_assoc_score_finish), then per trait c with an item in the tile reads tau_{c,j,i} once per j and applies it to all of the tile's SNPs with that item:
-// g = x, then g = fma(-a_j, tau_j, g) over ascending j with a_j = fma(mu, M_hj, D_hj) (the workgroup's own loads of M and D are uniform).  rows: the raw
-// matrix (compact == 0: row list[k]) or the bounce buffer of the batch (compact != 0: row k - k0).  G: item off[k0] is its first row of indiv doubles.
-__global__ void __launch_bounds__(256) k_assoc_spa_form(const uint8_t *__restrict__ rows, long bps, int compact, long indiv, long snps, int n, int kh,
-                                                         const int *__restrict__ list, const long *__restrict__ off, long k0, long k1, const int *__restrict__ flag,
-                                                         const int *__restrict__ nobs, const int *__restrict__ c1, const int *__restrict__ c2,
-                                                         const double *__restrict__ D, const double *__restrict__ M, const double *__restrict__ Ht,
-                                                         double *__restrict__ G, long iblocks, long blk0) {
-  const long b = blk0 + blockIdx.x;
-  const long kt = k0 + (b / iblocks) * kSpaTile;
-  const long i = (b % iblocks) * 256 + threadIdx.x;
-  const bool live = i < indiv;
-  const long item_base = off[k0];
-  double x[kSpaTile], mu[kSpaTile];
-  long s[kSpaTile], item[kSpaTile];
-#pragma unroll
-  for (int u = 0; u < kSpaTile; u++) {
-    x[u] = 0.0; mu[u] = 0.0; s[u] = -1; item[u] = 0;
-    const long k = kt + u;
-    if (k < k1) {
-      s[u] = list[k];
-      item[u] = off[k] - item_base;
-      mu[u] = __ddiv_rn((double)((long)c1[s[u]] + 2 * (long)c2[s[u]]), (double)nobs[s[u]]);
-      if (live) {
-        const uint8_t *row = rows + (size_t)(compact ? k - k0 : s[u]) * (size_t)bps;
-        const int code = (row[i >> 2] >> (2 * (int)(i & 3))) & 3;
-        x[u] = code == 0 ? 0.0 : code == 1 ? mu[u] : code == 2 ? 1.0 : 2.0;
-      }
-    }
-  }
-  for (int c = 0; c < n; c++) {
-    bool on[kSpaTile];
-    bool any = false;
-#pragma unroll
-    for (int u = 0; u < kSpaTile; u++) { on[u] = s[u] >= 0 && flag[(size_t)s[u] + (size_t)c * (size_t)snps] == 1; any = any || on[u]; }
-    if (!any) continue;
-    double g[kSpaTile];
-#pragma unroll
-    for (int u = 0; u < kSpaTile; u++) g[u] = x[u];
-    for (int j = 0; j < kh; j++) {
-      const size_t col = (size_t)c * (size_t)kh + (size_t)j;
-      const double tau = live ? Ht[col * (size_t)indiv + (size_t)i] : 0.0;
-#pragma unroll
-      for (int u = 0; u < kSpaTile; u++)
-        if (on[u]) {
-          const size_t ah = (size_t)s[u] + ((size_t)2 * (size_t)n + col) * (size_t)snps;
-          const double a = __fma_rn(mu[u], M[ah], D[ah]);
-          g[u] = __fma_rn(-a, tau, g[u]);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < kSpaTile; u++)
-      if (on[u]) {
-        if (live) G[(size_t)item[u] * (size_t)indiv + (size_t)i] = g[u];
-        item[u]++;
-      }
-  }
-}
-
-// K sums of a workgroup at once, in the order of assoc_block_sum: every thread returns with the K totals
-template <int K>
-__device__ __forceinline__ void spa_block_sums(double (&v)[K], double (*red)[4]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < K; q++) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
-    if (lane == 0) red[q][wave] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < K; q++) v[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-  __syncthreads();
-}
-
-// (b) one workgroup per (item, side): item = blk0 + blockIdx.x >> 1 of the batch (row `item` of G), side 0: sigma = +1, side 1: sigma = -1.  Thread t takes the
-// individuals t, t + 256, ... in ascending order; every sum ends in spa_block_sums, so its order depends on indiv alone.  First c0, A, G+ and G-, then Newton
-// from t = 0 with its bracket, entirely in the kernel: an evaluation reads g and p once and sums K' and K'' (the accepted t^: K and K''), thread 0 updates t,
-// the bracket and the state and broadcasts both through the LDS.  The header of mxa_assoc_score_spa has the rules.
-__global__ void __launch_bounds__(256) k_assoc_spa(const double *__restrict__ G, long indiv, const double *__restrict__ P, const int *__restrict__ item_s,
-                                                    const int *__restrict__ item_c, long item_base, long nitems, const double *__restrict__ score, long ldu, double tol,
-                                                    int max_iter, SpaSide *__restrict__ out, long blk0) {
-  __shared__ double red[4][4];
-  __shared__ double sh_t;
-  __shared__ int sh_state;                      // 0: a Newton evaluation is next, 1: the evaluation at the accepted t^ is next, 2: done
-  const long w = blk0 + blockIdx.x;
-  const long item = w >> 1;
-  if (item >= nitems) return;
-  const double sigma = (w & 1) ? -1.0 : 1.0;
-  const double *g = G + (size_t)item * (size_t)indiv;
-  const long s = item_s[item_base + item];
-  const int c = item_c[item_base + item];
-  const double *p = P + (size_t)c * (size_t)indiv;
-  double v4[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long i = threadIdx.x; i < indiv; i += 256) {
-    const double gi = g[i];
-    v4[0] = __fma_rn(gi, p[i], v4[0]);
-    v4[1] += fabs(gi);
-    v4[2] += fmax(gi, 0.0);
-    v4[3] += fmin(gi, 0.0);
-  }
-  spa_block_sums<4>(v4, red);
-  const double c0 = v4[0], A = v4[1];
-  const double q = sigma * fabs(score[(size_t)s + (size_t)c * (size_t)ldu]);
-  const double margin = sigma * (((w & 1) ? v4[3] : v4[2]) - c0 - q);
-  if (threadIdx.x == 0) {
-    sh_t = 0.0;
-    sh_state = 0;
-    if (margin <= 0x1p-30 * A) { out[w].tail = 0.0; out[w].status = kSpaOutside; out[w].evals = 0; sh_state = 2; }
-  }
-  __syncthreads();
-  int state = __builtin_amdgcn_readfirstlane(sh_state);
-  double t = sh_t, lo = -INFINITY, hi = INFINITY;
-  int evals = 0;
-  while (state != 2) {
-    double v3[3] = {0.0, 0.0, 0.0};            // K (state 1 only), K' (state 0 only), K''
-    for (long i = threadIdx.x; i < indiv; i += 256) {
-      const double gi = g[i], pi = p[i];
-      const double x = t * gi;
-      const double e = exp(-fabs(x));
-      const bool pos = x >= 0.0;
-      const double al = pos ? pi : 1.0 - pi, be = pos ? 1.0 - pi : pi;
-      const double d = al + be * e, r = 1.0 / d;  // one division a term: K' and K'' take the reciprocal
-      if (state == 1) v3[0] += fmax(x, 0.0) + log(d);
-      else v3[1] += gi * ((pos ? pi : pi * e) * r);
-      v3[2] += (gi * r) * (gi * r) * (al * be * e);
-    }
-    spa_block_sums<3>(v3, red);
-    if (threadIdx.x == 0) {
-      int status = -1;                           // -1: go on
-      double tail = 0.0;
-      if (state == 1) {
-        const double K = v3[0] - t * c0;
-        const double r = sqrt(2.0 * (t * q - K));
-        const double ws = t > 0.0 ? r : t < 0.0 ? -r : 0.0;
-        const double vs = t * sqrt(v3[2]);
-        const double zeta = ws + log(vs / ws) / ws;
-        status = isfinite(zeta) ? kSpaSolved : kSpaFailed;
-        if (status == kSpaSolved) tail = 0.5 * erfc(sigma * zeta * 0.70710678118654752440);
-      } else {
-        evals++;
-        const double f = (v3[1] - c0) - q;
-        if (f < 0.0) lo = t; else hi = t;
-        double tn = t - f / v3[2];
-        if (!isfinite(tn)) status = kSpaFailed;
-        else if (fabs(tn - t) <= tol * fabs(tn)) { sh_t = tn; sh_state = 1; }
-        else {
-          if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
-          if (!isfinite(tn) || evals >= max_iter) status = kSpaFailed;
-          else sh_t = tn;
-        }
-      }
-      if (status >= 0) { out[w].tail = tail; out[w].status = status; out[w].evals = evals; sh_state = 2; }
-    }
-    __syncthreads();
-    state = __builtin_amdgcn_readfirstlane(sh_state);
-    t = sh_t;
-  }
-}
-
-// one thread per item of the batch: the two sides combined.  The normal p-value that k_assoc_spa_classify left stays with the flag 2.
-__global__ void __launch_bounds__(256) k_assoc_spa_combine(long nitems, long item_base, const int *__restrict__ item_s, const int *__restrict__ item_c,
-                                                            const double *__restrict__ score, long ldu, const SpaSide *__restrict__ side, long snps,
-                                                            double *__restrict__ pval, int *__restrict__ flag, long blk0) {
-  const long item = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (item >= nitems) return;
-  const long s = item_s[item_base + item];
-  const int c = item_c[item_base + item];
-  const int obs = score[(size_t)s + (size_t)c * (size_t)ldu] >= 0.0 ? 0 : 1;
-  const SpaSide a = side[2 * item + obs], b = side[2 * item + (1 - obs)];
-  const size_t o = (size_t)s + (size_t)c * (size_t)snps;
-  if (a.status != kSpaSolved || b.status == kSpaFailed) { flag[o] = 2; return; }
-  flag[o] = 1;
-  pval[o] = a.tail + (b.status == kSpaSolved ? b.tail : 0.0);
-}
-
-// ---- the effect sizes of the score test (mxa_assoc_score_firth): the stage of the saddlepoint correction with its own classify epilogue, solve
-// and combine.  k_assoc_firth_classify writes the one-step values and the flag 0 / 3 of every (SNP, trait) and marks with 1 what is to be fitted (the one-step
-// values stay where the fit ends with the flag 2); beta, se, chisq, pval and flag: snps x n, ld snps.
-struct FirthFit { double beta, K, k2, k20; int status, evals; };   // beta^, K(beta^), K''(beta^), K''(0)
-
-__global__ void __launch_bounds__(256) k_assoc_firth_classify(long snps, int n, const double *__restrict__ score, const double *__restrict__ var,
-                                                               const double *__restrict__ zstat, long ldu, double z_cutoff, double *__restrict__ beta,
-                                                               double *__restrict__ se, double *__restrict__ chisq, double *__restrict__ pval, int *__restrict__ flag,
-                                                               long blk0) {
-  const long idx = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (idx >= snps * (long)n) return;
-  const size_t at = (size_t)(idx % snps) + (size_t)(idx / snps) * (size_t)ldu;
-  const double z = zstat[at];
-  if (!isfinite(z)) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    flag[idx] = 3; beta[idx] = nan; se[idx] = nan; chisq[idx] = nan; pval[idx] = nan;
-    return;
-  }
-  const double az = fabs(z), V = var[at];
-  flag[idx] = az < z_cutoff ? 0 : 1;
-  beta[idx] = __ddiv_rn(score[at], V);
-  se[idx] = __ddiv_rn(1.0, __dsqrt_rn(V));
-  chisq[idx] = __dmul_rn(z, z);
-  pval[idx] = erfc(__dmul_rn(az, 0.70710678118654752440));
-}
-
-// one workgroup per item: row `item` = blk0 + blockIdx.x of G, one solve.  Thread t takes the individuals t, t + 256, ... in ascending order; every sum ends in
-// spa_block_sums, so its order depends on indiv alone.  First c0, A, G+ and G- (penalty == 0: the support test of the observed side), then Newton from beta = 0
-// with its bracket, entirely in the kernel: an evaluation reads g and p once and sums K1, K2 and, with the penalty, K3 and K4 (the derivatives of K) -- one exp
-// and one division a term, the two further sums are FMA chains on g r and omega; the evaluation at the accepted beta^ sums K and K2.  Thread 0 updates beta, the
-// bracket and the state and broadcasts both through the LDS.  penalty is uniform over the launch.  The header of mxa_assoc_score_firth has the rules.
-__global__ void __launch_bounds__(256) k_assoc_firth(const double *__restrict__ G, long indiv, const double *__restrict__ P, const int *__restrict__ item_s,
-                                                      const int *__restrict__ item_c, long item_base, long nitems, const double *__restrict__ score, long ldu,
-                                                      int penalty, double tol, int max_iter, FirthFit *__restrict__ out, long blk0) {
-  __shared__ double red[4][4];
-  __shared__ double sh_b;
-  __shared__ int sh_state;                      // 0: a Newton evaluation is next, 1: the evaluation at the accepted beta^ is next, 2: done
-  const long item = blk0 + blockIdx.x;
-  if (item >= nitems) return;
-  const double *g = G + (size_t)item * (size_t)indiv;
-  const long s = item_s[item_base + item];
-  const int c = item_c[item_base + item];
-  const double *p = P + (size_t)c * (size_t)indiv;
-  double v4[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long i = threadIdx.x; i < indiv; i += 256) {
-    const double gi = g[i];
-    v4[0] = __fma_rn(gi, p[i], v4[0]);
-    v4[1] += fabs(gi);
-    v4[2] += fmax(gi, 0.0);
-    v4[3] += fmin(gi, 0.0);
-  }
-  spa_block_sums<4>(v4, red);
-  const double c0 = v4[0], A = v4[1];
-  const double U = score[(size_t)s + (size_t)c * (size_t)ldu];
-  if (threadIdx.x == 0) {
-    sh_b = 0.0;
-    sh_state = 0;
-    const double margin = U >= 0.0 ? (v4[2] - c0) - U : -((v4[3] - c0) - U);
-    if (penalty == 0 && margin <= 0x1p-30 * A) {   // the statistic lies on the edge of its support: the unpenalised likelihood has no maximum
-      out[item].beta = 0.0; out[item].K = 0.0; out[item].k2 = 0.0; out[item].k20 = 0.0; out[item].status = kSpaOutside; out[item].evals = 0;
-      sh_state = 2;
-    }
-  }
-  __syncthreads();
-  int state = __builtin_amdgcn_readfirstlane(sh_state);
-  double b = sh_b, lo = -INFINITY, hi = INFINITY, k20 = 0.0;
-  int evals = 0;
-  while (state != 2) {
-    double v2[2] = {0.0, 0.0}, w2[2] = {0.0, 0.0};   // K (state 1) or K1 (state 0), K2; K3, K4 (state 0 with the penalty)
-    for (long i = threadIdx.x; i < indiv; i += 256) {
-      const double gi = g[i], pi = p[i];
-      const double x = b * gi;
-      const double e = exp(-fabs(x));
-      const bool pos = x >= 0.0;
-      const double al = pos ? pi : 1.0 - pi, be = pos ? 1.0 - pi : pi;
-      const double d = al + be * e, r = 1.0 / d;  // one division a term
-      const double gr = gi * r, abe = al * be * e, t2 = gr * gr * abe;   // t2 = g^2 omega
-      if (state == 1) v2[0] += fmax(x, 0.0) + log(d);
-      else {
-        const double pr = (pos ? pi : pi * e) * r;
-        v2[0] += gi * pr;
-        if (penalty) {
-          const double t3 = t2 * gi;
-          w2[0] = fma(t3, 1.0 - 2.0 * pr, w2[0]);
-          w2[1] = fma(t3 * gi, 1.0 - 6.0 * (abe * r * r), w2[1]);
-        }
-      }
-      v2[1] += t2;
-    }
-    spa_block_sums<2>(v2, red);
-    if (penalty && state == 0) spa_block_sums<2>(w2, red);
-    if (threadIdx.x == 0) {
-      int status = -1;                           // -1: go on
-      double K = 0.0;
-      if (state == 1) {
-        K = v2[0] - b * c0;
-        status = kSpaSolved;
-      } else {
-        evals++;
-        const double K2 = v2[1];
-        if (evals == 1) k20 = K2;
-        double f = (v2[0] - c0) - U, fp = K2;
-        if (penalty) {
-          const double r3 = w2[0] / K2;
-          f -= 0.5 * r3;
-          const double alt = K2 - 0.5 * (w2[1] / K2 - r3 * r3);
-          if (alt > 0.0) fp = alt;
-        }
-        if (f < 0.0) lo = b; else hi = b;
-        double bn = b - f / fp;
-        if (!isfinite(bn)) status = kSpaFailed;
-        else if (fabs(bn - b) <= tol * fabs(bn)) { sh_b = bn; sh_state = 1; }
-        else {
-          if (!(bn > lo && bn < hi)) bn = 0.5 * (lo + hi);
-          if (!isfinite(bn) || evals >= max_iter) status = kSpaFailed;
-          else sh_b = bn;
-        }
-      }
-      if (status >= 0) {
-        out[item].beta = b; out[item].K = K; out[item].k2 = v2[1]; out[item].k20 = k20; out[item].status = status; out[item].evals = evals;
-        sh_state = 2;
-      }
-    }
-    __syncthreads();
-    state = __builtin_amdgcn_readfirstlane(sh_state);
-    b = sh_b;
-  }
-}
-
-// one thread per item of the batch: the results of a converged fit.  The one-step values that k_assoc_firth_classify left stay with the flag 2.
-__global__ void __launch_bounds__(256) k_assoc_firth_combine(long nitems, long item_base, const int *__restrict__ item_s, const int *__restrict__ item_c,
-                                                              const double *__restrict__ score, long ldu, const FirthFit *__restrict__ fit, int penalty, long snps,
-                                                              double *__restrict__ beta, double *__restrict__ se, double *__restrict__ chisq,
-                                                              double *__restrict__ pval, int *__restrict__ flag, long blk0) {
-  const long item = (blk0 + blockIdx.x) * 256 + threadIdx.x;
-  if (item >= nitems) return;
-  const long s = item_s[item_base + item];
-  const int c = item_c[item_base + item];
-  const size_t o = (size_t)s + (size_t)c * (size_t)snps;
-  const FirthFit a = fit[item];
-  flag[o] = 2;
-  if (a.status != kSpaSolved) return;
-  const double e = __ddiv_rn(1.0, __dsqrt_rn(a.k2));
-  double x2 = 2.0 * (a.beta * score[(size_t)s + (size_t)c * (size_t)ldu] - a.K);
-  if (penalty) x2 += log(a.k2 / a.k20);
-  if (!isfinite(e) || !isfinite(x2)) return;
-  x2 = fmax(x2, 0.0);
-  flag[o] = 1;
-  beta[o] = a.beta;
-  se[o] = e;
-  chisq[o] = x2;
-  pval[o] = erfc(sqrt(0.5 * x2));
-}
-
 // ---- host side
 struct HandleHolder {                // the one-shot object is released on every exit path
   Handle *h = nullptr;
@@ -777,8 +354,7 @@ struct AssocDriver {
     ncc = (ncols + kAssocCols - 1) / kAssocCols;
     max_n = std::min(ncols, 32);
     bps = (indiv + 3) / 4;
-    int p_dev = -1;
-    in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;   // rows in this device's memory are scanned where they lie
+    in_place = assoc_rows_in_place(plink, dev);   // rows in this device's memory are scanned where they lie
     chunk_rows = in_place ? snps : assoc_chunk_rows(snps, bps);
     // ---- memory pre-flight: the packed object, the staging chunk, B and its row-packed copy, D and M, the counts, the device copies of host results
     b_bytes = sizeof(double) * (size_t)indiv * (size_t)ncols;
@@ -897,179 +473,34 @@ int assoc_linear(const unsigned char *plink, long snps, long indiv, const double
   return 0;
 }
 
-// ---- the stage of mxa_assoc_score_spa and mxa_assoc_score_firth after the scan: what the entries take beyond mxa_assoc_score's arguments.  penalty < 0: the
-// saddlepoint correction (pval required); penalty 0 / 1: the fit (beta required; se, chisq and pval optional)
-struct SpaArgs {
-  const double *P;
-  long ldp;
-  double z_cutoff, tol;
-  int max_iter;
-  double *pval;
-  int *flag;
-  int penalty = -1;
-  double *beta = nullptr, *se = nullptr, *chisq = nullptr;
-  bool firth() const { return penalty >= 0; }
-};
-
-// the items one batch may hold: MXA_ASSOC_SPA_ITEMS (read per call, for tests), else what fits 4 GiB of g (512 items, 1024 workgroups of k_assoc_spa, at a
-// million individuals) -- the fit: 8 GiB, since k_assoc_firth has one workgroup an item and 512 of them leave half of the device's workgroup slots empty, cut
-// down to a multiple of the kFirthResident workgroups the device holds at once, so that no launch ends in a second round of a few (measured);
-// at least the n items of one SNP
-constexpr long kFirthResident = 1024;   // 256 CUs x 4 workgroups of 4 waves at 114 VGPRs
-long spa_batch_items(long indiv, int n, bool firth) {
-  long items = (long)(((size_t)(firth ? 8 : 4) << 30) / (sizeof(double) * (size_t)indiv));
-  if (firth && items > kFirthResident) items -= items % kFirthResident;
-  const char *e = getenv("MXA_ASSOC_SPA_ITEMS");
-  if (e && atol(e) > 0) items = atol(e);
-  return std::max<long>(n, items);
-}
-// the marked SNPs of one batch: MXA_ASSOC_SPA_BATCH, else unlimited for rows read in place and what fits a bounce buffer of 256 MiB for a host matrix
-long spa_batch_rows(long snps, long bps, bool in_place) {
-  long rows = in_place ? snps : std::max<long>(1, (long)(((size_t)256 << 20) / (size_t)bps));
-  const char *e = getenv("MXA_ASSOC_SPA_BATCH");
-  if (e && atol(e) > 0) rows = atol(e);
-  return std::min(rows, snps);
-}
-// device memory of the stage at its largest (every trait of every SNP marked): the pre-flight's share
-// (own: the snps x n arrays U, V, z that the stage allocates for itself; firth: beta, se and chisq beside pval, one FirthFit an item)
-size_t spa_bytes(long snps, long indiv, int n, int kh, long bps, bool in_place, int own, bool firth) {
-  const size_t cells = (size_t)snps * (size_t)n;
-  const size_t items = (size_t)std::min<long>(spa_batch_items(indiv, n, firth), (long)cells);
-  return cells * ((firth ? 4 : 1) * sizeof(double) + sizeof(int)) + (size_t)snps * sizeof(int) + ((size_t)snps + 1) * sizeof(long) + cells * 2 * sizeof(int) +
-         sizeof(double) * (size_t)indiv * (size_t)n * ((size_t)kh + 1) + items * (sizeof(double) * (size_t)indiv + (firth ? sizeof(FirthFit) : 2 * sizeof(SpaSide))) +
-         (in_place ? 0 : (size_t)spa_batch_rows(snps, bps, false) * (size_t)bps) + (size_t)own * cells * sizeof(double);
-}
-
-// After k_assoc_score_finish on d's stream: dU, dV and dZ are the scan's score, var and zstat on the device (ld ldu; dV: the fit only).  One host wait reads the
-// number of marked SNPs and items with the list and its offsets; where nothing is marked neither P nor H is touched and no further kernel is launched.  The two
-// entries share everything but the classify epilogue, the solve and the combine: the list, the items, tau, the batches, the bounce rows and k_assoc_spa_form.
-int spa_stage(AssocDriver &d, const unsigned char *plink, const SpaArgs &a, int kh, const double *dU, const double *dV, const double *dZ, long ldu, long ldo) {
-  const long snps = d.snps, indiv = d.indiv, bps = d.bps;
-  const int n = d.n;
-  hipStream_t s = d.s;
-  const size_t cells = (size_t)snps * (size_t)n;
-  const bool firth = a.firth();
-  XBuf bPv, bFl, bList, bOff, bCount;
-  if (bPv.alloc(sizeof(double) * cells * (firth ? 4 : 1)) || bFl.alloc(sizeof(int) * cells) || bList.alloc(sizeof(int) * (size_t)snps) ||
-      bOff.alloc(sizeof(long) * ((size_t)snps + 1)) || bCount.alloc(2 * sizeof(long))) return 1;
-  double *dPv = (double *)bPv.p, *dBeta = dPv + cells, *dSe = dBeta + cells, *dChi = dSe + cells;   // (the three of the fit)
-  int *dFl = (int *)bFl.p, *dList = (int *)bList.p;
-  long *dOff = (long *)bOff.p;
-  launch_in_block_chunks(((long)cells + 255) / 256, [&](unsigned nb, long b0) {
-    if (firth) k_assoc_firth_classify<<<nb, 256, 0, s>>>(snps, n, dU, dV, dZ, ldu, a.z_cutoff, dBeta, dSe, dChi, dPv, dFl, b0);
-    else k_assoc_spa_classify<<<nb, 256, 0, s>>>(snps, n, dZ, ldu, a.z_cutoff, dPv, dFl, b0);
-  });
-  k_assoc_spa_list<<<1, 256, 0, s>>>(snps, n, dFl, dList, dOff, (long *)bCount.p);
-  MXA_HIP(hipGetLastError());
-  long count[2] = {0, 0};
-  std::vector<int> list((size_t)snps);
-  std::vector<long> off((size_t)snps + 1);
-  MXA_HIP(hipMemcpyAsync(count, bCount.p, sizeof(count), hipMemcpyDeviceToHost, s));
-  MXA_HIP(hipMemcpyAsync(list.data(), dList, sizeof(int) * (size_t)snps, hipMemcpyDeviceToHost, s));
-  MXA_HIP(hipMemcpyAsync(off.data(), dOff, sizeof(long) * ((size_t)snps + 1), hipMemcpyDeviceToHost, s));
-  MXA_HIP(hipStreamSynchronize(s));             // the one wait of the stage (only the first count[0] entries of list and off mean anything)
-  const long nk = count[0], nitems = count[1];
-  XBuf bP, bHt, bItemS, bItemC, bG, bSide, bRows;
-  if (nitems > 0) {
-    const size_t col = sizeof(double) * (size_t)indiv;
-    if (bP.alloc(col * (size_t)n) || bHt.alloc(col * (size_t)n * (size_t)kh) || bItemS.alloc(sizeof(int) * (size_t)nitems) || bItemC.alloc(sizeof(int) * (size_t)nitems))
-      return 1;
-    MXA_HIP(hipMemcpy2DAsync(bP.p, col, a.P, sizeof(double) * (size_t)a.ldp, col, (size_t)n, hipMemcpyDefault, s));
-    const unsigned iblocks = (unsigned)((indiv + 255) / 256);
-    if (kh > 0)
-      k_assoc_spa_tau<<<dim3(iblocks, (unsigned)(n * kh)), 256, 0, s>>>(d.dB + (size_t)2 * (size_t)n * (size_t)indiv, d.dB + (size_t)n * (size_t)indiv, indiv, kh,
-                                                                        (double *)bHt.p);
-    launch_in_block_chunks((nk + 255) / 256, [&](unsigned nb, long b0) {
-      k_assoc_spa_items<<<nb, 256, 0, s>>>(nk, snps, n, dFl, dList, dOff, (int *)bItemS.p, (int *)bItemC.p, b0);
-    });
-    MXA_HIP(hipGetLastError());
-    const long max_items = std::min(spa_batch_items(indiv, n, firth), nitems), max_rows = std::min(spa_batch_rows(snps, bps, d.in_place), nk);
-    if (bG.alloc(sizeof(double) * (size_t)max_items * (size_t)indiv) || bSide.alloc((firth ? sizeof(FirthFit) : 2 * sizeof(SpaSide)) * (size_t)max_items) ||
-        (!d.in_place && bRows.alloc((size_t)max_rows * (size_t)bps))) return 1;
-    for (long k0 = 0; k0 < nk;) {
-      long k1 = k0 + 1;                         // one SNP's items always fit; further SNPs while the rows and the items do
-      while (k1 < nk && k1 - k0 < max_rows && off[(size_t)k1 + 1] - off[(size_t)k0] <= max_items) k1++;
-      const long items = off[(size_t)k1] - off[(size_t)k0];
-      const uint8_t *d_rows = plink;
-      if (!d.in_place) {                        // the marked rows of a host matrix, row by row (runs of neighbouring rows in one copy) into the bounce buffer
-        for (long k = k0; k < k1;) {
-          long e = k + 1;
-          while (e < k1 && list[(size_t)e] == list[(size_t)e - 1] + 1) e++;
-          MXA_HIP(hipMemcpyAsync((uint8_t *)bRows.p + (size_t)(k - k0) * (size_t)bps, plink + (size_t)list[(size_t)k] * (size_t)bps, (size_t)(e - k) * (size_t)bps,
-                                 hipMemcpyDefault, s));
-          k = e;
-        }
-        d_rows = (const uint8_t *)bRows.p;
-      }
-      const long tiles = (k1 - k0 + kSpaTile - 1) / kSpaTile;
-      launch_in_block_chunks(tiles * (long)iblocks, [&](unsigned nb, long b0) {
-        k_assoc_spa_form<<<nb, 256, 0, s>>>(d_rows, bps, d.in_place ? 0 : 1, indiv, snps, n, kh, dList, dOff, k0, k1, dFl, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD,
-                                            d.dM, (const double *)bHt.p, (double *)bG.p, (long)iblocks, b0);
-      });
-      launch_in_block_chunks(firth ? items : 2 * items, [&](unsigned nb, long b0) {
-        if (firth)
-          k_assoc_firth<<<nb, 256, 0, s>>>((const double *)bG.p, indiv, (const double *)bP.p, (const int *)bItemS.p, (const int *)bItemC.p, off[(size_t)k0], items, dU,
-                                           ldu, a.penalty, a.tol, a.max_iter, (FirthFit *)bSide.p, b0);
-        else
-          k_assoc_spa<<<nb, 256, 0, s>>>((const double *)bG.p, indiv, (const double *)bP.p, (const int *)bItemS.p, (const int *)bItemC.p, off[(size_t)k0], items, dU,
-                                         ldu, a.tol, a.max_iter, (SpaSide *)bSide.p, b0);
-      });
-      launch_in_block_chunks((items + 255) / 256, [&](unsigned nb, long b0) {
-        if (firth)
-          k_assoc_firth_combine<<<nb, 256, 0, s>>>(items, off[(size_t)k0], (const int *)bItemS.p, (const int *)bItemC.p, dU, ldu, (const FirthFit *)bSide.p, a.penalty,
-                                                   snps, dBeta, dSe, dChi, dPv, dFl, b0);
-        else
-          k_assoc_spa_combine<<<nb, 256, 0, s>>>(items, off[(size_t)k0], (const int *)bItemS.p, (const int *)bItemC.p, dU, ldu, (const SpaSide *)bSide.p, snps, dPv, dFl,
-                                                 b0);
-      });
-      MXA_HIP(hipGetLastError());
-      k0 = k1;
-    }
-  }
-  const size_t pcol = sizeof(double) * (size_t)snps, fcol = sizeof(int) * (size_t)snps;
-  const struct { double *to; const double *from; } results[4] = {{a.pval, dPv}, {a.beta, dBeta}, {a.se, dSe}, {a.chisq, dChi}};
-  for (int j = 0; j < (firth ? 4 : 1); j++)
-    if (results[j].to) MXA_HIP(hipMemcpy2DAsync(results[j].to, sizeof(double) * (size_t)ldo, results[j].from, pcol, pcol, (size_t)n, hipMemcpyDefault, s));
-  if (a.flag) MXA_HIP(hipMemcpy2DAsync(a.flag, sizeof(int) * (size_t)ldo, dFl, fcol, fcol, (size_t)n, hipMemcpyDefault, s));
-  MXA_HIP(hipStreamSynchronize(s));             // the buffers of the stage are released on return
-  return 0;
-}
-
-// B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c.  spa: the stage of the saddlepoint correction or of the
-// fit follows the epilogue
+// B = [R | Wt | H]: column c of R, column n + c of Wt, columns 2 n + c kh + j of H belong to trait c.  after: a stage of another unit follows the epilogue
+// (mxa_assoc_stage.h)
 int assoc_score(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
-                double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const SpaArgs *spa = nullptr, const AssocAfterScan *after = nullptr) {
+                double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const AssocAfterScan *after = nullptr) {
   const int ncols = n * (kh + 2);
-  AssocDriver d(after ? after->who : !spa ? "mxa_assoc_score" : spa->firth() ? "mxa_assoc_score_firth" : "mxa_assoc_score_spa", snps, indiv, ncols, n, out_dev);
+  AssocDriver d(after ? after->who : "mxa_assoc_score", snps, indiv, ncols, n, out_dev);
   double *const res[3] = {score, var, zstat};
   const size_t e_bytes = sizeof(double) * (size_t)snps * (size_t)n;
-  size_t extra = e_bytes;
-  if (after) extra += after->extra_bytes + (score ? 0 : e_bytes);
-  if (spa) {
-    int p_dev = -1;
-    const int dev = select_device();
-    if (dev < 0) return 1;
-    const bool in_place = ptr_location(plink, &p_dev) == 1 && p_dev == dev;
-    extra += spa_bytes(snps, indiv, n, kh, (indiv + 3) / 4, in_place, !score + !zstat + (spa->firth() && !var), spa->firth());
+  size_t extra = e_bytes;                       // E
+  if (after) {                                  // the stage's own memory, and an array for every result it reads that the caller did not give
+    extra += after->extra_bytes;
+    for (int j = 0; j < 3; j++)
+      if (after->reads[j] && !res[j]) extra += e_bytes;
   }
   if (d.begin(plink, res, extra)) return 1;
   hipStream_t s = d.s;
-  XBuf bE, bU, bV, bZ;
+  XBuf bE, bOwn[3];
   if (bE.alloc(e_bytes)) return 1;
   const long ldu = out_dev ? ldo : snps;
-  if (spa) {                                    // the stage reads U and z (the fit: and V) on the device, whether the caller asked for them or not
-    if (!d.out_d[0]) { if (bU.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[0] = (double *)bU.p; }
-    if (spa->firth() && !d.out_d[1]) { if (bV.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[1] = (double *)bV.p; }
-    if (!d.out_d[2]) { if (bZ.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[2] = (double *)bZ.p; }
-  }
-  if (after && !d.out_d[0]) { if (bU.alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[0] = (double *)bU.p; }   // a stage reads U on the device
+  for (int j = 0; j < 3 && after; j++)
+    if (after->reads[j] && !d.out_d[j]) { if (bOwn[j].alloc(sizeof(double) * (size_t)ldu * (size_t)n)) return 1; d.out_d[j] = (double *)bOwn[j].p; }
   double *dE = (double *)bE.p;
   const size_t col = sizeof(double) * (size_t)indiv;
-  double *dW = d.dB + (size_t)n * (size_t)indiv;
+  double *dW = d.dB + (size_t)n * (size_t)indiv, *dH = d.dB + (size_t)2 * (size_t)n * (size_t)indiv;
   MXA_HIP(hipMemcpy2DAsync(d.dB, col, R, sizeof(double) * (size_t)ldr, col, (size_t)n, hipMemcpyDefault, s));
   MXA_HIP(hipMemcpy2DAsync(dW, col, Wt, sizeof(double) * (size_t)ldw, col, (size_t)n, hipMemcpyDefault, s));
   if (kh > 0)
-    MXA_HIP(hipMemcpy2DAsync(d.dB + (size_t)2 * (size_t)n * (size_t)indiv, col, H, sizeof(double) * (size_t)ldh, col, (size_t)n * (size_t)kh, hipMemcpyDefault, s));
+    MXA_HIP(hipMemcpy2DAsync(dH, col, H, sizeof(double) * (size_t)ldh, col, (size_t)n * (size_t)kh, hipMemcpyDefault, s));
   if (d.pack_and_clear()) return 1;
   const long bps = d.bps;
   auto weights = [&](const uint8_t *d_rows, long r0, long nr) -> int {          // E: kScoreCols weight columns a pass
@@ -1090,9 +521,9 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
                                             ldu, b0);
   });
   MXA_HIP(hipGetLastError());
-  if (spa && spa_stage(d, plink, *spa, kh, d.out_d[0], d.out_d[1], d.out_d[2], ldu, ldo)) return 1;
   if (after) {
-    const AssocScanView v = {snps, indiv, bps, n, kh, d.in_place, out_dev, s, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD, d.dM, dW, d.out_d[0], ldu};
+    const AssocScanView v = {snps, indiv, bps, n, kh, d.in_place, out_dev, s, d.dCnt, d.dCnt + snps, d.dCnt + 2 * snps, d.dD, d.dM, dW, dH,
+                             d.out_d[0], d.out_d[1], d.out_d[2], ldu};
     if (after->run(after->self, v, plink)) return 1;
   }
   return d.copy_out(res, ldo, nobs);
@@ -1102,7 +533,7 @@ int assoc_score(const unsigned char *plink, long snps, long indiv, const double 
 
 int assoc_score_then(const unsigned char *plink, long snps, long indiv, const double *R, long ldr, const double *Wt, long ldw, const double *H, long ldh, int n, int kh,
                      double *score, double *var, double *zstat, long ldo, int *nobs, bool out_dev, const AssocAfterScan &after) {
-  return assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, out_dev, nullptr, &after);
+  return assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, out_dev, &after);
 }
 
 }  // namespace mxa
@@ -1129,15 +560,10 @@ extern "C" int mxa_assoc_linear(const unsigned char *plink, int snps, int indiv,
   const char *who = "mxa_assoc_linear";
   const char *bad = assoc_linear_args(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo);
   if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
-  int given = 0, on_dev = 0;
-  for (const double *p : {(const double *)beta, (const double *)se, (const double *)tstat})
-    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
-  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: beta, se and tstat must be all host or all device pointers", who); return 1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  const int rc = assoc_linear(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo, nobs, dof, on_dev != 0);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
+  bool out_dev = false;
+  if (results_on_one_side(who, "beta, se and tstat", {beta, se, tstat}, &out_dev)) return 1;
+  DeviceRestore restore;
+  return assoc_linear(plink, snps, indiv, Y, ldy, n, Q, ldq, k, beta, se, tstat, ldo, nobs, dof, out_dev);
 }
 
 extern "C" int mxa_assoc_logistic_null(int indiv, const double *y, const double *W, long ldw, int q, double tol, int max_iter, double *gamma, double *r, double *w,
@@ -1174,60 +600,9 @@ extern "C" int mxa_assoc_score(const unsigned char *plink, int snps, int indiv, 
   const char *who = "mxa_assoc_score";
   const char *bad = assoc_score_args(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo);
   if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
-  int given = 0, on_dev = 0;
-  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat})
-    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
-  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var and zstat must be all host or all device pointers", who); return 1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
+  bool out_dev = false;
+  if (results_on_one_side(who, "score, var and zstat", {score, var, zstat}, &out_dev)) return 1;
+  DeviceRestore restore;
+  return assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, out_dev);
 }
 
-extern "C" int mxa_assoc_score_spa(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
-                                   const double *H, long ldh, int n, int kh, double z_cutoff, double tol, int max_iter, double *score, double *var, double *zstat,
-                                   double *pval, long ldo, int *flag, int *nobs) {
-  using namespace mxa;
-  clear_error();
-  const char *who = "mxa_assoc_score_spa";
-  const char *bad = assoc_score_spa_args(plink, snps, indiv, P, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, tol, max_iter, score, var, zstat, pval, ldo);
-  if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
-  int given = 0, on_dev = 0;
-  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat, (const double *)pval})
-    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
-  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var, zstat and pval must be all host or all device pointers", who); return 1; }
-  if (flag && (ptr_location(flag, nullptr) == 1) != (on_dev != 0)) { set_error(1, "%s: flag and pval must be both host or both device pointers", who); return 1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  const SpaArgs spa = {P, ldp, z_cutoff, tol, max_iter, pval, flag};
-  const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0, &spa);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
-}
-
-extern "C" int mxa_assoc_score_firth(const unsigned char *plink, int snps, int indiv, const double *P, long ldp, const double *R, long ldr, const double *Wt, long ldw,
-                                     const double *H, long ldh, int n, int kh, double z_cutoff, int penalty, double tol, int max_iter, double *score, double *var,
-                                     double *zstat, double *beta, double *se, double *chisq, double *pval, long ldo, int *flag, int *nobs) {
-  using namespace mxa;
-  clear_error();
-  const char *who = "mxa_assoc_score_firth";
-  const char *bad = assoc_score_firth_args(plink, snps, indiv, P, ldp, R, ldr, Wt, ldw, H, ldh, n, kh, z_cutoff, penalty, tol, max_iter, score, var, zstat, beta, ldo);
-  if (bad) { set_error(1, "%s: %s", who, bad); return 1; }
-  int given = 0, on_dev = 0;
-  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat, (const double *)beta, (const double *)se, (const double *)chisq,
-                          (const double *)pval})
-    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
-  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var, zstat, beta, se, chisq and pval must be all host or all device pointers", who); return 1; }
-  if (flag && (ptr_location(flag, nullptr) == 1) != (on_dev != 0)) { set_error(1, "%s: flag and beta must be both host or both device pointers", who); return 1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  SpaArgs fit = {P, ldp, z_cutoff, tol, max_iter, pval, flag};
-  fit.penalty = penalty;
-  fit.beta = beta;
-  fit.se = se;
-  fit.chisq = chisq;
-  const int rc = assoc_score(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0, &fit);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
-}

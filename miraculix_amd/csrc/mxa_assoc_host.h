@@ -1,5 +1,5 @@
-// mxa_assoc_host.h -- the host-only part of the association scan (mxa_assoc.hip): the covariate basis of mxa_assoc_basis and the argument rules of
-// mxa_assoc_linear, mxa_assoc_score, mxa_assoc_score_spa and mxa_assoc_score_firth (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
+// mxa_assoc_host.h -- the host-only part of the association scan (mxa_assoc.hip) and of its saddlepoint / Firth stage (mxa_assoc_spa.hip): the covariate basis of
+// mxa_assoc_basis and the argument rules of mxa_assoc_linear, mxa_assoc_score, mxa_assoc_score_spa and mxa_assoc_score_firth (the null model of the score test: mxa_assoc_null_host.h).  Plain C++ without any HIP header, so that a stand-alone
 // program can compile it for the CPU (tools/assoc_host_check.cpp, tools/assoc_score_host_check.cpp, tools/assoc_firth_host_check.cpp, run under
 // -fsanitize=address,undefined).
 #pragma once

@@ -1,6 +1,6 @@
 // mxa_assoc_set.hip -- set-based association (include/miraculix_amd.h: mxa_assoc_set, mxa_assoc_skat_pvalue): burden and SKAT statistics of
 // SNP sets after the score scan of mxa_assoc_score.  The scan runs unchanged (mxa_assoc.hip: assoc_score_then); this unit is the stage that follows it on the
-// scan's stream.  Per batch of sets: the rows of the batch's SNPs are gathered (a host matrix: into a bounce buffer; a device matrix is read in place),
+// scan's stream, as mxa_assoc_spa.hip is for the saddlepoint correction and the fit (the interface and what the kernels share: mxa_assoc_stage.h).  Per batch of sets: the rows of the batch's SNPs are gathered (a host matrix: into a bounce buffer; a device matrix is read in place),
 // k_assoc_set_gram forms the weighted Gram S = X diag(w) X^T of every (set, trait) tile by tile on the fp64 MFMA, split over the individuals into pieces of
 // kSetSplit, k_assoc_set_phi folds the pieces in ascending order, subtracts the covariate term and mirrors, k_assoc_set_stat and k_assoc_set_fold sum the six
 // statistics.  No atomics anywhere: every sum over individuals runs in an order fixed by indiv alone, every sum over a set in an order fixed by its size alone,
@@ -25,13 +25,6 @@ typedef double set_v4 __attribute__((ext_vector_type(4)));
 struct SetDesc { int ent0, m, tj, tjp, c, pad; long s_off; };   // one (set, trait, tile pair tj <= tjp): the set's first entry in the batch, its size, the block of S
 struct SetItem { int ent0, m, c, set; long s_off, t_off; };     // one (set, trait): ... and its first slot of the per-tile partial statistics
 
-__device__ __forceinline__ double set_mu(const int *__restrict__ nobs, const int *__restrict__ c1, const int *__restrict__ c2, long s) {
-  return __ddiv_rn((double)((long)c1[s] + 2 * (long)c2[s]), (double)nobs[s]);   // as k_assoc_score_finish
-}
-__device__ __forceinline__ double set_decode(unsigned code, double mu) {         // 00 -> 0, 01 -> mu, 10 -> 1, 11 -> 2
-  return (code & 2u) ? ((code & 1u) ? 2.0 : 1.0) : ((code & 1u) ? mu : 0.0);
-}
-
 // ---- the hot path.  Workgroup blk0 + blockIdx.x = (work item, piece): the 16 x 16 tile (tj, tjp) of S of one (set, trait) over the individuals of piece p,
 // [kSetSplit p, kSetSplit p + kSetSplit).  Wave v takes the logical words 64 p + v, + 4, ... of the piece (the words of assoc_load_word: the same fields for
 // every alignment of a row).  Lane (r, g) = (lane & 15, lane >> 4) loads the word of row r of the A tile and of row r of the B tile (the diagonal tile: one
@@ -53,8 +46,8 @@ __global__ void __launch_bounds__(256) k_assoc_set_gram(const uint8_t *__restric
   const bool va = ja < d.m, vb = jb < d.m;
   double mu_a = 0.0, mu_b = 0.0;
   const uint8_t *row_a = rows, *row_b = rows;
-  if (va) { mu_a = set_mu(nobs, c1, c2, ent_snp[d.ent0 + ja]); row_a = rows + (size_t)ent_row[d.ent0 + ja] * (size_t)bps; }
-  if (vb) { mu_b = set_mu(nobs, c1, c2, ent_snp[d.ent0 + jb]); row_b = rows + (size_t)ent_row[d.ent0 + jb] * (size_t)bps; }
+  if (va) { mu_a = assoc_mu(nobs, c1, c2, ent_snp[d.ent0 + ja]); row_a = rows + (size_t)ent_row[d.ent0 + ja] * (size_t)bps; }
+  if (vb) { mu_b = assoc_mu(nobs, c1, c2, ent_snp[d.ent0 + jb]); row_b = rows + (size_t)ent_row[d.ent0 + jb] * (size_t)bps; }
   const int sh_a = (int)(reinterpret_cast<uintptr_t>(row_a) & 15), sh_b = (int)(reinterpret_cast<uintptr_t>(row_b) & 15);
   const double *w = W + (size_t)d.c * (size_t)indiv;
   const long nwords = (bps + 15) / 16, words_per_piece = kSetSplit / 64;
@@ -73,7 +66,7 @@ __global__ void __launch_bounds__(256) k_assoc_set_gram(const uint8_t *__restric
 #pragma unroll
     for (int q = 0; q < 16; q++) {
       const unsigned ca = (unsigned)((q < 8 ? a_lo : a_hi) >> (8 * (q & 7))) & 3u, cb = (unsigned)((q < 8 ? b_lo : b_hi) >> (8 * (q & 7))) & 3u;
-      const double xa = set_decode(ca, mu_a), xb = __dmul_rn(wt[q], set_decode(cb, mu_b));
+      const double xa = assoc_decode(ca, mu_a), xb = __dmul_rn(wt[q], assoc_decode(cb, mu_b));
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, xb, acc, 0, 0, 0);
     }
   }
@@ -99,7 +92,7 @@ __global__ void __launch_bounds__(256) k_assoc_set_phi(const SetDesc *__restrict
   double v = 0.0;
   for (long p = 0; p < pieces; p++) v += part[((size_t)di * (size_t)pieces + (size_t)p) * 256 + (size_t)t];
   const long s = ent_snp[d.ent0 + j], sp = ent_snp[d.ent0 + jp];
-  const double mu = set_mu(nobs, c1, c2, s), mup = set_mu(nobs, c1, c2, sp);
+  const double mu = assoc_mu(nobs, c1, c2, s), mup = assoc_mu(nobs, c1, c2, sp);
   for (int h = 0; h < kh; h++) {
     const size_t col = ((size_t)2 * (size_t)n + (size_t)d.c * (size_t)kh + (size_t)h) * (size_t)snps;
     const double a = __fma_rn(mu, M[col + (size_t)s], D[col + (size_t)s]), ap = __fma_rn(mup, M[col + (size_t)sp], D[col + (size_t)sp]);
@@ -110,24 +103,10 @@ __global__ void __launch_bounds__(256) k_assoc_set_phi(const SetDesc *__restrict
   o[(size_t)jp + (size_t)j * (size_t)d.m] = v;
 }
 
-// three sums of a workgroup at once: the wave's shuffles (32, ..., 1), then (w0 + w1) + (w2 + w3) through the LDS
-__device__ __forceinline__ void set_block_sums(double (&v)[3], double (*red)[4]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
-    if (lane == 0) red[q][wave] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 3; q++) v[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-}
-
 // ---- the sums over pairs: workgroup blk0 + blockIdx.x = slot of (item, row tile rb) takes the rows j in [16 rb, 16 rb + 16) of A = diag(omega) Phi
 // diag(omega), A_jj' = (omega_j Phi_jj') omega_j'.  Thread t takes the columns j' = t, t + 256, ... in ascending order and, per column, the tile's rows in
 // ascending order: varB += A_jj', c2 = fma(A_jj', A_jj', c2), and (A A)_jj' = the chain fma(A_jl, A_lj', .) over ascending l, never stored,
-// c4 = fma((A A)_jj', (A A)_jj', c4).  The three sums of the slot end in set_block_sums; k_assoc_set_fold adds the slots of an item in ascending order.
+// c4 = fma((A A)_jj', (A A)_jj', c4).  The three sums of the slot end in assoc_block_sums; k_assoc_set_fold adds the slots of an item in ascending order.
 __global__ void __launch_bounds__(256) k_assoc_set_stat(const SetItem *__restrict__ items, const int *__restrict__ tile_item, const double *__restrict__ ent_wt,
                                                          const double *__restrict__ phi, double *__restrict__ spart, long blk0) {
   __shared__ double red[3][4];
@@ -153,7 +132,7 @@ __global__ void __launch_bounds__(256) k_assoc_set_stat(const SetItem *__restric
       v[2] = __fma_rn(aa, aa, v[2]);
     }
   }
-  set_block_sums(v, red);
+  assoc_block_sums<3>(v, red);
   if (threadIdx.x < 3) spart[3 * (size_t)slot + threadIdx.x] = v[threadIdx.x];
 }
 
@@ -275,15 +254,8 @@ struct SetStage {
       }
       MXA_HIP(hipMemcpyAsync(bItems.p, h.items.data(), sizeof(SetItem) * (size_t)b.items, hipMemcpyHostToDevice, s));
       const uint8_t *d_rows = plink;
-      if (!in_place) {                          // the batch's distinct rows of a host matrix (runs of neighbouring rows in one copy) into the bounce buffer
-        const long nr = (long)h.rows.size();
-        for (long k = 0; k < nr;) {
-          long e = k + 1;
-          while (e < nr && h.rows[(size_t)e] == h.rows[(size_t)e - 1] + 1) e++;
-          MXA_HIP(hipMemcpyAsync((uint8_t *)bRows.p + (size_t)k * (size_t)v.bps, plink + (size_t)h.rows[(size_t)k] * (size_t)v.bps, (size_t)(e - k) * (size_t)v.bps,
-                                 hipMemcpyDefault, s));
-          k = e;
-        }
+      if (!in_place) {                          // the batch's distinct rows of a host matrix into the bounce buffer
+        if (assoc_gather_rows((uint8_t *)bRows.p, plink, v.bps, h.rows.data(), (long)h.rows.size(), s)) return 1;
         d_rows = (const uint8_t *)bRows.p;
       }
       if (b.descs > 0) {
@@ -333,27 +305,19 @@ extern "C" int mxa_assoc_set(const unsigned char *plink, int snps, int indiv, co
     set_error(1, "%s: %s", who, msg);
     return 1;
   }
-  int given = 0, on_dev = 0;
-  for (const double *p : {(const double *)score, (const double *)var, (const double *)zstat, (const double *)stat, (const double *)phi})
-    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
-  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: score, var, zstat, stat and phi must be all host or all device pointers", who); return 1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  int rc = 1;
+  bool out_dev = false;
+  if (results_on_one_side(who, "score, var, zstat, stat and phi", {score, var, zstat, stat, phi}, &out_dev)) return 1;
+  DeviceRestore restore;
   const int dev = select_device();
-  if (dev >= 0) {
-    int p_dev = -1;
-    SetStage st = {nsets, n, set_ptr, set_idx, set_wt, stat, phi, lds, ptr_location(plink, &p_dev) == 1 && p_dev == dev};
-    long max_entries = LONG_MAX;
-    const char *e = getenv("MXA_ASSOC_SET_BATCH");
-    if (e && atol(e) > 0) max_entries = atol(e);
-    st.plan = set_plan(nsets, set_ptr, n, indiv, max_entries, kSetBudget);
-    st.prepare();
-    const AssocAfterScan after = {who, st.bytes(indiv, ((long)indiv + 3) / 4, on_dev != 0), &st, set_stage_run};
-    rc = assoc_score_then(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, on_dev != 0, after);
-  }
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
+  if (dev < 0) return 1;
+  SetStage st = {nsets, n, set_ptr, set_idx, set_wt, stat, phi, lds, assoc_rows_in_place(plink, dev)};
+  long max_entries = LONG_MAX;
+  const char *e = getenv("MXA_ASSOC_SET_BATCH");
+  if (e && atol(e) > 0) max_entries = atol(e);
+  st.plan = set_plan(nsets, set_ptr, n, indiv, max_entries, kSetBudget);
+  st.prepare();
+  const AssocAfterScan after = {who, st.bytes(indiv, ((long)indiv + 3) / 4, out_dev), {true, false, false}, &st, set_stage_run};   // the stage reads U alone
+  return assoc_score_then(plink, snps, indiv, R, ldr, Wt, ldw, H, ldh, n, kh, score, var, zstat, ldo, nobs, out_dev, after);
 }
 
 extern "C" int mxa_assoc_skat_pvalue(long count, const double *Q, const double *c1, const double *c2, const double *c4, double *pval, double *df) {

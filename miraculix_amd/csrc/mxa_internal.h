@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -192,6 +193,13 @@ int enable_peer(int cur, int peer);
 // called once by every shard worker thread: this thread issues transfers at the same time as other threads
 void mark_thread_concurrent();
 int select_device();                       // honours HIP_DEVICE / CUDA_DEVICE; -1 + error when no device
+// the calling thread's current device is put back when an entry that selects or switches devices returns (a caller such as PyTorch keeps its own notion of
+// the current device)
+struct DeviceRestore {
+  int prev = -1;
+  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; } }
+  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
 // SNP-sharded objects (mxa_multi.cpp)
 int multi_requested();                     // MIRACULIX_NUM_GPUS (>= 1)
 int multi_create(const uint8_t *plink, const uint8_t *plink_t, long snps, long indiv, const double *f, int max_n, int shards, void **out);
@@ -219,6 +227,33 @@ void clear_error();   // every fallible API entry starts with it: mxa_last_error
 bool check_hip(hipError_t e, const char *func, int line);
 #define MXA_HIP(x) do { if (!::mxa::check_hip((x), __func__, __LINE__)) return 1; } while (0)
 void debug_info(const char *fmt, ...);
+
+// ---- what the entries of the association family repeat (mxa_assoc.hip, mxa_assoc_spa.hip, mxa_assoc_set.hip; the device guard: DeviceRestore above)
+// The result pointers of an entry (nullable each) are all host or all device pointers: *out_dev says which (host where none is given); a mix is refused
+// with the error "<who>: <names> must be all host or all device pointers" (return 1).
+inline int results_on_one_side(const char *who, const char *names, std::initializer_list<const void *> results, bool *out_dev) {
+  int given = 0, on_dev = 0;
+  for (const void *p : results)
+    if (p) { given++; on_dev += ptr_location(p, nullptr) == 1; }
+  if (on_dev != 0 && on_dev != given) { set_error(1, "%s: %s must be all host or all device pointers", who, names); return 1; }
+  *out_dev = on_dev != 0;
+  return 0;
+}
+// plink is memory of device dev: its rows are read where they lie
+inline bool assoc_rows_in_place(const void *plink, int dev) {
+  int p_dev = -1;
+  return ptr_location(plink, &p_dev) == 1 && p_dev == dev;
+}
+// rows[0 .. count) of a host matrix (pitch bps, ascending) -> rows 0 .. count of a bounce buffer on the device, runs of neighbouring rows in one copy
+inline int assoc_gather_rows(uint8_t *d_bounce, const unsigned char *plink, long bps, const int *rows, long count, hipStream_t s) {
+  for (long k = 0; k < count;) {
+    long e = k + 1;
+    while (e < count && rows[e] == rows[e - 1] + 1) e++;
+    MXA_HIP(hipMemcpyAsync(d_bounce + (size_t)k * (size_t)bps, plink + (size_t)rows[k] * (size_t)bps, (size_t)(e - k) * (size_t)bps, hipMemcpyDefault, s));
+    k = e;
+  }
+  return 0;
+}
 // Wall-clock phases of ONE ABI call (host side), printed as one line under PRINT_LEVEL > 0 / print_details: where the time of a call through the plain
 // symbols goes -- operand classification, workspace growth, the staged upload of a pageable B (the host thread blocks in it), the enqueueing of the
 // kernels, the final stream wait.  Off: one branch per mark.  gemm_any arms tl_call_clock, gemm_device marks through it.

@@ -98,14 +98,6 @@ class WorkerPool {
 };
 WorkerPool &worker_pool() { static WorkerPool *p = new WorkerPool(); return *p; }   // never destroyed: no thread joins at process exit
 
-// the calling thread's current device is put back when a multi-device entry returns (the entries switch devices while they work;
-// a caller such as PyTorch keeps its own notion of the current device)
-struct DeviceRestore {
-  int prev = -1;
-  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; } }
-  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 struct Shard {
   Handle *h = nullptr;
   long begin = 0, end = 0;                   // SNP block

@@ -7,23 +7,23 @@ flags 0, 2 and 3 exactly the one-step values or NaN (check_unfitted_cells); over
 that case's fitted cells; in the tail cases log pval by the relative rule of tail_errors (tests/_assoc_spa_ref.py) with its rules for the underflow; host and
 device operands give the same bits.
 
-What each test reaches in mxa_assoc.hip that the suite had not:
-  bisect        k_assoc_firth: `if (!(bn > lo && bn < hi)) bn = 0.5 * (lo + hi)` taken once to three times an item, on both sides (`if (f < 0.0) lo = b; else
-                hi = b` with both ends finite), beside items of the same launch that never take it; kh 3: the same with g != 0 at every individual.
+What each test reaches in mxa_assoc_spa.hip that the suite had not (spa_newton_step is the safeguarded step that k_assoc_firth shares with k_assoc_spa):
+  bisect        spa_newton_step: `if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi)` taken once to three times an item, on both sides (`if (f < 0.0) lo = t; else
+                hi = t` with both ends finite), beside items of the same launch that never take it; kh 3: the same with g != 0 at every individual.
   alt           k_assoc_firth: `if (alt > 0.0) fp = alt` NOT taken (alt <= 0, K'' stands in) at one evaluation of four items.
   negative      k_assoc_firth: the support test on U < 0, `-((v4[3] - c0) - U)`: kSpaOutside written (penalty 0, margin exactly 0), passed with a margin of
                 5e-4 ... 3e-3 A, and skipped with the penalty (beta^ < 0).
-  saturated     k_assoc_firth: `if (!isfinite(bn)) status = kSpaFailed` at the first evaluation (K''(0) = 0) and at the second (every exp(-|beta g|) = 0: f / 0
+  saturated     spa_newton_step: `if (!isfinite(tn)) return kNewtonFailed` at the first evaluation (K''(0) = 0) and at the second (every exp(-|beta g|) = 0: f / 0
                 without the penalty, 0 / 0 with it); k_assoc_firth_combine: `if (a.status != kSpaSolved) return` beside solved items of the same batch.
-  zero cutoff   k_assoc_firth_classify: `az < z_cutoff` with z_cutoff = 0 (false for z = 0); k_assoc_firth: f = 0 exactly, bn = b = 0 accepted at the first
-                evaluation by `fabs(bn - b) <= tol * fabs(bn)` with both sides 0; k_assoc_firth_combine: x2 = 0, pval = erfc(0) = 1.  (`fmax(x2, 0.0)` is not
+  zero cutoff   k_assoc_firth_classify: `az < z_cutoff` with z_cutoff = 0 (false for z = 0); k_assoc_firth: f = 0 exactly, tn = t = 0 accepted at the first
+                evaluation by `fabs(tn - t) <= tol * fabs(tn)` (spa_newton_step) with both sides 0; k_assoc_firth_combine: x2 = 0, pval = erfc(0) = 1.  (`fmax(x2, 0.0)` is not
                 reached with a negative x2: tests/test_assoc_firth_limits_cpu.py.)
   tails         k_assoc_firth_combine: `erfc(sqrt(0.5 * x2))` from 1e-14 down to 3.5e-290 and past its underflow (x2 up to 2700); k_assoc_firth with 33
                 individuals a thread (8195).
   lists         spa_stage with firth: 1145 items, more than kFirthResident = 1024 workgroups of k_assoc_firth in one launch; k_assoc_firth_combine with
                 blockIdx.x > 0; the batches cut by items, by rows and by both, item_base = off[k0] > 0 in both kernels.
-  max_iter      k_assoc_firth: `evals >= max_iter` on an evaluation that bisected, and on one that did not, beside accepted items.
-  tol           k_assoc_firth: the stop rule at 2^-12 (an evaluation or two earlier) and 2^-40 (later).
+  max_iter      spa_newton_step: `evals >= max_iter` on an evaluation that bisected, and on one that did not, beside accepted items.
+  tol           spa_newton_step: the stop rule at 2^-12 (an evaluation or two earlier) and 2^-40 (later).
 
 Measured on an MI355X (flags as [0, 1, 2, 3]; eps seen on x86-64 with 80-bit long double / the device's largest of the four differences; penalty 0, then 1):
   bisect (259, kh 1)        flags [9, 24, 0, 0]: 6.4e-14 / 1.9e-14 and 6.2e-14 / 2.4e-14

@@ -114,7 +114,7 @@ def test_the_item_knob_cuts_where_the_table_says(which):
 
 def test_the_item_knob_is_read_per_call_and_documented():
     read = lambda *parts: open(os.path.join(ROOT, *parts)).read()          # noqa: E731
-    source = read("miraculix_amd", "csrc", "mxa_assoc.hip")
+    source = read("miraculix_amd", "csrc", "mxa_assoc_spa.hip")
     body = source[source.index("long spa_batch_items("):source.index("long spa_batch_rows(")]
     assert 'getenv("MXA_ASSOC_SPA_ITEMS")' in body and "static" not in body and "std::max<long>(n," in body
     header = read("include", "miraculix_amd.h")

@@ -4,19 +4,20 @@ asserts the conditions on the inputs without a device.  The comparison is that m
 bit for bit mxa_assoc_score's; |log pval - log p_LD| <= 16 max(eps, 2^-48), eps = the case's largest |log p_64 - log p_LD|; host and device operands, and
 every batch size, give the same bits.
 
-What each test reaches in mxa_assoc.hip that the suite had not:
+What each test reaches in mxa_assoc_spa.hip that the suite had not:
   many_marked_snps    k_assoc_spa_list: rounds beyond the first of `for (s0 ...; s0 += 256)` with base_k and base_item carried, both spa_block_scan calls on
                       the same LDS array per round, a partial last round.  k_assoc_spa_items and k_assoc_spa_combine: blockIdx.x > 0 (577 and 269 marked SNPs,
                       1145 and 716 items).  k_assoc_spa_form with n = 8, and with n (kh + 2) = 36: a_j read from the columns 6 ... 35 of D and M, the last four of
                       them in the product's second chunk of 32 columns.
   round_boundaries    the same loop with marks at the first and last thread of a round, a round without a mark (tot_k = 0), a round entirely marked, a last
-                      round of 6 SNPs; entirely missing rows between them.  spa_stage's gather for a host matrix: one run of 1030 rows, and 515 single rows.
+                      round of 6 SNPs; entirely missing rows between them.  spa_stage's gather for a host matrix (assoc_gather_rows): one run of 1030 rows, and 515 single
+                      rows.
                       MXA_ASSOC_SPA_BATCH in {1, 8, 9, 257}: batches that end on, before and after a tile of kSpaTile = 8, and one past 256 marked SNPs.
   item_cut            spa_stage: `off[k1 + 1] - off[k0] <= max_items` ends batches (MXA_ASSOC_SPA_ITEMS), alone, with the row cut, and raised to n ("one SNP's
                       items always fit"); k_assoc_spa_form with item_base = off[k0] > 0 and tiles counted from a k0 that is no multiple of 8.
-  max_iter            k_assoc_spa: `evals >= max_iter` in the bracket branch on some sides while others of the same batch are accepted; k_assoc_spa_combine:
+  max_iter            k_assoc_spa, in spa_newton_step: `evals >= max_iter` behind the bracket check on some sides while others of the same batch are accepted; k_assoc_spa_combine:
                       `b.status == kSpaFailed` and `a.status != kSpaSolved` beside solved items.
-  loose_tol           k_assoc_spa: `fabs(tn - t) <= tol * fabs(tn)` with a tol that ends the loop an evaluation earlier than 2^-30.
+  loose_tol           k_assoc_spa, in spa_newton_step: `fabs(tn - t) <= tol * fabs(tn)` with a tol that ends the loop an evaluation earlier than 2^-30.
   deep_tail           k_assoc_spa: the tail 0.5 erfc(zeta / sqrt 2) from 1e-14 down to 7e-290 and past the underflow of erfc.
 
 Measured on an MI355X (flags as [0, 1, 2, 3]; eps seen on x86-64 with 80-bit long double / the device's largest |log pval - log p_LD|):

@@ -15,4 +15,6 @@ from . import assoc  # noqa: F401
 from .crossproduct import ld_prune, ld_prune_csr  # noqa: F401
 from .assoc import assoc_basis, assoc_linear, assoc_logistic, assoc_logistic_null, assoc_score, assoc_score_firth, assoc_score_spa  # noqa: F401
 from .assoc import assoc_logistic_sets, assoc_set, assoc_skat_pvalue  # noqa: F401
+from . import mixed  # noqa: F401
+from .mixed import assoc_mixed, assoc_mixed_null  # noqa: F401
 from .lib import load_shared_library, set_library_path, check_library_handle  # noqa: F401

@@ -30,6 +30,7 @@
 #   assoc-firth-kernels [snps indiv]   the library kernels inside mxa_assoc_score_spa and mxa_assoc_score_firth, one by one, with the time per item and per (item, evaluation) of k_assoc_spa and k_assoc_firth: tools/perf_assoc_firth.py ... trace under rocprofv3 --kernel-trace, in a run of its own
 #   assoc-set [snps indiv reps]   the set tests (mxa_assoc_set) with sets of 32, 8 and 256 neighbouring SNPs at n = 1, q = 3, beside mxa_assoc_score on the same operands and beside the torch route (decode to fp64 + bmm), one process, alternating calls
 #   assoc-set-kernels [snps indiv]   the library kernels inside mxa_assoc_set, one by one: tools/perf_assoc_set.py ... trace under rocprofv3 --kernel-trace, in a run of its own
+#   assoc-mixed [snps indiv blocks]   the mixed-model scan (miraculix_amd.mixed.assoc_mixed) at n = 1, q = 3, LOCO over the blocks: one whole call, split into the kinship products, the score scan and everything else (HIP events), and the kernel classes of a run of its own under rocprofv3 --kernel-trace
 #   gemm <snps indiv n reps>   k_gemm / k_gemm_i8 kernel time of one shape, 'N' and 'T'
 #   rehearse             the driver's N > 1 bench commands on one GPU (8 virtual shards in-process; 2 and 4 launcher ranks over gloo)
 #   soak                 tools/soak.py + fuzz_shapes.py + fuzz_crossprod.py
@@ -192,6 +193,13 @@ assoc-set-kernels)
   ( cd /tmp && timeout -k 10 800 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc_set.py" ${1:-50000} ${2:-1000000} trace > "$O/assoc_set_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_set_trace_run.log"; exit 1; }
   f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc_set.py summarize "$f" 2>&1 | tee "$O/assoc_set_kernels.txt" || exit 1
   rm -rf "$D"; cp -f "$O/assoc_set_kernels.txt" "$R/profiles/r19_assoc_set_kernels.txt" ;;
+assoc-mixed)
+  # whole-call time of one assoc_mixed call with the split gram / scan / everything else from HIP events, then the kernel classes of a traced run of its own; the text is what profiles/r20_assoc_mixed.txt holds
+  timeout -k 10 900 python3 tools/perf_assoc_mixed.py ${1:-50000} ${2:-1000000} ${3:-5} 2>&1 | tee "$O/assoc_mixed.txt" || exit 1
+  D="$O/assoc_mixed_trace"; rm -rf "$D"; mkdir -p "$D"
+  ( cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv -d "$D" -- python3 "$R/tools/perf_assoc_mixed.py" ${1:-50000} ${2:-1000000} ${3:-5} trace > "$O/assoc_mixed_trace_run.log" 2>&1 ) || { tail -5 "$O/assoc_mixed_trace_run.log"; exit 1; }
+  f=$(find "$D" -name '*kernel_trace.csv' | head -1) && python3 tools/perf_assoc_mixed.py summarize "$f" 2>&1 | tee -a "$O/assoc_mixed.txt" || exit 1
+  rm -rf "$D"; cp -f "$O/assoc_mixed.txt" "$R/profiles/r20_assoc_mixed.txt" ;;
 gemm)
   timeout -k 10 600 python3 tools/perf_gemm.py "$@" 2>&1 | tee -a "$O/gemm.txt" ;;
 rehearse)

@@ -8,23 +8,19 @@ Measured on an MI355X (the bound is 5.7e-14 in every case, eps at most 4.2e-16):
 Shapes: the Gram tile edge is T = 16 and the split unit 4096 individuals.  indiv in {1, 5, 255, 257, 1023, 2051, 4099} (field, byte, word and wave edges; 4099
 crosses the split unit: two pieces); set sizes {0, 1, 2, 15, 16, 17, 33} in every case -- an empty set, the last SNP row alone, a SNP repeated, unsorted
 non-contiguous indices, a contiguous run, overlapping draws with repeats -- and one set of 1024 entries drawn from 64 SNPs at indiv = 257; (n, kh) over
-{1, 2, 3} x {0, 1, 4}; missing calls at 0 and 5 %; weights NULL and random; the padding fields of every row's last byte are dirty throughout."""
-import functools
-import os
-
+{1, 2, 3} x {0, 1, 4}; missing calls at 0 and 5 %; weights NULL and random; the padding fields of every row's last byte are dirty throughout.
+The raw call, the comparison on bytes, the accuracy rule and the cached cases are in tests/_assoc_set_call.py, shared with tests/test_assoc_set_limits_gpu.py."""
 import numpy as np
 import pytest
 
 import _assoc_set_ref as sr
+from _assoc_set_call import LD, NAMES, SNPS, _dev, call, case, check_accuracy, references, same, same_results  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-LD = sr.LD
-SNPS = 24
 #        indiv  n kh missing weights
 CASES = [(1, 1, 0, 0.0, False), (5, 2, 1, 0.0, True), (255, 3, 4, 0.05, True), (257, 1, 1, 0.05, False), (1023, 2, 4, 0.0, True), (2051, 3, 0, 0.05, False),
          (4099, 1, 4, 0.05, True), (257, 2, 0, 0.05, True), (255, 3, 1, 0.0, False)]
-NAMES = ("B", "varB", "Q", "c1", "c2", "c4")
 
 
 @pytest.fixture(scope="module")
@@ -32,115 +28,6 @@ def mx():
     import miraculix_amd as m
     m.load_shared_library()
     return m
-
-
-def make_sets(snps, seed):
-    rng = np.random.default_rng([seed, 31])
-    return [np.zeros(0, np.int64), np.array([snps - 1]), np.array([7, 7]), rng.permutation(snps)[:15], np.arange(4, 20), rng.integers(0, snps, 17),
-            rng.integers(0, snps, 33)]
-
-
-@functools.lru_cache(maxsize=None)
-def case(indiv, n, kh, missing, weighted):
-    codes, R, Wt, H = sr.random_case(indiv, SNPS, n, kh, seed=6, missing=missing)
-    sets = make_sets(SNPS, indiv)
-    rng = np.random.default_rng([indiv, 41])
-    weights = [rng.uniform(0.3, 4.0, len(s)) for s in sets] if weighted else None
-    X = sr.pack_dirty(codes, indiv)
-    for a in (codes, R, Wt, H, X):
-        a.setflags(write=False)
-    return codes, X, R, Wt, H, sets, weights
-
-
-@functools.lru_cache(maxsize=None)
-def references(indiv, n, kh, missing, weighted):
-    codes, _, R, Wt, H, sets, weights = case(indiv, n, kh, missing, weighted)
-    return sr.set_reference(codes, R, Wt, H, sets, weights, LD), sr.set_reference(codes, R, Wt, H, sets, weights, np.float64)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.array(a, order="C")).to("cuda:0")
-
-
-def call(mx, X, indiv, R, Wt, H, sets, weights, scan=True, phi=True, device=False, env=None):
-    """one raw call of the C entry: dict(stat (nsets, n, 6), phi: list of (n, m, m) or None, score, var, z (snps, n), nobs) as numpy"""
-    L, p = mx.lib.check_library_handle(), mx.lib.ptr
-    snps = X.shape[0]
-    n = R.shape[1]
-    kh = H.shape[1] // n
-    ptr = np.zeros(len(sets) + 1, np.int64)
-    ptr[1:] = np.cumsum([len(s) for s in sets])
-    idx = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32) for s in sets]) if ptr[-1] else np.zeros(1, np.int32), np.int32)
-    wt = None if weights is None else np.ascontiguousarray(np.concatenate([np.asarray(w, np.float64) for w in weights] + [np.zeros(1)]))
-    nsets, total = len(sets), int(sum(len(s) ** 2 for s in sets)) * n
-    ops = [np.ascontiguousarray(X), np.ascontiguousarray(R.T), np.ascontiguousarray(Wt.T), np.ascontiguousarray(H.T) if kh else None]
-    outs = dict(score=np.full((n, snps), -7.5), var=np.full((n, snps), -7.5), z=np.full((n, snps), -7.5), stat=np.full((6 * n, nsets + 1), -7.5),
-                phi=np.full(total + 2, -7.5))
-    nobs = np.full(snps, -3, np.int32)
-    if device:
-        ops = [None if o is None else _dev(o) for o in ops]
-        outs = {k: _dev(v) for k, v in outs.items()}
-    old = {k: os.environ.get(k) for k in (env or {})}
-    try:
-        for k, v in (env or {}).items():
-            os.environ[k] = str(v)
-        rc = L.mxa_assoc_set(p(ops[0]), snps, indiv, p(ops[1]), indiv, p(ops[2]), indiv, p(ops[3]), indiv, n, kh, nsets, p(ptr), p(idx), p(wt),
-                             p(outs["score"]) if scan else None, p(outs["var"]) if scan else None, p(outs["z"]) if scan else None, snps, p(nobs) if scan else None,
-                             p(outs["stat"]), nsets + 1, p(outs["phi"]) if phi else None)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    assert rc == 0, mx.lib.last_error()
-    if device:
-        import torch
-        torch.cuda.synchronize()
-        outs = {k: v.cpu().numpy() for k, v in outs.items()}
-    assert np.all(outs["stat"][:, nsets] == -7.5) and np.all(outs["phi"][total:] == -7.5)          # nothing beyond row nsets - 1, nothing behind the last block
-    if not phi:
-        assert np.all(outs["phi"] == -7.5)
-    if not scan:
-        assert all(np.all(outs[k] == -7.5) for k in ("score", "var", "z")) and np.all(nobs == -3)
-    res = dict(stat=outs["stat"][:, :nsets].reshape(n, 6, nsets).transpose(2, 0, 1).copy(), score=outs["score"].T, var=outs["var"].T, z=outs["z"].T, nobs=nobs, phi=None)
-    if phi:
-        res["phi"], at = [], 0
-        for s in sets:
-            m = len(s)
-            res["phi"].append(outs["phi"][at:at + n * m * m].reshape(n, m, m).transpose(0, 2, 1).copy())
-            at += n * m * m
-    return res
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def same_results(a, b):
-    ok = same(a["stat"], b["stat"])
-    if a["phi"] is not None and b["phi"] is not None:
-        ok = ok and len(a["phi"]) == len(b["phi"]) and all(same(x, y) for x, y in zip(a["phi"], b["phi"]))
-    return ok
-
-
-def check_accuracy(got, refs, label):
-    ld, f64 = refs
-    worst = {}
-    for name, pick in [("Phi", lambda r: (r["phi"], r["sphi"]))] + [(NAMES[t], (lambda t: lambda r: (r["stat"][:, t], r["sstat"][:, t]))(t)) for t in range(6)]:
-        eps = max(sr.scaled_error(pick(b)[0], *pick(a)) for a, b in zip(ld, f64))
-        if name == "Phi":
-            err = max(sr.scaled_error(g, *pick(a)) for a, g in zip(ld, got["phi"]))
-        else:
-            t = NAMES.index(name)
-            err = max(sr.scaled_error(got["stat"][k, :, t], *pick(a)) for k, a in enumerate(ld))
-        worst[name] = (err, eps)
-        print(f"{label} {name:5s} scaled error {err:.3e}  eps {eps:.3e}  bound {16 * max(eps, sr.TOL):.3e}")
-    for name, (err, eps) in worst.items():
-        assert err <= 16 * max(eps, sr.TOL), (label, name, err, eps)
-    return worst
 
 
 @pytest.mark.parametrize("indiv,n,kh,missing,weighted", CASES)
